@@ -6,7 +6,15 @@ batch of synthetic input: a whole 128x128 frame (16 384 rays) with 64 coarse + 1
 through two 8-layer / 256-wide RenderRayNets (BASELINE configs[1]).  One ray-sample = one MLP
 evaluation of one sample point: 64 (coarse) + 192 (fine) = 256 per ray, 4 194 304 per step.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline `value`, `ms_per_step`, the roofline
+and per-kernel times of the timed loop's own event pairs).  Everything else the script measures or checks - the other
+precision modes, the render and training operating points, the --netwidth points, the training sections, the live PMC
+traffic passes, the CPU baselines, the comparisons with the CPU reference path and the strong-scaling frame check - runs
+only with `--full`.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32, at most
+64 MB in all: a fixed, seeded sample of rays when the outputs are larger); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 With N > 1 and no WORLD_SIZE in the environment the script launches its own N ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`); when a
@@ -15,7 +23,7 @@ GPUs than ranks are visible (dry runs of the multi-rank path on a 1-GPU box) the
 group runs on gloo.
 
 The headline `value` is measured in the reference's own arithmetic: exact fp32 (`--precision fp32`,
-v_mfma_f32_16x16x4_f32).  The operand-split modes on the 16-bit matrix cores are timed in the same run and
+v_mfma_f32_16x16x4_f32).  With `--full` the operand-split modes on the 16-bit matrix cores are timed in the same run and
 reported under `other_precisions_1gpu`, each with its algorithmic roofline fraction.
 
 Inputs are resident in HBM before the timed region.  Rays of independent frames shard across ranks
@@ -566,8 +574,43 @@ def train_section(precision, workload, data, rays, steps, world, rank, dev, back
                                          "loss_last": losses[-1]}, backend is not None)}
 
 
+# ---------------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SEED = 20240607
+
+
+def output_names(n_outputs, run_fine=1):
+    """File names of the pipelines' return tuples (models/*_pipeline.py: coarse rgb, fine rgb, [warp,] samples, [warped,] densities)."""
+    if n_outputs == 6:
+        return ["rgb", "rgb_fine", "warp_fine", "ray_samples_fine", "warped_samples_fine", "densities_fine"]
+    if n_outputs == 4:
+        return ["rgb", "rgb_fine", "ray_samples_fine", "densities_fine"] if run_fine else ["rgb", "rgb_fine", "ray_samples", "densities"]
+    return [f"out{i}" for i in range(n_outputs)]
+
+
+def dump_outputs(out_dir, named, limit=DUMP_LIMIT_BYTES):
+    """Write {name: numpy array} as out_dir/<name>.npy in float32 (float64 stays float64).  When the arrays hold more than
+    `limit` bytes (files included), every array keeps the same fixed, seeded sample of its rows (rays) - the same rows from
+    run to run.  Returns {name: {"shape": shape written, "rows_of": rows computed}}."""
+    import numpy as np
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in named.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    budget = limit - 4096 * len(arrs)          # (room for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for k, a in arrs.items():
+        n = a.shape[0] if a.ndim else 1
+        if total > budget and a.ndim:
+            keep = max(1, int(n * budget / total))
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        written[k] = {"shape": list(a.shape), "rows_of": n}
+    return written
+
+
 # ---------------------------------------------------------------------------------------------------- main
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -607,7 +650,20 @@ def main():
                          "models/append_vertices_pipeline.py:30-58), append_smpl_params differentiates the goal pose")
     ap.add_argument("--no-alt", action="store_true", help="skip the other precision modes")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes behind roofline.traffic")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: other precisions, operating and --netwidth points, training sections, live PMC "
+                         "traffic, CPU baselines and the comparisons with the CPU reference path (the options above that "
+                         "configure these take effect only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def main():
+    a = parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a.gpus))
@@ -706,13 +762,19 @@ def main():
             barrier(dev)
             elapsed = time.perf_counter() - t0
         kern = prof.summary()
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        named = dict(zip(output_names(len(out), run_fine), (t.detach().cpu().numpy() for t in out)))
+        if frame is not None:
+            named["rgb_fine_frame"] = frame.detach().cpu().numpy()
+        dumped = dump_outputs(a.dump_outputs, named)
     elapsed = max_over_ranks(elapsed, dev)
     per_rank = gather_per_rank({"rank": rank, "device": torch.cuda.get_device_name(dev),
                                 "arch": torch.cuda.get_device_properties(dev).gcnArchName, "device_index": dev.index,
                                 "rays_per_step": rays, "ms_per_step": elapsed_own / a.steps * 1e3,
                                 "value": a.steps * evals_per_step / elapsed_own}, grouped)
     strong_check = None
-    if strong and rank == 0:      # the assembled frame against this rank rendering the whole frame alone (outside the timed region)
+    if a.full and strong and rank == 0:      # the assembled frame against this rank rendering the whole frame alone (outside the timed region)
         with torch.no_grad():
             whole = pipe([torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in full_np])[1]
         strong_check = float((whole - frame).abs().max())
@@ -770,7 +832,7 @@ def main():
                 "peak_allocated_bytes": int(torch.cuda.max_memory_allocated(dev))}
 
     points = None
-    if a.points and world == 1 and not grouped:
+    if a.full and a.points and world == 1 and not grouped:
         points = [operating_point(n) for n in sorted({int(v) for v in a.points.split(",") if v.strip()}) if n <= rays]
         if 800 <= rays and run_fine:
             points.append(eval_without_no_grad(800))
@@ -832,7 +894,7 @@ def main():
                 "peak_tflops": PEAK_F32_MFMA_TFLOPS, "dtype": "f32"}
 
     width_points = None
-    if a.netwidth_points and world == 1 and not grouped and a.workload == "nerf" and run_fine and a.precision == "fp32":
+    if a.full and a.netwidth_points and world == 1 and not grouped and a.workload == "nerf" and run_fine and a.precision == "fp32":
         try:
             width_points = [netwidth_point(int(v)) for v in a.netwidth_points.split(",") if v.strip()]
         except Exception as e:
@@ -865,7 +927,7 @@ def main():
         return r
 
     alt = {}
-    if not a.no_alt:
+    if a.full and not a.no_alt:
         with torch.no_grad():
             for prec in sorted(MODES):
                 if prec == a.precision:
@@ -889,7 +951,7 @@ def main():
             pipe.set_precision(a.precision)
 
     train = train_alt = None
-    if a.train_rays > 0 and run_fine:
+    if a.full and a.train_rays > 0 and run_fine:
         try:
             loader = None
             if a.train_from_raygen:
@@ -929,7 +991,7 @@ def main():
         roof = roofline_of(a.precision, calls, avg_ms, upl)
         alg_bytes = upl * (12 + 16) + rays * 12       # positions in, raw out, one direction per ray
         roof["algorithmic_hbm_bytes_per_launch"] = alg_bytes
-        if world == 1 and not a.no_pmc:
+        if a.full and world == 1 and not a.no_pmc:
             child = ["--steps", "3", "--warmup", "1", "--cpu-rays", "0", "--train-rays", "0", "--no-alt", "--no-pmc",
                      "--precision", a.precision, "--workload", a.workload, "--res", str(a.res), "--points", ""]
             if a.coarse_only:
@@ -968,6 +1030,8 @@ def main():
             "precision": a.precision,
             "kernels_ms_per_step": {k: v[1] / a.steps for k, v in sorted(kern.items())},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if grouped:     # an N > 1 record proves itself: who took part, on which devices, how long each rank took
             line["per_rank"] = per_rank
             line["collective"] = (dict(collective_info(backend, frame_rays * 3, "all-gather of the rendered rows (rgb_fine) into the "
@@ -1011,7 +1075,7 @@ def main():
             line["train"] = train
         if train_alt:
             line["train_other_precisions"] = train_alt
-        if world == 1 and a.cpu_rays > 0:
+        if a.full and world == 1 and a.cpu_rays > 0:
             # (append_vertices: the reference materialises 83 KB per sample - a far smaller sample fills the time budget)
             n = min(a.cpu_rays if a.workload != "append_vertices" else min(a.cpu_rays, 64), rays)
             info, ref = cpu_baseline(a.workload, params, data_np, n, run_fine)

@@ -202,3 +202,39 @@ def test_quality_keys_of_the_bench_line():
     same = bench.quality_keys([out[0], torch.from_numpy(cpu)], [cpu, cpu], gt, 64, None, None, None)
     assert same["psnr_db_hip_vs_cpu_reference_render"] is None and same["psnr_delta_db_vs_oracle"] == 0.0
     json.dumps(same)
+
+
+def test_plain_run_options():
+    """A plain run measures the headline only: --full (everything else) is off by default, --steps sets the timed steps."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_names_dtypes_and_size_bound(tmp_path):
+    """--dump-outputs: float32 .npy files named after the pipeline's return tuple; above the byte bound every array keeps the
+    same seeded sample of rows, identical from run to run."""
+    assert bench.output_names(4) == ["rgb", "rgb_fine", "ray_samples_fine", "densities_fine"]
+    assert bench.output_names(4, run_fine=0)[2:] == ["ray_samples", "densities"] and len(bench.output_names(6)) == 6
+    rng = np.random.default_rng(3)
+    named = {"rgb": rng.random((1000, 3)), "samples": rng.random((1000, 40, 3)).astype(np.float32),
+             "idx": np.arange(1000, dtype=np.int64)}
+    w = bench.dump_outputs(str(tmp_path / "all"), named)
+    assert w["samples"] == {"shape": [1000, 40, 3], "rows_of": 1000}
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in named}
+    assert got["rgb"].dtype == np.float64 and got["samples"].dtype == np.float32 and got["idx"].dtype == np.float32
+    assert np.array_equal(got["samples"], named["samples"]) and np.array_equal(got["idx"], np.arange(1000))
+    limit = 200_000
+    for d in ("a", "b"):
+        w = bench.dump_outputs(str(tmp_path / d), named, limit=limit)
+        assert sum(os.path.getsize(tmp_path / d / (k + ".npy")) for k in named) <= limit
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in named}
+    b = {k: np.load(tmp_path / "b" / (k + ".npy")) for k in named}
+    rows = a["idx"].astype(np.int64)
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0) and w["idx"]["rows_of"] == 1000
+    assert all(np.array_equal(a[k], b[k]) for k in named)
+    assert np.array_equal(a["samples"], named["samples"][rows]) and np.array_equal(a["rgb"], named["rgb"][rows])

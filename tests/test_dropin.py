@@ -1,6 +1,7 @@
-"""smpl_nerf_amd.dropin against the real reference checkout (build container only: skipped where /root/reference is
-absent, i.e. on the GPU box).  Wiring only - no compute: after install() the reference's own Solver / inference modules
-hold the HIP-backed classes and operators."""
+"""smpl_nerf_amd.dropin against a stand-in checkout written per test: the reference's module layout (namespace packages
+models/ and solver/ beside utils.py) with the import forms the drop-in has to follow - `from torchsearchsorted import
+searchsorted` in utils.py (utils.py:14), `from utils import ...` and `from models.x import Y` copies in models/*.py and
+solver/*.py.  Wiring only - no compute: after install() those modules hold the HIP-backed classes and operators."""
 import importlib
 import importlib.util
 import os
@@ -8,28 +9,47 @@ import sys
 
 import pytest
 
-REF = os.environ.get("SNERF_REFERENCE", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "models")), reason="reference checkout not present")
+# stand-in modules: path -> source (the reference's names and import forms, no behaviour)
+STAND_IN = {
+    "utils.py": (
+        "from torchsearchsorted import searchsorted\n\n\n"
+        "class PositionalEncoder():\n"
+        "    def __init__(self, number_frequencies, include_identity):\n"
+        "        self.number_frequencies = number_frequencies\n"
+        "        self.include_identity = include_identity\n\n\n"
+        "def raw2outputs(*args, **kw):\n    raise NotImplementedError\n\n\n"
+        "def sample_pdf(*args, **kw):\n    raise NotImplementedError\n\n\n"
+        "def fine_sampling(*args, **kw):\n    raise NotImplementedError\n"),
+    "models/render_ray_net.py": "class RenderRayNet:\n    pass\n",
+    "models/warp_field_net.py": "class WarpFieldNet:\n    pass\n",
+    "models/nerf_pipeline.py": ("from utils import raw2outputs, fine_sampling, PositionalEncoder\n\n\n"
+                                "class NerfPipeline:\n    pass\n"),
+    "models/smpl_nerf_pipeline.py": ("from models.nerf_pipeline import NerfPipeline\n\n\n"
+                                     "class SmplNerfPipeline(NerfPipeline):\n    pass\n"),
+    "models/append_smpl_params_pipeline.py": ("from models.nerf_pipeline import NerfPipeline\n"
+                                              "from utils import fine_sampling, raw2outputs\n\n\n"
+                                              "class AppendSmplParamsPipeline(NerfPipeline):\n    pass\n"),
+    "solver/nerf_solver.py": ("from models.nerf_pipeline import NerfPipeline\nfrom utils import PositionalEncoder\n\n\n"
+                              "class NerfSolver:\n    pass\n"),
+    "solver/smpl_nerf_solver.py": ("from models.smpl_nerf_pipeline import SmplNerfPipeline\n"
+                                   "from solver.nerf_solver import NerfSolver\n\n\n"
+                                   "class SmplNerfSolver(NerfSolver):\n    pass\n"),
+}
+TOP = ("utils", "models", "solver", "torchsearchsorted")
 
 
-def test_install_rebinds_the_reference_modules():
-    here = os.path.dirname(os.path.abspath(__file__))
-    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(here, "golden", "make_golden.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
+def stand_in_checkout(root):
+    for rel, src in STAND_IN.items():
+        path = root / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(src)
+    return str(root)
+
+
+def test_install_rebinds_the_reference_modules(tmp_path):
+    ref = stand_in_checkout(tmp_path / "checkout")
     before = set(sys.modules)
-    for name in ("cv2", "imageio"):                      # third-party modules the image lacks; never called here
-        mg._stub(name)
-    tm = mg._stub("trimesh")
-    tm.base = mg._stub("trimesh.base", Trimesh=object)
-    tm.ray = mg._stub("trimesh.ray")
-    tm.ray.ray_triangle = mg._stub("trimesh.ray.ray_triangle", RayMeshIntersector=object)
-    try:
-        importlib.import_module("torch.utils.tensorboard")
-    except Exception:
-        mg._stub("torch.utils.tensorboard", SummaryWriter=object)
-    saved = {k: sys.modules.get(k) for k in list(sys.modules)
-             if k.split(".")[0] in ("utils", "models", "solver", "torchsearchsorted")}
+    saved = {k: sys.modules.get(k) for k in list(sys.modules) if k.split(".")[0] in TOP}
     saved_path, saved_meta = list(sys.path), list(sys.meta_path)
     from smpl_nerf_amd import dropin, nets, ops, pipelines
     try:
@@ -37,13 +57,13 @@ def test_install_rebinds_the_reference_modules():
             sys.modules.pop(k, None)
         dropin._installed = False
         dropin._originals.clear()
-        dropin.install(REF)
+        dropin.install(ref)
         import torchsearchsorted
         assert torchsearchsorted.searchsorted is ops.searchsorted
-        U = importlib.import_module("utils")                       # the reference's utils.py (imports torchsearchsorted)
+        U = importlib.import_module("utils")                       # the checkout's utils.py (imports torchsearchsorted)
         assert U.searchsorted is ops.searchsorted and U.raw2outputs is ops.raw2outputs
         assert U.fine_sampling is ops.fine_sampling and U.sample_pdf is ops.sample_pdf
-        NS = importlib.import_module("solver.nerf_solver")         # solver/nerf_solver.py:5 `from models.nerf_pipeline import ...`
+        NS = importlib.import_module("solver.nerf_solver")         # `from models.nerf_pipeline import NerfPipeline`
         assert NS.NerfPipeline is pipelines.NerfPipeline
         SS = importlib.import_module("solver.smpl_nerf_solver")
         assert SS.SmplNerfPipeline is pipelines.SmplNerfPipeline
@@ -53,22 +73,23 @@ def test_install_rebinds_the_reference_modules():
         assert NP.NerfPipeline is pipelines.NerfPipeline and NP.raw2outputs is ops.raw2outputs
         assert importlib.import_module("models.warp_field_net").WarpFieldNet is nets.WarpFieldNet
         AP = importlib.import_module("models.append_smpl_params_pipeline")
-        assert AP.AppendSmplParamsPipeline is pipelines.AppendSmplParamsPipeline
-        # the reference's own encoder class is kept and is what our pipelines accept
+        assert AP.AppendSmplParamsPipeline is pipelines.AppendSmplParamsPipeline and AP.fine_sampling is ops.fine_sampling
+        # the checkout's own encoder class is kept and is what our pipelines accept
         enc = U.PositionalEncoder(10, False)
+        assert U.PositionalEncoder is not None and not isinstance(enc, ops.PositionalEncoder)
         pipe = NS.NerfPipeline(nets.RenderRayNet(), nets.RenderRayNet(), object(), enc, U.PositionalEncoder(4, False))
         d = pipe.model_coarse.desc_for_encoders(pipe.position_encoder, pipe.direction_encoder)
         assert (d.pos_freqs, d.dir_freqs, d.pos_identity) == (10, 4, 0)
-        assert dropin.install(REF) == 0                            # idempotent
+        assert dropin.install(ref) == 0                            # idempotent
     finally:
         sys.meta_path[:] = saved_meta
         sys.path[:] = saved_path
-        for k in [k for k in sys.modules if k.split(".")[0] in ("utils", "models", "solver", "torchsearchsorted")]:
+        for k in [k for k in sys.modules if k.split(".")[0] in TOP]:
             sys.modules.pop(k, None)
         sys.modules.update({k: v for k, v in saved.items() if v is not None})
         dropin._installed = False
-        for k in set(sys.modules) - before:               # the stand-ins and whatever the reference pulled in
-            if k.split(".")[0] in ("cv2", "imageio", "trimesh", "camera", "render", "make_golden") or k == "torch.utils.tensorboard":
+        for k in set(sys.modules) - before:               # whatever the checkout pulled in
+            if k.split(".")[0] in TOP:
                 sys.modules.pop(k, None)
 
 
@@ -76,12 +97,13 @@ def test_install_normalises_the_root(tmp_path):
     """a symlinked root matches the (absolute, resolved) module paths; a sibling directory whose name merely
     starts with the root's does not; a missing directory is an error."""
     from smpl_nerf_amd import dropin
+    ref = stand_in_checkout(tmp_path / "checkout")
     link = tmp_path / "ref_link"
-    os.symlink(REF, link)
+    os.symlink(ref, link)
     root = dropin._norm_root(str(link))
-    assert root == os.path.join(os.path.realpath(REF), "")
-    assert dropin._under(os.path.join(REF, "utils.py"), root)
-    assert not dropin._under(os.path.realpath(REF) + "2/utils.py", root)
+    assert root == os.path.join(os.path.realpath(ref), "")
+    assert dropin._under(os.path.join(ref, "utils.py"), root)
+    assert not dropin._under(os.path.realpath(ref) + "2/utils.py", root)
     with pytest.raises(FileNotFoundError):
         dropin.install(str(tmp_path / "nope"))
 

@@ -556,7 +556,7 @@ def test_bench_launches_its_own_ranks(dev):
     n_gpus = 2 (gloo when only one GPU is visible)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--cpu-rays", "0", "--train-rays", "512", "--train-steps", "2", "--no-alt", "--no-pmc"],
+                        "--cpu-rays", "0", "--train-rays", "512", "--train-steps", "2", "--no-alt", "--no-pmc", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -581,7 +581,7 @@ def test_bench_strong_scaling_mode_assembles_one_frame(dev):
     equals the single-rank render bit for bit (rays are independent), value counts the frame once."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", "strong", "--steps", "2",
-                        "--warmup", "1", "--cpu-rays", "0", "--train-rays", "0", "--no-alt", "--no-pmc"],
+                        "--warmup", "1", "--cpu-rays", "0", "--train-rays", "0", "--no-alt", "--no-pmc", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

@@ -519,7 +519,7 @@ def test_bench_takes_its_rccl_branch_at_world_size_one():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SNERF_BENCH_FORCE_GROUP="1", SNERF_DIST_BACKEND="nccl")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-rays", "0",
-                        "--train-rays", "512", "--train-steps", "2", "--no-alt", "--no-pmc", "--points="],
+                        "--train-rays", "512", "--train-steps", "2", "--no-alt", "--no-pmc", "--points=", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

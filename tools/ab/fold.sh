@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 for cfg in ${CONFIGS:-1:4 0:4 2:4}; do
   f=${cfg%%:*}; pf=${cfg##*:}
   rm -rf /tmp/abprof
-  SNERF_WGRAD_FOLD=$f rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abprof -- python $R/bench.py --steps 1 --warmup 1 --no-pmc --no-alt --cpu-rays 0 --points= --train-rays ${RAYS:-4096} --train-steps 10 > /tmp/ab.json 2>/dev/null
+  SNERF_WGRAD_FOLD=$f rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abprof -- python $R/bench.py --full --steps 1 --warmup 1 --no-pmc --no-alt --cpu-rays 0 --points= --train-rays ${RAYS:-4096} --train-steps 10 > /tmp/ab.json 2>/dev/null
   python - <<PY
 import json,glob,csv
 l=json.loads(open('/tmp/ab.json').read().strip().splitlines()[-1]); t=l['train']

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc_train
 mkdir -p $OUT
-ARGS="--steps 1 --warmup 1 --no-pmc --no-alt --cpu-rays 0 --points= --train-rays 4096 --train-steps 3"
+ARGS="--full --steps 1 --warmup 1 --no-pmc --no-alt --cpu-rays 0 --points= --train-rays 4096 --train-steps 3"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU SQ_INSTS_VALU --output-format csv -d /tmp/p1 -- python $R/bench.py $ARGS > /dev/null 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VMEM SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d /tmp/p2 -- python $R/bench.py $ARGS > /dev/null 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VMEM --output-format csv -d /tmp/p3 -- python $R/bench.py $ARGS > /dev/null 2>&1

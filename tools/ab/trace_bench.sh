@@ -1,9 +1,9 @@
 #!/bin/bash
-# rocprofv3 kernel trace of a bench.py training section: bash tools/ab/trace_bench.sh <workload> <train-rays> [top-n]
+# rocprofv3 kernel trace of a bench.py --full training section: bash tools/ab/trace_bench.sh <workload> <train-rays> [top-n]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 rm -rf /tmp/tb
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tb -- python $R/bench.py --workload $1 --steps 1 --warmup 1 --no-pmc --no-alt --cpu-rays 0 --points= --train-rays $2 --train-steps 20 > /tmp/tb.json 2>/tmp/tb.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tb -- python $R/bench.py --full --workload $1 --steps 1 --warmup 1 --no-pmc --no-alt --cpu-rays 0 --points= --train-rays $2 --train-steps 20 > /tmp/tb.json 2>/tmp/tb.err
 python - <<'PY'
 import json
 d = json.loads(open('/tmp/tb.json').read().strip().splitlines()[-1])

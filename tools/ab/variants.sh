@@ -7,7 +7,7 @@ cp $R/smpl_nerf_amd/csrc/libsmplnerf_hip.so /tmp/orig.so
 for lib in $LIBS; do
   cp $R/$lib $R/smpl_nerf_amd/csrc/libsmplnerf_hip.so
   rm -rf /tmp/abprof
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abprof -- python $R/bench.py --steps 1 --warmup 1 --no-pmc --no-alt --cpu-rays 0 --points= --train-rays ${RAYS:-4096} --train-steps 10 > /tmp/ab.json 2>/dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abprof -- python $R/bench.py --full --steps 1 --warmup 1 --no-pmc --no-alt --cpu-rays 0 --points= --train-rays ${RAYS:-4096} --train-steps 10 > /tmp/ab.json 2>/dev/null
   python - <<PY
 import json,glob,csv
 l=json.loads(open('/tmp/ab.json').read().strip().splitlines()[-1]); t=l['train']

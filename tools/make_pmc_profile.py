@@ -20,10 +20,10 @@ ALG_BYTES = {1048576: 1048576 * (12 + 16) + 16384 * 12, 3145728: 3145728 * (12 +
 
 
 def main(sq, fetch, write, tsq=None, tfetch=None, twrite=None):
-    out = {"command": "render rows: rocprofv3 --pmc <counters> --output-format csv -- python bench.py --steps 3 --warmup 1 "
+    out = {"command": "render rows: rocprofv3 --pmc <counters> --output-format csv -- python bench.py --full --steps 3 --warmup 1 "
                       "--cpu-rays 0 --train-rays 0 --no-pmc (three separate passes: SQ/GRBM, FETCH_SIZE, WRITE_SIZE; every "
                       "dispatch of a render kernel is a frame launch of the bench); training rows: the same three passes of "
-                      "python bench.py --steps 1 --warmup 1 --cpu-rays 0 --train-steps 3 --no-pmc",
+                      "python bench.py --full --steps 1 --warmup 1 --cpu-rays 0 --train-steps 3 --no-pmc",
            "note": "FETCH_SIZE/WRITE_SIZE are KB; mfma_pipe_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs * "
                    "1024 SIMDs); effective clock = GRBM_GUI_ACTIVE / 8 / duration.  MI355X_MICROARCH.md: FETCH_SIZE "
                    "under-reports wide 16 B/lane streams by 2x; these kernels read 4 B/lane inputs and take their weights "
@@ -96,7 +96,7 @@ def generic(sq, fetch, write, kernels, command):
 if __name__ == "__main__":
     if sys.argv[1] == "--smpl-nerf":
         generic(*sys.argv[2:5], SMPL_KERNELS,
-                "rocprofv3 --pmc <counters> --output-format csv -- python bench.py --workload smpl_nerf --steps 3 --warmup 1 "
+                "rocprofv3 --pmc <counters> --output-format csv -- python bench.py --full --workload smpl_nerf --steps 3 --warmup 1 "
                 "--cpu-rays 0 --train-steps 3 --no-pmc --no-alt --points= (three separate passes: SQ/GRBM, FETCH_SIZE, WRITE_SIZE)")
     else:
         main(*sys.argv[1:7])
