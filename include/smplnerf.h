@@ -160,10 +160,11 @@ SNERF_API int snerf_sample_pdf_f32(const float *z, const float *weights, const f
                          snerf_stream_t stream);
 
 /* Strict variants (SURVEY 8b `strict_cumsum`): index parity with the reference FROM THE SAME WEIGHTS.  The reference's
- * pdf is weights / torch.sum(weights) (utils.py:201); torch's CPU sum is a vectorised fp32 cascade whose bits depend on the
- * host's SIMD width, and a 1-ulp difference in it moves ~0.15 % of the indices.  `tot` [B] = that sum as the reference's
- * host evaluated it (e.g. (weights[:, 1:-1] + 1e-5).sum(-1) with torch on the CPU); every other step is independent of
- * the evaluation order, so cdf, inds and the samples are then bit-identical to the reference's. */
+ * pdf is weights / torch.sum(weights) (utils.py:201); torch's CPU sum is an fp32 cascade over 8-lane vectors, one fixed
+ * order on x86 hosts (default, AVX2 and AVX-512 builds alike), and a 1-ulp difference in it moves ~0.1 % of the indices.
+ * `tot` [B] = that sum (snerf_reference_sum_f32 below computes it on the device; or (weights[:, 1:-1] + 1e-5).sum(-1) with
+ * torch on the CPU); every other step is independent of the evaluation order, so cdf, inds and the samples are then
+ * bit-identical to the reference's. */
 SNERF_API int snerf_sample_pdf_strict_f32(const float *z, const float *weights, const float *u, const float *o, const float *d,
                                 const float *tot, int64_t B, int Nc, int Nf, int64_t *inds, float *z_samples,
                                 float *z_fine, float *pts, snerf_stream_t stream);
@@ -175,6 +176,21 @@ SNERF_API int snerf_sample_pdf_bins_strict_f32(const float *bins, const float *w
  * z_samples [B, Nf].  2 <= Nb <= 1023. */
 SNERF_API int snerf_sample_pdf_bins_f32(const float *bins, const float *weights, const float *u, int64_t B,
                               int Nb, int Nf, int64_t *inds, float *z_samples, snerf_stream_t stream);
+
+/* torch.sum(x[b, :n] + add, -1) as torch's CPU kernel evaluates it for a contiguous fp32 row (x86 hosts); 0 <= n <= 32767.
+ * x [B, row_stride] (row_stride >= n when B > 1), out [B].  The order (an fp32 cascade over 8-lane vectors with 4 columns and
+ * 4 levels) is written out in smpl_nerf_amd/csrc/refsum.h.  The device form runs one wavefront per row; the _host form takes
+ * host pointers and runs on the calling thread (no HIP call).  B == 0 is a no-op.  Rows of 32768 elements and more may be
+ * split over threads by torch and are not covered.  Added after 0.1.9 without a version bump: a C host detects these two
+ * entries and SNERF_REFERENCE_SUM by looking up snerf_reference_sum_f32 with dlsym. */
+SNERF_API int snerf_reference_sum_f32(const float *x, int64_t row_stride, int64_t B, int n, float add, float *out,
+                                      snerf_stream_t stream);
+SNERF_API int snerf_reference_sum_host_f32(const float *x_host, int64_t row_stride, int64_t B, int n, float add, float *out_host);
+/* OR into `precision` of snerf_render_rays_f32 / _add_f32 / _smpl_f32 and of the training entries that sample
+ * (snerf_nerf_train_{grads,step}[_ig]_f32, snerf_nerf_train_step_dp[_ig]_f32, snerf_smpl_nerf_train_{grads,step}[_aux]_f32,
+ * snerf_smpl_nerf_train_step_dp_f32): the hierarchical sampler takes the reference-order sum (strict mode, no host round
+ * trip).  Without it the sum is the fp64 one, as before. */
+#define SNERF_REFERENCE_SUM 0x100
 
 /* Backward of sample_pdf(bins, weights, args) (utils.py:194-228 under autograd; fine_sampling detaches its result,
  * utils.py:260, so no pipeline needs it): d_z_samples [B, Nf] -> d_bins [B, Nb], d_weights [B, Nb-1], with the forward's

@@ -12,6 +12,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libsmplnerf_hip.so")
 SPLIT_F16X3 = 16   # include/smplnerf.h SNERF_SPLIT_F16X3: nsplit / precision code of the two-part fp16 kernel
+REFERENCE_SUM = 0x100   # include/smplnerf.h SNERF_REFERENCE_SUM: ORed into a precision, the sampler sums in torch's CPU order
 
 SNERF_OK = 0
 
@@ -78,6 +79,8 @@ SIGNATURES = {
     "snerf_sample_pdf_bins_strict_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, _P, _P, _P]),
     "snerf_sample_pdf_bins_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P, _P, _P]),
     "snerf_sample_pdf_bins_f32": (c_int, [_P, _P, _P, c_int64, c_int, c_int, _P, _P, _P]),
+    "snerf_reference_sum_f32": (c_int, [_P, c_int64, c_int64, c_int, c_float, _P, _P]),
+    "snerf_reference_sum_host_f32": (c_int, [_P, c_int64, c_int64, c_int, c_float, _P]),
     "snerf_mlp_param_floats": (c_int64, [POINTER(MlpDesc)]),
     "snerf_mlp_packed_floats": (c_int64, [POINTER(MlpDesc)]),
     "snerf_mlp_pack_f32": (c_int, [POINTER(MlpDesc), _P, _P, _P]),

@@ -145,6 +145,8 @@ static int snerf::render_rays_impl(const snerf_mlp_desc *desc_coarse, const void
                                    int white_background, void *workspace, float *rgb, float *rgb_fine, float *samples_fine,
                                    float *densities_fine, snerf_stream_t stream) {
     using namespace snerf;
+    const bool refsum = (precision & SNERF_REFERENCE_SUM) != 0;
+    precision &= ~SNERF_REFERENCE_SUM;
     if (precision != 0 && precision != 2 && precision != 3 && precision != SNERF_SPLIT_F16X3)
         return fail(SNERF_E_BADARG, "render_rays: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)");
     if (B < 0 || Nc < 1 || Nf < 0) return fail(SNERF_E_BADARG, "render_rays: bad B/Nc/Nf");
@@ -184,8 +186,8 @@ static int snerf::render_rays_impl(const snerf_mlp_desc *desc_coarse, const void
                                       alpha_c, stream)))
         return rc;
     // hierarchical samples (:47) and the fine net on them (:49-65)
-    if ((rc = snerf_sample_pdf_f32(z_vals, weights_c, u, rays_o, rays_d, B, Nc, Nf, nullptr, z_samples, z_fine,
-                                   samples_fine, stream)))
+    if ((rc = sample_pdf_merged(refsum, z_vals, weights_c, u, rays_o, rays_d, B, Nc, Nf, nullptr, z_samples, z_fine,
+                                samples_fine, stream)))
         return rc;
     const int N = Nc + Nf;
     if ((rc = mlp(desc_fine, packed_fine, precision, samples_fine, rays_d, B * N, N, raw_f, stream, additional, fold_ws, fold_f))) return rc;
@@ -209,6 +211,8 @@ extern "C" int snerf_render_rays_smpl_f32(const snerf_mlp_desc *desc_coarse, con
                                           float *warp_fine, float *samples_fine, float *warped_fine,
                                           float *densities_fine, snerf_stream_t stream) {
     using namespace snerf;
+    const bool refsum = (precision & SNERF_REFERENCE_SUM) != 0;
+    precision &= ~SNERF_REFERENCE_SUM;
     if (precision != 0 && precision != 2 && precision != 3 && precision != SNERF_SPLIT_F16X3)
         return fail(SNERF_E_BADARG, "render_rays_smpl: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)");
     if (B < 0 || Nc < 1 || Nf < 1) return fail(SNERF_E_BADARG, "render_rays_smpl: bad B/Nc/Nf");
@@ -238,8 +242,8 @@ extern "C" int snerf_render_rays_smpl_f32(const snerf_mlp_desc *desc_coarse, con
                                       stream)))
         return rc;
     // hierarchical samples on the un-warped ray (:68), then the fine stage (:71-98)
-    if ((rc = snerf_sample_pdf_f32(z_vals, weights_c, u, rays_o, rays_d, B, Nc, Nf, nullptr, z_samples, z_fine, samples_fine,
-                                   stream)))
+    if ((rc = sample_pdf_merged(refsum, z_vals, weights_c, u, rays_o, rays_d, B, Nc, Nf, nullptr, z_samples, z_fine, samples_fine,
+                                stream)))
         return rc;
     if ((rc = warp(desc_warp, packed_warp, precision, samples_fine, pose_enc, rays_o, B * N, N, warp_fine, warped_fine, sdirs_f,
                    ws + sw.fold, sw.fold_bytes, stream)))

@@ -14,13 +14,16 @@
 // are evaluated in fp64 and rounded to fp32 once per element - identical to torch's CPU cumsum and
 // independent of the reduction order, which is what makes a wavefront scan legal here; every other
 // operation is a single correctly-rounded fp32 op in the reference's order (no FMA contraction).
-// The *_strict entry points take the normalising sums as an input (`tot` [B], what torch.sum returned on the
-// reference's host): the only step of the reference whose bits depend on the host.
+// The normalising sum is the one step whose bits depend on the order: the reference's torch.sum is ATen's fp32 cascade
+// over 8-lane vectors, the same order on every x86 host (refsum.h).  Strict mode reproduces it: the *_strict entry points
+// take the sums as an input (`tot` [B]), and the REFSUM instantiations (SNERF_REFERENCE_SUM in the render / training
+// entries) compute them in the kernel, 32 lanes of the wave each running one (column, vector lane) of that cascade.
 //
 // The merge exploits that both lists are ascending (rank = own index + cross-rank by bisection);
 // a wave-uniform check detects an out-of-order input and falls back to an O(n^2) stable rank sort,
 // so the output is always exactly sorted(cat(z, samples)).
 #include "snerf_common.h"
+#include "refsum.h"
 
 namespace snerf {
 
@@ -57,10 +60,33 @@ __device__ __forceinline__ int count_below(const float *__restrict__ row, int n,
 }
 __host__ __device__ inline int sp_round4(int n) { return (n + 3) & ~3; }
 
+// torch.sum(x[0 .. n) + a) in refsum.h's order by one wave, the result in every lane.  Lane 8k + l (k < 4) runs the level
+// cascade of ILP column k for vector lane l (row r of that column: x[32r + 8k + l] - the 32 lanes read 32 adjacent floats),
+// lanes l < 8 add the leftover vectors and fold the columns, then every lane adds the scalar tail and the 8 lane partials in
+// the same order (uniform operands: no broadcast needed).  n < 8: every lane evaluates the scalar form.
+__device__ __forceinline__ float refsum_wave(const float *__restrict__ x, int n, float a, int lane) {
+    using refsum::add;
+    if (n < refsum::V) return refsum::row(x, n, a);
+    const int nv = n >> 3, rows = nv >> 2;
+    const int k = (lane >> 3) & 3, l = lane & 7;
+    float c = 0.f;
+    if (lane < 32) c = refsum::cascade([&](int64_t r) { return add(x[32 * (int)r + 8 * k + l], a); }, rows);
+    if (lane < 8)
+        for (int v = 4 * rows; v < nv; ++v) c = add(c, add(x[8 * v + l], a));
+    const float c1 = __shfl(c, lane + 8), c2 = __shfl(c, lane + 16), c3 = __shfl(c, lane + 24);
+    c = add(add(add(c, c1), c2), c3);
+    float fin = 0.f;
+    for (int j = 8 * nv; j < n; ++j) fin = add(fin, add(x[j], a));
+#pragma unroll
+    for (int q = 0; q < refsum::V; ++q) fin = add(fin, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), q)));
+    return fin;
+}
+
 // DIRECT = the literal sample_pdf(bins, weights) calling convention (utils.py:194): `z` holds the
 // bins [B, Nc-1] and `weights` the interior weights [B, Nc-2]; no merge, no points.
 // NC, NF > 0: the sample counts as compile-time constants (the launcher picks the 64 + 128 instance for the pipeline's shape).
-template <bool DIRECT, int NC, int NF>
+// REFSUM: the normalising sum in the reference's order (refsum_wave) instead of fp64; tot_in is not read.
+template <bool DIRECT, int NC, int NF, bool REFSUM = false>
 __global__ __launch_bounds__(SP_THREADS) void sample_pdf_kernel(
     const float *__restrict__ z, const float *__restrict__ weights, const float *__restrict__ u,
     const float *__restrict__ o, const float *__restrict__ d, const float *__restrict__ tot_in, int64_t B, int Nc_arg, int Nf_arg,
@@ -91,7 +117,8 @@ __global__ __launch_bounds__(SP_THREADS) void sample_pdf_kernel(
     bool sorted_in = true;
     if (DIRECT) {
         for (int i = lane; i < Nb; i += WAVE) s_bins[i] = zr[i];
-        for (int i = lane + 1; i <= M; i += WAVE) part += (double)__fadd_rn(wr[i], 1e-5f);
+        if (!REFSUM)
+            for (int i = lane + 1; i <= M; i += WAVE) part += (double)__fadd_rn(wr[i], 1e-5f);
     } else {
         for (int i = lane; i < Nc; i += WAVE) {
             const float zi = zr[i];
@@ -101,13 +128,12 @@ __global__ __launch_bounds__(SP_THREADS) void sample_pdf_kernel(
                 s_bins[i] = __fmul_rn(0.5f, __fadd_rn(zn, zi));
                 sorted_in = sorted_in && (zi <= zn);
             }
-            if (i >= 1 && i <= M) part += (double)__fadd_rn(wr[i], 1e-5f);
+            if (!REFSUM && i >= 1 && i <= M) part += (double)__fadd_rn(wr[i], 1e-5f);
         }
     }
-    // strict mode: the caller supplies the normalising sum torch.sum produced on the reference's host (utils.py:201; a
-    // vectorised fp32 cascade whose bits depend on that host's SIMD width) - every later step is order-independent, so
-    // cdf, indices and samples then equal the reference's bit for bit
-    const float tot = tot_in ? tot_in[ray] : (float)wave_sum(part);
+    // strict mode: the normalising sum in torch's CPU order (utils.py:201; refsum.h), computed here (REFSUM) or supplied by the
+    // caller - every later step is order-independent, so cdf, indices and samples then equal the reference's bit for bit
+    const float tot = REFSUM ? refsum_wave(wr + 1, M, 1e-5f, lane) : tot_in ? tot_in[ray] : (float)wave_sum(part);
 
     // ---- cdf = [0, cumsum(pdf)] : fp64 wavefront scan with a carry between 64-element chunks ----
     if (lane == 0) s_cdf[0] = 0.f;
@@ -307,9 +333,50 @@ __global__ __launch_bounds__(SP_THREADS) void sample_pdf_bwd_kernel(const float 
 }  // namespace snerf
 
 namespace snerf {
+// snerf_reference_sum_f32: one wave per row, the sampler's own strict-sum routine
+__global__ __launch_bounds__(SP_THREADS) void reference_sum_kernel(const float *__restrict__ x, int64_t row_stride, int64_t B, int n,
+                                                                   float a, float *__restrict__ out) {
+    const int lane = lane_id();
+    const int64_t row = (int64_t)blockIdx.x * SP_WAVES + (threadIdx.x >> 6);
+    if (row >= B) return;
+    const float s = refsum_wave(x + row * row_stride, n, a, lane);
+    if (lane == 0) out[row] = s;
+}
+
 static int launch_sample_pdf(bool direct, const float *z, const float *weights, const float *u, const float *o,
                              const float *d, const float *tot, int64_t B, int Nc, int Nf, int64_t *inds, float *z_samples,
-                             float *z_fine, float *pts, snerf_stream_t stream);
+                             float *z_fine, float *pts, snerf_stream_t stream, bool refsum = false);
+
+// the merged sampler of the render / training entries (snerf_common.h): refsum = SNERF_REFERENCE_SUM was ORed into their precision
+int sample_pdf_merged(bool refsum, const float *z, const float *weights, const float *u, const float *o, const float *d, int64_t B,
+                      int Nc, int Nf, int64_t *inds, float *z_samples, float *z_fine, float *pts, snerf_stream_t stream) {
+    return launch_sample_pdf(false, z, weights, u, o, d, nullptr, B, Nc, Nf, inds, z_samples, z_fine, pts, stream, refsum);
+}
+}  // namespace snerf
+
+static int reference_sum_args(const float *x, int64_t row_stride, int64_t B, int n, float *out, const char *what) {
+    if (B < 0 || n < 0 || n > snerf::refsum::MAX_N)
+        return snerf::fail(SNERF_E_BADARG, "%s: need B >= 0 and 0 <= n <= %d (got %lld, %d)", what, snerf::refsum::MAX_N, (long long)B, n);
+    if (B > 1 && row_stride < n) return snerf::fail(SNERF_E_BADARG, "%s: row_stride %lld < n %d", what, (long long)row_stride, n);
+    if (B > 0 && (!out || (n > 0 && !x))) return snerf::fail(SNERF_E_BADARG, "%s: x / out is null", what);
+    return SNERF_OK;
+}
+
+extern "C" int snerf_reference_sum_f32(const float *x, int64_t row_stride, int64_t B, int n, float add, float *out,
+                                       snerf_stream_t stream) {
+    using namespace snerf;
+    if (int rc = reference_sum_args(x, row_stride, B, n, out, "reference_sum")) return rc;
+    if (B == 0) return SNERF_OK;
+    const int64_t grid = (B + SP_WAVES - 1) / SP_WAVES;
+    if (grid > 0x7fffffffLL) return fail(SNERF_E_BADARG, "reference_sum: B too large");
+    hipLaunchKernelGGL(reference_sum_kernel, dim3((unsigned)grid), dim3(SP_THREADS), 0, (hipStream_t)stream, x, row_stride, B, n, add, out);
+    return check_launch("reference_sum");
+}
+
+extern "C" int snerf_reference_sum_host_f32(const float *x_host, int64_t row_stride, int64_t B, int n, float add, float *out_host) {
+    if (int rc = reference_sum_args(x_host, row_stride, B, n, out_host, "reference_sum_host")) return rc;
+    for (int64_t b = 0; b < B; ++b) out_host[b] = snerf::refsum::row(x_host + b * row_stride, n, add);
+    return SNERF_OK;
 }
 
 extern "C" int snerf_sample_pdf_f32(const float *z, const float *weights, const float *u, const float *o,
@@ -343,7 +410,7 @@ extern "C" int snerf_sample_pdf_bins_f32(const float *bins, const float *weights
 
 static int snerf::launch_sample_pdf(bool direct, const float *z, const float *weights, const float *u, const float *o,
                                     const float *d, const float *tot, int64_t B, int Nc, int Nf, int64_t *inds,
-                                    float *z_samples, float *z_fine, float *pts, snerf_stream_t stream) {
+                                    float *z_samples, float *z_fine, float *pts, snerf_stream_t stream, bool refsum) {
     if (B < 0) return fail(SNERF_E_BADARG, "sample_pdf: negative B");
     if (Nc < 3 || Nc > 1024 || Nf < 1 || Nf > 1024)
         return fail(SNERF_E_BADARG, "sample_pdf: need 3 <= Nc <= 1024 and 1 <= Nf <= 1024 (got %d, %d; below three coarse samples the "
@@ -359,10 +426,19 @@ static int snerf::launch_sample_pdf(bool direct, const float *z, const float *we
             hipFuncSetAttribute(reinterpret_cast<const void *>(sample_pdf_kernel<true, 0, 0>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
             return fail(SNERF_E_LAUNCH, "sample_pdf: cannot raise dynamic LDS limit");
+        if (refsum && hipFuncSetAttribute(reinterpret_cast<const void *>(sample_pdf_kernel<false, 0, 0, true>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
+            return fail(SNERF_E_LAUNCH, "sample_pdf: cannot raise dynamic LDS limit");
     }
     const int64_t grid = (B + SP_WAVES - 1) / SP_WAVES;
     if (grid > 0x7fffffffLL) return fail(SNERF_E_BADARG, "sample_pdf: B too large");
-    if (direct)
+    if (refsum && Nc == 64 && Nf == 128)   // (refsum: the merged form only - the entries that take the flag merge)
+        hipLaunchKernelGGL((sample_pdf_kernel<false, 64, 128, true>), dim3((unsigned)grid), dim3(SP_THREADS), lds, (hipStream_t)stream,
+                           z, weights, u, o, d, nullptr, B, Nc, Nf, inds, z_samples, z_fine, pts);
+    else if (refsum)
+        hipLaunchKernelGGL((sample_pdf_kernel<false, 0, 0, true>), dim3((unsigned)grid), dim3(SP_THREADS), lds, (hipStream_t)stream, z,
+                           weights, u, o, d, nullptr, B, Nc, Nf, inds, z_samples, z_fine, pts);
+    else if (direct)
         hipLaunchKernelGGL((sample_pdf_kernel<true, 0, 0>), dim3((unsigned)grid), dim3(SP_THREADS), lds, (hipStream_t)stream, z,
                            weights, u, o, d, tot, B, Nc, Nf, inds, z_samples, z_fine, pts);
     else if (Nc == 64 && Nf == 128)

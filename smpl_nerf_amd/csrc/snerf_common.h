@@ -48,6 +48,11 @@ struct Tuning {
 };
 const Tuning &tuning();
 
+// sampler.hip: snerf_sample_pdf_f32's merged form for the render / training entries; refsum = the normalising sum in the
+// reference's order (SNERF_REFERENCE_SUM ORed into their precision), computed in the kernel
+int sample_pdf_merged(bool refsum, const float *z, const float *weights, const float *u, const float *o, const float *d, int64_t B,
+                      int Nc, int Nf, int64_t *inds, float *z_samples, float *z_fine, float *pts, snerf_stream_t stream);
+
 __host__ __device__ inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 constexpr int WAVE = 64;

@@ -469,6 +469,8 @@ static int nerf_train_grads_impl(const snerf_mlp_desc *desc_coarse, const void *
                                  snerf_stream_t stream, snerf_stream_t aux_stream, snerf_comm_t comm, float *flat_g, int64_t flat_n,
                                  const snerf_input_grads *ig = nullptr) {
     using namespace snerf;
+    const bool refsum = (precision & SNERF_REFERENCE_SUM) != 0;
+    precision &= ~SNERF_REFERENCE_SUM;
     if (precision != 0 && !split_code(precision))
         return fail(SNERF_E_BADARG, "nerf_train_grads: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)");
     if (!batch) return fail(SNERF_E_BADARG, "nerf_train_grads: batch is null");
@@ -568,8 +570,8 @@ static int nerf_train_grads_impl(const snerf_mlp_desc *desc_coarse, const void *
         if ((rc = fwd_train(desc_coarse, packed_coarse, x, d, add, b * Nc, Nc, raw_c, act_c))) return rc;
         if ((rc = snerf_composite_fwd_f32(raw_c, z, d, 0, nz_c, b, Nc, wb, rgb_c, Nf > 0 ? weights_c : nullptr, nullptr, stream))) return rc;
         if (Nf > 0) {
-            if ((rc = snerf_sample_pdf_f32(z, weights_c, batch->u, batch->rays_o + r0 * 3, d, b, Nc, Nf, nullptr, nullptr, z_fine,
-                                           pts_f, stream)))
+            if ((rc = sample_pdf_merged(refsum, z, weights_c, batch->u, batch->rays_o + r0 * 3, d, b, Nc, Nf, nullptr, nullptr, z_fine,
+                                        pts_f, stream)))
                 return rc;
             if ((rc = fwd_train(desc_fine, packed_fine, pts_f, d, add, b * N, N, raw_f, act_f))) return rc;
             if ((rc = snerf_composite_fwd_f32(raw_f, z_fine, d, 0, nz_f, b, N, wb, rgb_fo, nullptr, nullptr, stream))) return rc;
@@ -784,6 +786,8 @@ static int smpl_nerf_train_grads_impl(const snerf_mlp_desc *desc_coarse, const v
                                       void *workspace, float *grad_coarse, float *grad_fine, float *grad_warp, float *loss, float *rgb,
                                       float *rgb_fine, snerf_stream_t stream, snerf_stream_t aux_stream) {
     using namespace snerf;
+    const bool refsum = (precision & SNERF_REFERENCE_SUM) != 0;
+    precision &= ~SNERF_REFERENCE_SUM;
     if (precision != 0 && !split_code(precision))
         return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)");
     if (!batch) return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: batch is null");
@@ -863,7 +867,7 @@ static int smpl_nerf_train_grads_impl(const snerf_mlp_desc *desc_coarse, const v
         if ((rc = fwd_train(desc_coarse, packed_coarse, warped_c, sdirs_c, b * Nc, Nc, raw_c, act_c))) return rc;
         if ((rc = snerf_composite_fwd_f32(raw_c, z, sdirs_c, 1, nz_c, b, Nc, wb, rgb_c, Nf > 0 ? weights_c : nullptr, nullptr, stream))) return rc;
         if (Nf > 0) {   // hierarchical samples on the un-warped ray (:68), then the fine stage (:71-98)
-            if ((rc = snerf_sample_pdf_f32(z, weights_c, batch->u, o, d, b, Nc, Nf, nullptr, nullptr, z_fine, pts_f, stream))) return rc;
+            if ((rc = sample_pdf_merged(refsum, z, weights_c, batch->u, o, d, b, Nc, Nf, nullptr, nullptr, z_fine, pts_f, stream))) return rc;
             if ((rc = snerf_warp_fwd_train_f32(desc_warp, packed_warp, pts_f, pe, o, b * N, N, warp_f, warped_f, sdirs_f, act_wf, stream))) return rc;
             if ((rc = fwd_train(desc_fine, packed_fine, warped_f, sdirs_f, b * N, N, raw_f, act_f))) return rc;
             if ((rc = snerf_composite_fwd_f32(raw_f, z_fine, d, 0, nz_f, b, N, wb, rgb_fo, nullptr, nullptr, stream))) return rc;

@@ -12,6 +12,7 @@ no CPU implementation here: a CPU tensor is an error, like a missing library.
 """
 from __future__ import annotations
 
+import platform
 from typing import Optional, Tuple
 
 import torch
@@ -244,20 +245,71 @@ def uniform_u(n: int, device) -> torch.Tensor:
     return u
 
 
-def reference_normalising_sum(interior_weights: torch.Tensor) -> torch.Tensor:
-    """torch.sum(weights + 1e-5, -1) of utils.py:200-201 evaluated by torch's own CPU kernel on this host - exactly what
-    the reference's CPU path computes here (a vectorised fp32 cascade: its bits depend on the host's SIMD width, which
-    is why it cannot be restated portably) - returned on the weights' device.  Costs a device -> host -> device round
-    trip; used only in strict mode (args.strict_cumsum)."""
+# the rows device_reference_sum_ok() holds the library's order against torch.sum with
+_REFSUM_PROBE_LENGTHS = (1, 7, 8, 9, 31, 32, 33, 62, 63, 126, 190, 511, 512, 513, 1022)
+_REFSUM_MAX_N = 32767          # include/smplnerf.h snerf_reference_sum_f32
+_REFSUM_OK = None
+
+
+def _reference_sum_probe() -> bool:
+    """True when torch.sum on this host follows the order of snerf_reference_sum_*_f32 (csrc/refsum.h): an x86_64 machine, a
+    capability whose float sum runs on 8-lane vectors (DEFAULT, AVX2, AVX512) and a CPU-only comparison of the host entry
+    with torch.sum on fixed seeded rows.  No device work, so it is safe under graph capture."""
+    if platform.machine().lower() not in ("x86_64", "amd64"):
+        return False
+    if torch.backends.cpu.get_cpu_capability() not in ("DEFAULT", "AVX2", "AVX512"):
+        return False
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(2026)
+    for n in _REFSUM_PROBE_LENGTHS:
+        x = torch.pow(10.0, torch.rand((4, n), generator=g) * 6 - 3).float().contiguous()
+        for add in (0.0, 1e-5):
+            got = torch.empty(4, dtype=torch.float32)
+            check(lib.snerf_reference_sum_host_f32(x.data_ptr(), n, 4, n, add, got.data_ptr()), "snerf_reference_sum_host_f32")
+            if not torch.equal(torch.sum(x + add, -1).view(torch.int32), got.view(torch.int32)):
+                return False
+    return True
+
+
+def device_reference_sum_ok() -> bool:
+    """Whether the device can stand in for torch's CPU sum in strict mode (decided once per process, _reference_sum_probe)."""
+    global _REFSUM_OK
+    if _REFSUM_OK is None:
+        _REFSUM_OK = _reference_sum_probe()
+    return _REFSUM_OK
+
+
+def _host_normalising_sum(interior_weights: torch.Tensor) -> torch.Tensor:
+    """The sum by torch's own CPU kernel: a device -> host -> device round trip and a sync (hosts whose torch.sum takes
+    another order than the library's, see device_reference_sum_ok)."""
     w = interior_weights.detach().to("cpu", torch.float32)
     return torch.sum(w + 1e-5, -1).to(interior_weights.device).contiguous()
+
+
+def reference_normalising_sum(interior_weights: torch.Tensor) -> torch.Tensor:
+    """torch.sum(weights + 1e-5, -1) of utils.py:200-201 bit for bit as torch's CPU kernel evaluates it - exactly what the
+    reference's CPU path computes (ATen's fp32 cascade over 8-lane vectors: one order on every x86 host, restated in
+    csrc/refsum.h) - returned on the weights' device.  Where device_reference_sum_ok(), snerf_reference_sum_f32 computes it on
+    the device (no sync; graph-capturable); elsewhere torch computes it on the host.  Used in strict mode (args.strict_cumsum)."""
+    w = interior_weights.detach()
+    if w.dim() != 2 or not w.is_cuda or w.dtype != torch.float32 or w.shape[1] > _REFSUM_MAX_N or not device_reference_sum_ok():
+        return _host_normalising_sum(interior_weights)
+    if w.shape[1] > 1 and w.stride(1) != 1 or w.shape[0] > 1 and w.stride(0) < w.shape[1]:
+        w = w.contiguous()
+    B, n = w.shape
+    out = torch.empty(B, device=w.device, dtype=torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(w.device), _lib.timed("reference_sum"):
+        check(lib.snerf_reference_sum_f32(ptr(w), w.stride(0) if B > 1 else n, B, n, 1e-5, ptr(out), current_stream()),
+              "snerf_reference_sum_f32")
+    return out
 
 
 def hierarchical_samples(ray_translation, ray_direction, z_vals, weights, number_fine_samples: int,
                          want_inds=False, want_samples=False, tot=None, strict=False):
     """One launch of snerf_sample_pdf_f32 -> dict(z_fine, pts, [inds], [z_samples]).  strict (or an explicit `tot` [B]):
-    the normalising sums come from the reference's own host kernel, so the indices equal the reference's bit for bit
-    from the same weights (snerf_sample_pdf_strict_f32)."""
+    the normalising sums in the order of torch's CPU kernel (reference_normalising_sum), so the indices equal the reference's
+    bit for bit from the same weights (snerf_sample_pdf_strict_f32)."""
     B, Nc = z_vals.shape
     Nf = int(number_fine_samples)
     dev = z_vals.device

@@ -57,9 +57,10 @@ class PipelineArgs:
     human_pose_encoding is 1 (config_parser.py:72 has 0, with which the reference's own smpl_nerf fine branch crashes,
     quirk Q5).  PipelineArgs.reference_defaults() returns the parser's values.
 
-    strict_cumsum (not a reference field): 1 = the hierarchical sampler takes its normalising sums from
-    torch's CPU kernel on this host, like the reference's CPU path, so that the sample indices equal the reference's bit
-    for bit from the same weights (ops.reference_normalising_sum; costs a host round trip per call)."""
+    strict_cumsum (not a reference field): 1 = the hierarchical sampler takes its normalising sums in the order
+    of torch's CPU kernel, like the reference's CPU path, so that the sample indices equal the reference's bit for bit from
+    the same weights (ops.reference_normalising_sum: on the device where ops.device_reference_sum_ok(), with the single-call
+    render and the one-call training step; a host round trip per call elsewhere)."""
 
     def __init__(self, **kw):
         self.sigma_noise_std = 0.0
@@ -77,6 +78,12 @@ class PipelineArgs:
         d = dict(sigma_noise_std=1.0, white_background=0, run_fine=1, number_fine_samples=128, human_pose_encoding=0)
         d.update(kw)
         return cls(**d)
+
+
+def _sampler_prec(prec: int, args) -> int:
+    """The precision code of a render entry with SNERF_REFERENCE_SUM ORed in when strict mode's sum runs on the device."""
+    from . import _lib
+    return prec | (_lib.REFERENCE_SUM if getattr(args, "strict_cumsum", 0) and ops.device_reference_sum_ok() else 0)
 
 
 class NerfPipeline(nn.Module):
@@ -115,9 +122,12 @@ class NerfPipeline(nn.Module):
         """Inference (autograd off) goes through the single C-ABI call of render_rays() - what inference.py:251-252's
         `pipeline(data)` costs a host then is one call instead of five; same kernels, same results (tools/ab/fuzz_render.py holds
         them bit for bit).  The five-call form stays for autograd, for a _lib.profile() (which brackets every launch with an
-        event pair: bench.py's roofline), for the strict sampler (a host round trip) and for the checkers' keep_fine."""
+        event pair: bench.py's roofline), for the checkers' keep_fine and for the strict sampler on hosts where it is a host
+        round trip (ops.device_reference_sum_ok() false)."""
         from . import _lib
-        if torch.is_grad_enabled() or _lib._PROFILE is not None or self.keep_fine or getattr(self.args, "strict_cumsum", 0):
+        if torch.is_grad_enabled() or _lib._PROFILE is not None or self.keep_fine:
+            return False
+        if getattr(self.args, "strict_cumsum", 0) and not ops.device_reference_sum_ok():
             return False
         nets = [self.model_coarse, self.model_fine] + ([self.model_warp_field] if hasattr(self, "model_warp_field") else [])
         if len({getattr(m, "precision", "fp32") for m in nets}) != 1 or any(getattr(m, "_layered", False) for m in nets):
@@ -188,7 +198,7 @@ class NerfPipeline(nn.Module):
         nc, nf = self._noise((B, Nc), dev), (self._noise((B, N), dev) if Nf else None)
         x, o, d, z = (t.contiguous() for t in (ray_samples, ray_translation, ray_direction, z_vals))
         with _on_device(dev), _lib.timed("render_rays"):
-            check(lib.snerf_render_rays_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), prec, ptr(x), ptr(o),
+            check(lib.snerf_render_rays_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), _sampler_prec(prec, args), ptr(x), ptr(o),
                                             ptr(d), ptr(z), ptr(u), ptr(nc), ptr(nf), B, Nc, Nf,
                                             1 if args.white_background else 0, ptr(ws), ptr(rgb), ptr(rgb_fine),
                                             ptr(samples_fine), ptr(dens), current_stream()), "snerf_render_rays_f32")
@@ -301,7 +311,7 @@ class SmplNerfPipeline(NerfPipeline):
         nc, nf = self._noise((B, Nc), dev), self._noise((B, N), dev)
         x, o, d, z = (t.contiguous() for t in (ray_samples, ray_translation, ray_direction, z_vals))
         with _on_device(dev), _lib.timed("render_rays_smpl"):
-            check(lib.snerf_render_rays_smpl_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), wdesc, ptr(wpacked), prec,
+            check(lib.snerf_render_rays_smpl_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), wdesc, ptr(wpacked), _sampler_prec(prec, args),
                                                  ptr(x), ptr(o), ptr(d), ptr(z), ptr(pose_enc), ptr(u), ptr(nc), ptr(nf), B, Nc,
                                                  Nf, 1 if args.white_background else 0, ptr(ws), ptr(rgb), ptr(rgb_fine),
                                                  ptr(warp_f), ptr(samples_f), ptr(warped_f), ptr(dens), current_stream()),
@@ -446,7 +456,7 @@ class AppendSmplParamsPipeline(NerfPipeline):
         nc, nf = self._noise((B, Nc), dev), (self._noise((B, N), dev) if Nf else None)
         x, o, d, z = (t.contiguous() for t in (ray_samples, ray_translation, ray_direction, z_vals))
         with _on_device(dev), _lib.timed("render_rays_add"):
-            check(lib.snerf_render_rays_add_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), prec, ptr(x), ptr(o), ptr(d),
+            check(lib.snerf_render_rays_add_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), _sampler_prec(prec, args), ptr(x), ptr(o), ptr(d),
                                                 ptr(z), ptr(pose), ptr(u), ptr(nc), ptr(nf), B, Nc, Nf,
                                                 1 if args.white_background else 0, ptr(ws), ptr(rgb), ptr(rgb_fine),
                                                 ptr(samples_fine), ptr(dens), current_stream()), "snerf_render_rays_add_f32")

@@ -25,6 +25,7 @@ import time
 import torch
 
 from . import _lib
+from . import ops
 from . import dist as sdist
 from . import io as sio
 
@@ -567,8 +568,10 @@ class DataParallelTrainer:
         (oc_off, oc_n), (of_off, of_n) = oc["seg"]
         g_c = self._flat_g.data_ptr() + 4 * oc_off
         g_f = self._flat_g.data_ptr() + 4 * of_off
+        # the precision argument of the entries: the nets' code, with SNERF_REFERENCE_SUM for the strict sampler (nets_c keeps ns)
+        prec = ns | (_lib.REFERENCE_SUM if getattr(args, "strict_cumsum", 0) else 0)
         head = (descs[0], packed[0].data_ptr(), packed_t[0].data_ptr(), descs[1] if Nf else None, _lib.ptr(packed[1]),
-                _lib.ptr(packed_t[1]), ns, ctypes.byref(cb), self.rays_per_chunk, oc["ws"].data_ptr(), g_c, g_f if Nf else None,
+                _lib.ptr(packed_t[1]), prec, ctypes.byref(cb), self.rays_per_chunk, oc["ws"].data_ptr(), g_c, g_f if Nf else None,
                 loss.data_ptr(), rgb.data_ptr(), rgb_fine.data_ptr())
         opt = self.optim
         aux = oc["aux"].cuda_stream if oc["aux"] is not None else None
@@ -581,7 +584,7 @@ class DataParallelTrainer:
         if W is not None:
             w_off = W["seg"][0]
             g_w = self._flat_g.data_ptr() + 4 * w_off
-            head = head[:6] + (wdesc, packed_w.data_ptr(), packed_t_w.data_ptr(), ns, ctypes.byref(cb), pose_enc.data_ptr(),
+            head = head[:6] + (wdesc, packed_w.data_ptr(), packed_t_w.data_ptr(), prec, ctypes.byref(cb), pose_enc.data_ptr(),
                                self.rays_per_chunk, oc["ws"].data_ptr(), g_c, g_f if Nf else None, g_w, loss.data_ptr(), rgb.data_ptr(),
                                rgb_fine.data_ptr())
             # (the _aux_ forms, 0.1.8: small chunks run the coarse chain of the backward on the auxiliary stream; comm may be None)
@@ -694,7 +697,9 @@ class DataParallelTrainer:
         if oc is not None and len(batch) == (6 if (oc["warp"] is not None or oc["posed"]) else 5) and \
                 all(t.is_cuda and (not t.requires_grad or (i == 4 and oc["posed"] and not oc["verts"])) and
                     (t.dtype == torch.float32 or (oc["verts"] and i == 4)) for i, t in enumerate(batch)) and \
-                not getattr(self.pipeline.args, "strict_cumsum", 0):
+                not (getattr(self.pipeline.args, "strict_cumsum", 0) and not ops.device_reference_sum_ok()):
+            # (strict mode: the call takes SNERF_REFERENCE_SUM where the device sums in torch's CPU order; a host round trip
+            # through the autograd path elsewhere)
             # (a batch tensor that wants a gradient: the autograd path - except the pose rows of the pose-conditioned pipelines,
             # whose gradient the call returns, r05)
             return self._step_one_call(oc, batch)
