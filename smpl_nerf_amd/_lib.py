@@ -61,6 +61,19 @@ class InputGrads(ctypes.Structure):      # snerf_input_grads
     _fields_ = [("d_additional", _P), ("params_coarse", _P), ("params_fine", _P)]
 
 
+# The parameter groups the training entries share, in the header's order:
+_D, _W = POINTER(MlpDesc), POINTER(WarpDesc)
+_NETS = [_D, _P, _P, _D, _P, _P]      # desc, packed, packed_t of the coarse and of the fine net
+_WARP = [_W, _P, _P]                  # desc_warp, packed_warp, packed_t_warp
+# precision, batch, rays_per_chunk, workspace, grad_coarse, grad_fine, loss, rgb, rgb_fine
+_NERF = _NETS + [c_int, POINTER(NerfBatch), c_int64, _P, _P, _P, _P, _P, _P]
+# precision, batch, pose_enc, rays_per_chunk, workspace, grad_coarse, grad_fine, grad_warp, loss, rgb, rgb_fine
+_SMPL = _NETS + _WARP + [c_int, POINTER(NerfBatch), _P, c_int64, _P, _P, _P, _P, _P, _P, _P]
+_ADAM = [POINTER(AdamState), POINTER(AdamRange), c_int, POINTER(AdamNet), c_int]      # adam, ranges_host, n_ranges, nets_host, n_nets
+_IG = [POINTER(InputGrads)]
+_OFF = [c_int64]                      # warp_param_offset
+# (what follows them: the optional comm, then stream and, where the entry has one, aux_stream)
+
 # name -> (restype, argtypes); must list every symbol include/smplnerf.h declares
 SIGNATURES = {
     "snerf_version": (c_int, []),
@@ -135,23 +148,15 @@ SIGNATURES = {
     "snerf_mlp_stream_slots": (c_int, [POINTER(MlpDesc), _P, _P, c_int, _P]),
     "snerf_smpl_nerf_train_workspace_bytes": (c_int64, [POINTER(MlpDesc), POINTER(MlpDesc), POINTER(WarpDesc), c_int64, c_int, c_int,
                                                         c_int64]),
-    "snerf_smpl_nerf_train_grads_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, POINTER(WarpDesc), _P, _P, c_int,
-                                                POINTER(NerfBatch), _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "snerf_smpl_nerf_train_step_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, POINTER(WarpDesc), _P, _P, c_int,
-                                               POINTER(NerfBatch), _P, c_int64, _P, _P, _P, _P, _P, _P, _P, POINTER(AdamState),
-                                               POINTER(AdamRange), c_int, POINTER(AdamNet), c_int, c_int64, _P]),
+    "snerf_smpl_nerf_train_grads_f32": (c_int, _SMPL + [_P]),
+    "snerf_smpl_nerf_train_step_f32": (c_int, _SMPL + _ADAM + _OFF + [_P]),
     "snerf_warp_repack_f32": (c_int, [POINTER(WarpDesc), _P, c_int64, c_int64, _P, _P, _P]),
     "snerf_adam_step_f32": (c_int, [POINTER(AdamState), POINTER(AdamRange), c_int, POINTER(AdamNet), c_int, _P]),
     "snerf_nerf_train_workspace_bytes": (c_int64, [POINTER(MlpDesc), POINTER(MlpDesc), c_int64, c_int, c_int, c_int64]),
-    "snerf_nerf_train_grads_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, c_int, POINTER(NerfBatch), c_int64,
-                                           _P, _P, _P, _P, _P, _P, _P, _P]),
-    "snerf_nerf_train_step_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, c_int, POINTER(NerfBatch), c_int64,
-                                          _P, _P, _P, _P, _P, _P, POINTER(AdamState), POINTER(AdamRange), c_int, POINTER(AdamNet), c_int, _P, _P]),
-    "snerf_nerf_train_grads_ig_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, c_int, POINTER(NerfBatch), c_int64,
-                                              _P, _P, _P, _P, _P, _P, POINTER(InputGrads), _P, _P]),
-    "snerf_nerf_train_step_ig_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, c_int, POINTER(NerfBatch), c_int64,
-                                             _P, _P, _P, _P, _P, _P, POINTER(AdamState), POINTER(AdamRange), c_int, POINTER(AdamNet), c_int,
-                                             POINTER(InputGrads), _P, _P]),
+    "snerf_nerf_train_grads_f32": (c_int, _NERF + [_P, _P]),
+    "snerf_nerf_train_step_f32": (c_int, _NERF + _ADAM + [_P, _P]),
+    "snerf_nerf_train_grads_ig_f32": (c_int, _NERF + _IG + [_P, _P]),
+    "snerf_nerf_train_step_ig_f32": (c_int, _NERF + _ADAM + _IG + [_P, _P]),
     # any --netwidth: nn.Linear as stand-alone GEMMs (csrc/linear.hip)
     "snerf_linear_fwd_f32": (c_int, [_P, c_int64, c_int, c_int64, _P, c_int64, c_int, _P, c_int, c_int, _P, c_int64, _P]),
     "snerf_linear_bwd_input_f32": (c_int, [_P, c_int64, c_int, c_int64, _P, c_int64, c_int, c_int, _P, c_int64, _P]),
@@ -164,20 +169,11 @@ SIGNATURES = {
     "snerf_comm_destroy": (c_int, [_P]),
     "snerf_comm_info": (c_int, [_P, POINTER(ctypes.c_int32), POINTER(ctypes.c_int32)]),
     "snerf_comm_allreduce_avg_f32": (c_int, [_P, _P, c_int64, _P]),
-    "snerf_nerf_train_step_dp_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, c_int, POINTER(NerfBatch), c_int64,
-                                             _P, _P, _P, _P, _P, _P, POINTER(AdamState), POINTER(AdamRange), c_int, POINTER(AdamNet), c_int,
-                                             _P, _P, _P]),
-    "snerf_nerf_train_step_dp_ig_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, c_int, POINTER(NerfBatch), c_int64,
-                                                _P, _P, _P, _P, _P, _P, POINTER(AdamState), POINTER(AdamRange), c_int, POINTER(AdamNet), c_int,
-                                                POINTER(InputGrads), _P, _P, _P]),
-    "snerf_smpl_nerf_train_step_dp_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, POINTER(WarpDesc), _P, _P, c_int,
-                                                  POINTER(NerfBatch), _P, c_int64, _P, _P, _P, _P, _P, _P, _P, POINTER(AdamState),
-                                                  POINTER(AdamRange), c_int, POINTER(AdamNet), c_int, c_int64, _P, _P]),
-    "snerf_smpl_nerf_train_grads_aux_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, POINTER(WarpDesc), _P, _P, c_int,
-                                                    POINTER(NerfBatch), _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "snerf_smpl_nerf_train_step_aux_f32": (c_int, [POINTER(MlpDesc), _P, _P, POINTER(MlpDesc), _P, _P, POINTER(WarpDesc), _P, _P, c_int,
-                                                   POINTER(NerfBatch), _P, c_int64, _P, _P, _P, _P, _P, _P, _P, POINTER(AdamState),
-                                                   POINTER(AdamRange), c_int, POINTER(AdamNet), c_int, c_int64, _P, _P, _P]),
+    "snerf_nerf_train_step_dp_f32": (c_int, _NERF + _ADAM + [_P, _P, _P]),
+    "snerf_nerf_train_step_dp_ig_f32": (c_int, _NERF + _ADAM + _IG + [_P, _P, _P]),
+    "snerf_smpl_nerf_train_step_dp_f32": (c_int, _SMPL + _ADAM + _OFF + [_P, _P]),
+    "snerf_smpl_nerf_train_grads_aux_f32": (c_int, _SMPL + [_P, _P]),
+    "snerf_smpl_nerf_train_step_aux_f32": (c_int, _SMPL + _ADAM + _OFF + [_P, _P, _P]),
 }
 
 _lib = None

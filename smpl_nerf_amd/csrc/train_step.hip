@@ -457,168 +457,310 @@ namespace snerf {
 // dp_comm.hip
 int dp_allreduce_avg(snerf_comm_t comm, float *buf, int64_t begin, int64_t end, int64_t skip_begin, int64_t skip_end, hipStream_t stream,
                      const char *what);
+
+// ------------------------------------------------------------------------------------------------
+// the argument record of the training entries: everything a gradient half reads, by name.  Every exported entry fills one
+// and hands it to nerf_train_grads / smpl_nerf_train_grads; the step entries go on to finish_step.
+// ------------------------------------------------------------------------------------------------
+struct NetArgs {
+    const snerf_mlp_desc *desc;
+    const void *packed, *packed_t;
+    float *grad;
+};
+struct WarpArgs {
+    const snerf_warp_desc *desc;
+    float *packed, *packed_t;    // read by the gradient half; re-packed behind Adam by the step entries
+    float *grad;
+    const float *pose_enc;
+};
+struct TrainArgs {
+    NetArgs coarse, fine;
+    WarpArgs warp;               // the smpl_nerf form only
+    int precision;               // may carry SNERF_REFERENCE_SUM
+    const snerf_nerf_batch *batch;
+    int64_t rays_per_chunk;
+    void *workspace;
+    float *loss, *rgb, *rgb_fine;
+    snerf_stream_t stream, aux_stream;
+    // comm != NULL (the data-parallel step): the flat gradient buffer flat_g[0 .. flat_n), which holds the nets' gradients as
+    // segments, is averaged over the ranks between the backward and Adam
+    snerf_comm_t comm;
+    float *flat_g;
+    int64_t flat_n;
+    const snerf_input_grads *input_grads;
+};
+struct AdamCall {
+    const snerf_adam_state *adam;
+    const snerf_adam_range *ranges_host;
+    int n_ranges;
+    const snerf_adam_net *nets_host;
+    int n_nets;
+};
+
+// What follows the gradient half in a step entry.  smpl_who != NULL is the smpl_nerf form: its one collective (comm != NULL: the
+// whole flat buffer; the nerf form issues its two inside the gradient half, behind the last chunk), Adam, the warp net's streams
+// re-packed from the new parameters.
+static int finish_step(const TrainArgs &a, const AdamCall &o, const char *smpl_who = nullptr, int64_t warp_param_offset = 0) {
+    int rc;
+    if (smpl_who && a.comm && (rc = dp_allreduce_avg(a.comm, a.flat_g, 0, a.flat_n, 0, 0, (hipStream_t)a.stream, smpl_who))) return rc;
+    if ((rc = snerf_adam_step_f32(o.adam, o.ranges_host, o.n_ranges, o.nets_host, o.n_nets, a.stream))) return rc;
+    if (!smpl_who) return SNERF_OK;
+    return snerf_warp_repack_f32(a.warp.desc, o.adam ? o.adam->params : nullptr, o.adam ? o.adam->n_params : 0, warp_param_offset,
+                                 a.warp.packed, a.warp.packed_t, a.stream);
 }
 
-// comm != NULL (the data-parallel step): the flat gradient buffer flat_g[0 .. flat_n), which holds grad_coarse / grad_fine as
-// segments, is averaged over the ranks behind the last chunk's backward - the coarse net's segment on the auxiliary stream beside
-// the fine net's backward when the two run concurrently, the rest on `stream` behind the join
-static int nerf_train_grads_impl(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
-                                 const snerf_mlp_desc *desc_fine, const void *packed_fine, const void *packed_t_fine,
-                                 int precision, const snerf_nerf_batch *batch, int64_t rays_per_chunk, void *workspace,
-                                 float *grad_coarse, float *grad_fine, float *loss, float *rgb, float *rgb_fine,
-                                 snerf_stream_t stream, snerf_stream_t aux_stream, snerf_comm_t comm, float *flat_g, int64_t flat_n,
-                                 const snerf_input_grads *ig = nullptr) {
-    using namespace snerf;
-    const bool refsum = (precision & SNERF_REFERENCE_SUM) != 0;
-    precision &= ~SNERF_REFERENCE_SUM;
-    if (precision != 0 && !split_code(precision))
-        return fail(SNERF_E_BADARG, "nerf_train_grads: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)");
-    if (!batch) return fail(SNERF_E_BADARG, "nerf_train_grads: batch is null");
-    const int64_t B = batch->B;
-    const int Nc = batch->Nc, Nf = batch->Nf, N = Nc + Nf;
-    if (B < (comm ? 0 : 1) || Nc < 1 || Nf < 0) return fail(SNERF_E_BADARG, "nerf_train_grads: need B >= 1, Nc >= 1, Nf >= 0");
-    if (comm && B == 0) {
-        // a rank whose shard ran out (RayBatchLoader allows unequal shards) still takes part in the step's collectives, in the
-        // order every other rank issues them, with a zero gradient
-        if (!flat_g || flat_n < 1 || !desc_coarse || !grad_coarse || !loss) return fail(SNERF_E_BADARG, "nerf_train_step_dp: null pointer");
-        const int64_t pc = snerf_mlp_param_floats(desc_coarse);
-        const int64_t c0 = grad_coarse - flat_g;
-        if (pc < 1 || c0 < 0 || c0 + pc > flat_n) return fail(SNERF_E_BADARG, "nerf_train_step_dp: grad_coarse must lie inside adam->grads[0 .. n_params)");
-        hipStream_t s0 = (hipStream_t)stream;
-        if (hipMemsetAsync(flat_g, 0, (size_t)flat_n * sizeof(float), s0) != hipSuccess ||
-            hipMemsetAsync(loss, 0, 3 * sizeof(float), s0) != hipSuccess)
-            return fail(SNERF_E_LAUNCH, "nerf_train_step_dp: memset failed");
-        if (int rc0 = dp_allreduce_avg(comm, flat_g, c0, c0 + pc, 0, 0, s0, "nerf_train_step_dp")) return rc0;
-        return dp_allreduce_avg(comm, flat_g, 0, flat_n, c0, c0 + pc, s0, "nerf_train_step_dp");
+// A rank of a data-parallel step whose shard ran out (B == 0; RayBatchLoader allows unequal shards): zero gradient, zero loss.
+// It still takes part in the step's collectives, in the order every other rank issues them: the caller goes on to those.
+static int dp_empty_shard(const TrainArgs &a, const char *who) {
+    hipStream_t s = (hipStream_t)a.stream;
+    if (hipMemsetAsync(a.flat_g, 0, (size_t)a.flat_n * sizeof(float), s) != hipSuccess ||
+        hipMemsetAsync(a.loss, 0, 3 * sizeof(float), s) != hipSuccess)
+        return fail(SNERF_E_LAUNCH, "%s: memset failed", who);
+    return SNERF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// what the two gradient halves share (`who` is the entry-name prefix of the error texts)
+// ------------------------------------------------------------------------------------------------
+struct Shape {
+    int precision;    // without SNERF_REFERENCE_SUM
+    bool refsum;
+    int64_t B, chunk;
+    int Nc, Nf, N;
+};
+// min_B = 0 admits the empty shard of a data-parallel step
+static int decode_shape(const TrainArgs &a, int64_t min_B, const char *who, Shape &sh) {
+    sh.refsum = (a.precision & SNERF_REFERENCE_SUM) != 0;
+    sh.precision = a.precision & ~SNERF_REFERENCE_SUM;
+    if (sh.precision != 0 && !split_code(sh.precision))
+        return fail(SNERF_E_BADARG, "%s: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)", who);
+    if (!a.batch) return fail(SNERF_E_BADARG, "%s: batch is null", who);
+    sh.B = a.batch->B;
+    sh.Nc = a.batch->Nc, sh.Nf = a.batch->Nf, sh.N = sh.Nc + sh.Nf;
+    if (sh.B < min_B || sh.Nc < 1 || sh.Nf < 0) return fail(SNERF_E_BADARG, "%s: need B >= 1, Nc >= 1, Nf >= 0", who);
+    sh.chunk = effective_chunk(sh.B, a.rays_per_chunk);
+    return SNERF_OK;
+}
+static int check_workspace_and_width(const TrainArgs &a, const Shape &sh, const char *who) {
+    if (!aligned(a.workspace, 256)) return fail(SNERF_E_ALIGN, "%s: workspace must be 256-byte aligned", who);
+    if (sh.precision != 0 && (a.coarse.desc->width != 256 || (sh.Nf > 0 && a.fine.desc->width != 256)))
+        return fail(SNERF_E_BADARG, "%s: the split-precision kernels exist for width 256", who);
+    return SNERF_OK;
+}
+
+// typed view of a carved workspace.  set[0]: the scratch of a net's backward; set[1]: the coarse net's own set when its backward
+// runs beside the fine net's (TrainWs::concurrent)
+struct BwdSet {
+    float *d_raw, *dy, *gpart;
+};
+struct TrainBufs {
+    float *raw_c, *weights_c, *z_fine, *pts_f, *raw_f, *d_rgb_c, *d_rgb_f, *act_c, *act_f, *contract;
+    double *loss_acc;
+    BwdSet set[2];
+};
+static float *at(void *workspace, int64_t off) { return reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + off); }
+static TrainBufs carve(const TrainWs &w, void *ws) {
+    TrainBufs m;
+    m.raw_c = at(ws, w.raw_c), m.weights_c = at(ws, w.weights_c), m.z_fine = at(ws, w.z_fine), m.pts_f = at(ws, w.pts_f);
+    m.raw_f = at(ws, w.raw_f), m.d_rgb_c = at(ws, w.d_rgb_c), m.d_rgb_f = at(ws, w.d_rgb_f), m.act_c = at(ws, w.act_c);
+    m.act_f = at(ws, w.act_f), m.contract = at(ws, w.contract);
+    m.loss_acc = reinterpret_cast<double *>(at(ws, w.loss_acc));
+    m.set[0] = {at(ws, w.d_raw), at(ws, w.dy), at(ws, w.gpart)};
+    m.set[1] = {at(ws, w.d_raw2), at(ws, w.dy2), at(ws, w.gpart2)};
+    return m;
+}
+
+// small chunks with an auxiliary stream: the coarse net's backward (the smpl_nerf form: the whole coarse chain) beside the fine
+// net's, on the second scratch set.  fork / join enqueue nothing when `on` is false.
+struct Concurrent {
+    bool on;
+    hipEvent_t ev_fork, ev_join;
+    hipStream_t s, aux;
+    snerf_stream_t stream_c;    // where the coarse backward runs
+    int fork(const char *who) const {
+        if (on && (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent(aux, ev_fork, 0) != hipSuccess))
+            return fail(SNERF_E_LAUNCH, "%s: cannot fork onto the auxiliary stream", who);
+        return SNERF_OK;
     }
-    if (!desc_coarse || !packed_coarse || !packed_t_coarse || !batch->ray_samples || !batch->rays_d || !batch->z_vals ||
-        !batch->rgb_truth || !workspace || !grad_coarse || !loss || !rgb || !rgb_fine)
+    int join(const char *who) const {
+        if (on && (hipEventRecord(ev_join, aux) != hipSuccess || hipStreamWaitEvent(s, ev_join, 0) != hipSuccess))
+            return fail(SNERF_E_LAUNCH, "%s: cannot join the auxiliary stream", who);
+        return SNERF_OK;
+    }
+};
+static int concurrent_setup(const TrainArgs &a, const TrainWs &w, Concurrent &c) {
+    c.on = w.concurrent && a.aux_stream && a.aux_stream != a.stream;
+    c.ev_fork = c.ev_join = nullptr;
+    c.s = (hipStream_t)a.stream, c.aux = (hipStream_t)a.aux_stream;
+    c.stream_c = c.on ? a.aux_stream : a.stream;
+    return c.on ? fork_join_events(c.ev_fork, c.ev_join) : SNERF_OK;
+}
+
+// the rays [r0, r0 + b) of the batch and of the outputs
+struct Chunk {
+    int64_t r0, b;
+    bool first, last;
+    const float *x, *o, *d, *z, *gt, *nz_c, *nz_f;
+    float *rgb_c, *rgb_f;
+};
+static Chunk chunk_of(const TrainArgs &a, const Shape &sh, int64_t r0) {
+    const snerf_nerf_batch *t = a.batch;
+    Chunk c;
+    c.r0 = r0;
+    c.b = (sh.B - r0 < sh.chunk) ? sh.B - r0 : sh.chunk;
+    c.first = r0 == 0, c.last = r0 + c.b >= sh.B;
+    c.x = t->ray_samples + r0 * sh.Nc * 3, c.d = t->rays_d + r0 * 3, c.z = t->z_vals + r0 * sh.Nc, c.gt = t->rgb_truth + r0 * 3;
+    c.o = t->rays_o ? t->rays_o + r0 * 3 : nullptr;
+    c.nz_c = t->noise_coarse ? t->noise_coarse + r0 * sh.Nc : nullptr;
+    c.nz_f = t->noise_fine ? t->noise_fine + r0 * sh.N : nullptr;
+    c.rgb_c = a.rgb + r0 * 3, c.rgb_f = a.rgb_fine + r0 * 3;
+    return c;
+}
+
+// loss value and d loss / d rgb of a chunk (solver/nerf_solver.py:48-52, 85-86)
+static int launch_loss(const TrainArgs &a, const Shape &sh, const TrainBufs &m, const Chunk &c, const char *what) {
+    const float norm = (float)(2.0 / (3.0 * (double)sh.B));      // mse_loss_backward: 2 / numel
+    const double inv_total = 1.0 / (3.0 * (double)sh.B);
+    hipLaunchKernelGGL(mse_grad_kernel, dim3(1), dim3(MSE_THREADS), 0, (hipStream_t)a.stream, c.rgb_c, sh.Nf > 0 ? c.rgb_f : nullptr, c.gt,
+                       c.b * 3, norm, m.d_rgb_c, m.d_rgb_f, m.loss_acc, c.first ? 1 : 0, c.last ? 1 : 0, inv_total, a.loss);
+    return check_launch(what);
+}
+
+// run_fine = 0: the pipeline returns `rgb` twice (models/nerf_pipeline.py:43-44)
+static int copy_rgb_fine(const TrainArgs &a, const Shape &sh, const char *who) {
+    if (sh.Nf == 0 && a.rgb_fine != a.rgb &&
+        hipMemcpyAsync(a.rgb_fine, a.rgb, (size_t)sh.B * 3 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)a.stream) != hipSuccess)
+        return fail(SNERF_E_LAUNCH, "%s: device copy failed", who);
+    return SNERF_OK;
+}
+
+// (data-parallel step) the coarse net's gradient as a segment [c0, c1) of the flat buffer
+static int coarse_segment(const TrainArgs &a, int64_t &c0, int64_t &c1) {
+    const int64_t pc = snerf_mlp_param_floats(a.coarse.desc);
+    c0 = a.coarse.grad - a.flat_g;
+    c1 = c0 + pc;
+    if (pc < 1 || c0 < 0 || c1 > a.flat_n) return fail(SNERF_E_BADARG, "nerf_train_step_dp: grad_coarse must lie inside adam->grads[0 .. n_params)");
+    return SNERF_OK;
+}
+
+// The gradient half of the nerf form.  With comm, the collectives of the step are issued behind the last chunk's backward.
+static int nerf_train_grads(const TrainArgs &a) {
+    const char *const who = "nerf_train_grads", *const who_dp = "nerf_train_step_dp";
+    const NetArgs &C = a.coarse, &F = a.fine;
+    const snerf_nerf_batch *batch = a.batch;
+    const snerf_input_grads *ig = a.input_grads;
+    Shape sh;
+    int rc;
+    if ((rc = decode_shape(a, a.comm ? 0 : 1, who, sh))) return rc;
+    const int64_t B = sh.B;
+    const int Nc = sh.Nc, Nf = sh.Nf, N = sh.N, precision = sh.precision;
+    int64_t cb0 = 0, cb1 = 0;
+    if (a.comm && B == 0) {
+        if (!a.flat_g || a.flat_n < 1 || !C.desc || !C.grad || !a.loss) return fail(SNERF_E_BADARG, "nerf_train_step_dp: null pointer");
+        if ((rc = coarse_segment(a, cb0, cb1))) return rc;
+        if ((rc = dp_empty_shard(a, who_dp))) return rc;
+        if ((rc = dp_allreduce_avg(a.comm, a.flat_g, cb0, cb1, 0, 0, (hipStream_t)a.stream, who_dp))) return rc;
+        return dp_allreduce_avg(a.comm, a.flat_g, 0, a.flat_n, cb0, cb1, (hipStream_t)a.stream, who_dp);
+    }
+    if (!C.desc || !C.packed || !C.packed_t || !batch->ray_samples || !batch->rays_d || !batch->z_vals || !batch->rgb_truth ||
+        !a.workspace || !C.grad || !a.loss || !a.rgb || !a.rgb_fine)
         return fail(SNERF_E_BADARG, "nerf_train_grads: null pointer");
-    if (Nf > 0 && (!desc_fine || !packed_fine || !packed_t_fine || !grad_fine || !batch->rays_o || !batch->u))
+    if (Nf > 0 && (!F.desc || !F.packed || !F.packed_t || !F.grad || !batch->rays_o || !batch->u))
         return fail(SNERF_E_BADARG, "nerf_train_grads: the fine pass needs desc_fine, its streams, grad_fine, rays_o and u");
-    const int add_dim = desc_coarse->add_dim;
-    if (Nf > 0 && desc_fine->add_dim != add_dim)
+    const int add_dim = C.desc->add_dim;
+    if (Nf > 0 && F.desc->add_dim != add_dim)
         return fail(SNERF_E_BADARG, "nerf_train_grads: both nets must read the same per-ray additional inputs (add_dim %d vs %d)", add_dim,
-                    desc_fine->add_dim);
+                    F.desc->add_dim);
     if (add_dim && !batch->additional) return fail(SNERF_E_BADARG, "nerf_train_grads: the nets have additional inputs but batch->additional is null");
     float *d_add = ig ? ig->d_additional : nullptr;
     if (d_add && (!add_dim || !ig->params_coarse || (Nf > 0 && !ig->params_fine)))
         return fail(SNERF_E_BADARG, "nerf_train_grads: d_additional needs nets with additional inputs and their parameters (params_coarse / params_fine)");
-    if (!aligned(workspace, 256)) return fail(SNERF_E_ALIGN, "nerf_train_grads: workspace must be 256-byte aligned");
-    if (precision != 0 && (desc_coarse->width != 256 || (Nf > 0 && desc_fine->width != 256)))
-        return fail(SNERF_E_BADARG, "nerf_train_grads: the split-precision kernels exist for width 256");
-    const int64_t chunk = effective_chunk(B, rays_per_chunk);
+    if ((rc = check_workspace_and_width(a, sh, who))) return rc;
     TrainWs w{};
-    int rc;
-    if ((rc = train_ws(desc_coarse, desc_fine, chunk, Nc, Nf, w))) return rc;
-    char *ws = reinterpret_cast<char *>(workspace);
-    auto f = [&](int64_t off) { return reinterpret_cast<float *>(ws + off); };
-    float *raw_c = f(w.raw_c), *weights_c = f(w.weights_c), *z_fine = f(w.z_fine), *pts_f = f(w.pts_f), *raw_f = f(w.raw_f);
-    float *d_rgb_c = f(w.d_rgb_c), *d_rgb_f = f(w.d_rgb_f), *d_raw = f(w.d_raw), *act_c = f(w.act_c), *act_f = f(w.act_f);
-    float *dy = f(w.dy), *gpart = f(w.gpart), *cscratch = f(w.contract);
-    // small chunks with an auxiliary stream: the coarse net's backward beside the fine net's, on its own scratch buffers
-    const bool concurrent = w.concurrent && aux_stream && aux_stream != stream;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    if (concurrent && (rc = fork_join_events(ev_fork, ev_join))) return rc;
-    float *d_raw_c = concurrent ? f(w.d_raw2) : d_raw, *dy_c = concurrent ? f(w.dy2) : dy, *gpart_c = concurrent ? f(w.gpart2) : gpart;
-    const snerf_stream_t stream_c = concurrent ? aux_stream : stream;
-    // (data-parallel step) the coarse net's gradient as a segment [cb0, cb1) of the flat buffer
-    int64_t cb0 = 0, cb1 = 0;
-    bool coarse_bucket = false;
-    if (comm) {
-        if (!flat_g || flat_n < 1) return fail(SNERF_E_BADARG, "nerf_train_step_dp: no flat gradient buffer");
-        const int64_t pc = snerf_mlp_param_floats(desc_coarse);
-        cb0 = grad_coarse - flat_g;
-        cb1 = cb0 + pc;
-        coarse_bucket = pc > 0 && cb0 >= 0 && cb1 <= flat_n;
-        if (!coarse_bucket) return fail(SNERF_E_BADARG, "nerf_train_step_dp: grad_coarse must lie inside adam->grads[0 .. n_params)");
-        const int64_t pf = Nf > 0 ? snerf_mlp_param_floats(desc_fine) : 0;
-        if (Nf > 0 && (grad_fine - flat_g < 0 || grad_fine - flat_g + pf > flat_n))
+    if ((rc = train_ws(C.desc, F.desc, sh.chunk, Nc, Nf, w))) return rc;
+    const TrainBufs m = carve(w, a.workspace);
+    Concurrent cc;
+    if ((rc = concurrent_setup(a, w, cc))) return rc;
+    const BwdSet &sf = m.set[0], &sc = m.set[cc.on ? 1 : 0];
+    if (a.comm) {
+        if (!a.flat_g || a.flat_n < 1) return fail(SNERF_E_BADARG, "nerf_train_step_dp: no flat gradient buffer");
+        if ((rc = coarse_segment(a, cb0, cb1))) return rc;
+        const int64_t pf = Nf > 0 ? snerf_mlp_param_floats(F.desc) : 0;
+        if (Nf > 0 && (F.grad - a.flat_g < 0 || F.grad - a.flat_g + pf > a.flat_n))
             return fail(SNERF_E_BADARG, "nerf_train_step_dp: grad_fine must lie inside adam->grads[0 .. n_params)");
     }
-    double *loss_acc = reinterpret_cast<double *>(ws + w.loss_acc);
-    hipStream_t s = (hipStream_t)stream;
+    const snerf_stream_t stream = a.stream;
     const int wb = batch->white_background ? 1 : 0;
-    const float norm = (float)(2.0 / (3.0 * (double)B));      // mse_loss_backward: 2 / numel
-    const double inv_total = 1.0 / (3.0 * (double)B);
-    auto fwd_train = [&](const snerf_mlp_desc *d, const void *packed, const float *x, const float *dirs, const float *add, int64_t n,
-                         int spr, float *raw, float *act) {
+    auto fwd_train = [&](const NetArgs &n, const float *x, const float *dirs, const float *add, int64_t cnt, int spr, float *raw, float *act) {
         if (precision == 0)
-            return snerf_mlp_fwd_train_f32(d, reinterpret_cast<const float *>(packed), x, dirs, 0, add, n, spr, raw, act, stream);
-        return snerf_mlp_fwd_train_bf16_f32(d, packed, precision, x, dirs, 0, add, n, spr, raw, act, stream);
+            return snerf_mlp_fwd_train_f32(n.desc, reinterpret_cast<const float *>(n.packed), x, dirs, 0, add, cnt, spr, raw, act, stream);
+        return snerf_mlp_fwd_train_bf16_f32(n.desc, n.packed, precision, x, dirs, 0, add, cnt, spr, raw, act, stream);
     };
-    auto bwd = [&](const snerf_mlp_desc *d, const void *packed_t, const float *act, const float *d_raw_, int64_t n, float *dy_,
-                   float *gpart_, float *grad, bool accumulate, snerf_stream_t st, int64_t n_beside) {
+    auto bwd = [&](const NetArgs &n, const float *act, const BwdSet &t, int64_t cnt, bool accumulate, snerf_stream_t st, int64_t n_beside) {
         if (precision == 0)
-            return launch_bwd(d, reinterpret_cast<const float *>(packed_t), act, d_raw_, n, dy_, gpart_, grad, nullptr, nullptr, 0, 1,
-                              nullptr, nullptr, st, accumulate, false, n_beside);
-        return launch_bwd_bf16(d, packed_t, precision, act, d_raw_, n, dy_, gpart_, grad, nullptr, nullptr, 0, 1, nullptr, nullptr,
-                               st, accumulate);
+            return launch_bwd(n.desc, reinterpret_cast<const float *>(n.packed_t), act, t.d_raw, cnt, t.dy, t.gpart, n.grad, nullptr, nullptr,
+                              0, 1, nullptr, nullptr, st, accumulate, false, n_beside);
+        return launch_bwd_bf16(n.desc, n.packed_t, precision, act, t.d_raw, cnt, t.dy, t.gpart, n.grad, nullptr, nullptr, 0, 1, nullptr,
+                               nullptr, st, accumulate);
     };
     // (the weight-gradient launches of a chunk small enough for the concurrent backward split their jobs for each net's share of the
     // chip - by the size rule alone, with or without an auxiliary stream: the summation order, hence every bit of the gradients,
     // does not depend on the streams the caller brings)
-    for (int64_t r0 = 0; r0 < B; r0 += chunk) {
-        const int64_t b = (B - r0 < chunk) ? B - r0 : chunk;
-        const float *x = batch->ray_samples + r0 * Nc * 3, *d = batch->rays_d + r0 * 3, *z = batch->z_vals + r0 * Nc;
-        const float *gt = batch->rgb_truth + r0 * 3;
-        const float *nz_c = batch->noise_coarse ? batch->noise_coarse + r0 * Nc : nullptr;
-        const float *nz_f = batch->noise_fine ? batch->noise_fine + r0 * N : nullptr;
-        float *rgb_c = rgb + r0 * 3, *rgb_fo = rgb_fine + r0 * 3;
+    for (int64_t r0 = 0; r0 < B; r0 += sh.chunk) {
+        const Chunk c = chunk_of(a, sh, r0);
+        const int64_t b = c.b;
         const float *add = add_dim ? batch->additional + r0 * add_dim : nullptr;   // per-ray constants (append_smpl_params_pipeline.py:29-52)
         // forward (models/nerf_pipeline.py:29-65) with every layer input saved
-        if ((rc = fwd_train(desc_coarse, packed_coarse, x, d, add, b * Nc, Nc, raw_c, act_c))) return rc;
-        if ((rc = snerf_composite_fwd_f32(raw_c, z, d, 0, nz_c, b, Nc, wb, rgb_c, Nf > 0 ? weights_c : nullptr, nullptr, stream))) return rc;
+        if ((rc = fwd_train(C, c.x, c.d, add, b * Nc, Nc, m.raw_c, m.act_c))) return rc;
+        if ((rc = snerf_composite_fwd_f32(m.raw_c, c.z, c.d, 0, c.nz_c, b, Nc, wb, c.rgb_c, Nf > 0 ? m.weights_c : nullptr, nullptr, stream)))
+            return rc;
         if (Nf > 0) {
-            if ((rc = sample_pdf_merged(refsum, z, weights_c, batch->u, batch->rays_o + r0 * 3, d, b, Nc, Nf, nullptr, nullptr, z_fine,
-                                        pts_f, stream)))
+            if ((rc = sample_pdf_merged(sh.refsum, c.z, m.weights_c, batch->u, c.o, c.d, b, Nc, Nf, nullptr, nullptr, m.z_fine, m.pts_f, stream)))
                 return rc;
-            if ((rc = fwd_train(desc_fine, packed_fine, pts_f, d, add, b * N, N, raw_f, act_f))) return rc;
-            if ((rc = snerf_composite_fwd_f32(raw_f, z_fine, d, 0, nz_f, b, N, wb, rgb_fo, nullptr, nullptr, stream))) return rc;
+            if ((rc = fwd_train(F, m.pts_f, c.d, add, b * N, N, m.raw_f, m.act_f))) return rc;
+            if ((rc = snerf_composite_fwd_f32(m.raw_f, m.z_fine, c.d, 0, c.nz_f, b, N, wb, c.rgb_f, nullptr, nullptr, stream))) return rc;
         }
-        // loss value and d loss / d rgb (solver/nerf_solver.py:48-52, 85-86)
-        hipLaunchKernelGGL(mse_grad_kernel, dim3(1), dim3(MSE_THREADS), 0, s, rgb_c, Nf > 0 ? rgb_fo : nullptr, gt, b * 3, norm,
-                           d_rgb_c, d_rgb_f, loss_acc, r0 == 0 ? 1 : 0, r0 + b >= B ? 1 : 0, inv_total, loss);
-        if ((rc = check_launch("nerf_train_grads(mse)"))) return rc;
+        if ((rc = launch_loss(a, sh, m, c, "nerf_train_grads(mse)"))) return rc;
         // backward: compositing, then dgrad + wgrad + reduce of each net (the hierarchical samples are detached, utils.py:260)
-        if (concurrent && (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent((hipStream_t)aux_stream, ev_fork, 0) != hipSuccess))
-            return fail(SNERF_E_LAUNCH, "nerf_train_grads: cannot fork onto the auxiliary stream");
+        if ((rc = cc.fork(who))) return rc;
         if (Nf > 0) {
-            if ((rc = snerf_composite_bwd_f32(raw_f, z_fine, d, 0, nz_f, b, N, wb, d_rgb_f, d_raw, nullptr, stream))) return rc;
-            if ((rc = bwd(desc_fine, packed_t_fine, act_f, d_raw, b * N, dy, gpart, grad_fine, r0 > 0, stream, w.concurrent ? b * Nc : 0))) return rc;
-            if (d_add && (rc = contract_additional(desc_fine, ig->params_fine, dy, b * N, N, d_add + r0 * add_dim, true, cscratch, stream))) return rc;
+            if ((rc = snerf_composite_bwd_f32(m.raw_f, m.z_fine, c.d, 0, c.nz_f, b, N, wb, m.d_rgb_f, sf.d_raw, nullptr, stream))) return rc;
+            if ((rc = bwd(F, m.act_f, sf, b * N, r0 > 0, stream, w.concurrent ? b * Nc : 0))) return rc;
+            if (d_add && (rc = contract_additional(F.desc, ig->params_fine, sf.dy, b * N, N, d_add + r0 * add_dim, true, m.contract, stream)))
+                return rc;
         }
-        if ((rc = snerf_composite_bwd_f32(raw_c, z, d, 0, nz_c, b, Nc, wb, d_rgb_c, d_raw_c, nullptr, stream_c))) return rc;
-        if ((rc = bwd(desc_coarse, packed_t_coarse, act_c, d_raw_c, b * Nc, dy_c, gpart_c, grad_coarse, r0 > 0, stream_c, w.concurrent ? b * N : 0))) return rc;
+        if ((rc = snerf_composite_bwd_f32(m.raw_c, c.z, c.d, 0, c.nz_c, b, Nc, wb, m.d_rgb_c, sc.d_raw, nullptr, cc.stream_c))) return rc;
+        if ((rc = bwd(C, m.act_c, sc, b * Nc, r0 > 0, cc.stream_c, w.concurrent ? b * N : 0))) return rc;
+        if ((rc = cc.join(who))) return rc;
         // The collectives of the step are the same two on every rank, whatever its batch size, chunking and streams (RCCL matches
         // collectives by issue order and size; ADVICE r05: the concurrent form depends on the rank's own B): first the coarse net's
         // segment [cb0, cb1), then the rest of the flat buffer - both on `stream`, behind the join.
-        const bool last = r0 + b >= B;
-        if (concurrent && (hipEventRecord(ev_join, (hipStream_t)aux_stream) != hipSuccess || hipStreamWaitEvent(s, ev_join, 0) != hipSuccess))
-            return fail(SNERF_E_LAUNCH, "nerf_train_grads: cannot join the auxiliary stream");
         // (r06, late: both on `stream`, behind the join.  r05 put the coarse bucket on the auxiliary stream beside the fine net's
         // backward - two collectives of ONE communicator in flight on two streams.  That has never run on more than one rank, it buys
         // the overlap of a 2.4 MB all-reduce, and it is the one pattern of the step RCCL does not promise to order for us: one stream.)
-        if (comm && last && (rc = dp_allreduce_avg(comm, flat_g, cb0, cb1, 0, 0, s, "nerf_train_step_dp"))) return rc;
-        if (comm && last && (rc = dp_allreduce_avg(comm, flat_g, 0, flat_n, cb0, cb1, s, "nerf_train_step_dp"))) return rc;
+        if (a.comm && c.last && (rc = dp_allreduce_avg(a.comm, a.flat_g, cb0, cb1, 0, 0, cc.s, who_dp))) return rc;
+        if (a.comm && c.last && (rc = dp_allreduce_avg(a.comm, a.flat_g, 0, a.flat_n, cb0, cb1, cc.s, who_dp))) return rc;
         // the coarse net's share of d loss / d additional inputs: behind the join (the two backwards may have run side by side; the
         // coarse net's d Y buffer is its own then), added to the fine net's
-        if (d_add && (rc = contract_additional(desc_coarse, ig->params_coarse, dy_c, b * Nc, Nc, d_add + r0 * add_dim, Nf == 0, cscratch, stream)))
+        if (d_add && (rc = contract_additional(C.desc, ig->params_coarse, sc.dy, b * Nc, Nc, d_add + r0 * add_dim, Nf == 0, m.contract, stream)))
             return rc;
     }
-    if (Nf == 0 && rgb_fine != rgb &&
-        hipMemcpyAsync(rgb_fine, rgb, (size_t)B * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return fail(SNERF_E_LAUNCH, "nerf_train_grads: device copy failed");
-    return SNERF_OK;
+    return copy_rgb_fine(a, sh, who);
 }
+
+}  // namespace snerf
 
 extern "C" int snerf_nerf_train_grads_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
                                           const snerf_mlp_desc *desc_fine, const void *packed_fine, const void *packed_t_fine,
                                           int precision, const snerf_nerf_batch *batch, int64_t rays_per_chunk, void *workspace,
                                           float *grad_coarse, float *grad_fine, float *loss, float *rgb, float *rgb_fine,
                                           snerf_stream_t stream, snerf_stream_t aux_stream) {
-    return nerf_train_grads_impl(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, precision, batch,
-                                 rays_per_chunk, workspace, grad_coarse, grad_fine, loss, rgb, rgb_fine, stream, aux_stream, nullptr, nullptr, 0);
+    snerf::TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream, a.aux_stream = aux_stream;
+    return snerf::nerf_train_grads(a);
 }
 
 extern "C" int snerf_nerf_train_grads_ig_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
@@ -626,9 +768,28 @@ extern "C" int snerf_nerf_train_grads_ig_f32(const snerf_mlp_desc *desc_coarse, 
                                              int precision, const snerf_nerf_batch *batch, int64_t rays_per_chunk, void *workspace,
                                              float *grad_coarse, float *grad_fine, float *loss, float *rgb, float *rgb_fine,
                                              const snerf_input_grads *input_grads, snerf_stream_t stream, snerf_stream_t aux_stream) {
-    return nerf_train_grads_impl(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, precision, batch,
-                                 rays_per_chunk, workspace, grad_coarse, grad_fine, loss, rgb, rgb_fine, stream, aux_stream, nullptr, nullptr, 0,
-                                 input_grads);
+    snerf::TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream, a.aux_stream = aux_stream;
+    a.input_grads = input_grads;
+    return snerf::nerf_train_grads(a);
+}
+
+extern "C" int snerf_nerf_train_step_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
+                                         const snerf_mlp_desc *desc_fine, const void *packed_fine, const void *packed_t_fine,
+                                         int precision, const snerf_nerf_batch *batch, int64_t rays_per_chunk, void *workspace,
+                                         float *grad_coarse, float *grad_fine, float *loss, float *rgb, float *rgb_fine,
+                                         const snerf_adam_state *adam, const snerf_adam_range *ranges_host, int n_ranges,
+                                         const snerf_adam_net *nets_host, int n_nets, snerf_stream_t stream, snerf_stream_t aux_stream) {
+    snerf::TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream, a.aux_stream = aux_stream;
+    if (int rc = snerf::nerf_train_grads(a)) return rc;
+    return snerf::finish_step(a, {adam, ranges_host, n_ranges, nets_host, n_nets});
 }
 
 extern "C" int snerf_nerf_train_step_ig_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
@@ -638,12 +799,15 @@ extern "C" int snerf_nerf_train_step_ig_f32(const snerf_mlp_desc *desc_coarse, c
                                             const snerf_adam_state *adam, const snerf_adam_range *ranges_host, int n_ranges,
                                             const snerf_adam_net *nets_host, int n_nets, const snerf_input_grads *input_grads,
                                             snerf_stream_t stream, snerf_stream_t aux_stream) {
+    snerf::TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream, a.aux_stream = aux_stream;
+    a.input_grads = input_grads;
     // (the contraction reads the parameters: it runs inside the gradient half, before Adam moves them)
-    int rc = nerf_train_grads_impl(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, precision, batch,
-                                   rays_per_chunk, workspace, grad_coarse, grad_fine, loss, rgb, rgb_fine, stream, aux_stream, nullptr, nullptr,
-                                   0, input_grads);
-    if (rc) return rc;
-    return snerf_adam_step_f32(adam, ranges_host, n_ranges, nets_host, n_nets, stream);
+    if (int rc = snerf::nerf_train_grads(a)) return rc;
+    return snerf::finish_step(a, {adam, ranges_host, n_ranges, nets_host, n_nets});
 }
 
 extern "C" int snerf_nerf_train_step_dp_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
@@ -656,11 +820,14 @@ extern "C" int snerf_nerf_train_step_dp_f32(const snerf_mlp_desc *desc_coarse, c
     using namespace snerf;
     if (!comm) return fail(SNERF_E_BADARG, "nerf_train_step_dp: comm is null (the single-GPU step is snerf_nerf_train_step_f32)");
     if (!adam || !adam->grads || adam->n_params < 1) return fail(SNERF_E_BADARG, "nerf_train_step_dp: adam / adam->grads is null");
-    int rc = nerf_train_grads_impl(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, precision, batch,
-                                   rays_per_chunk, workspace, grad_coarse, grad_fine, loss, rgb, rgb_fine, stream, aux_stream, comm,
-                                   const_cast<float *>(adam->grads), adam->n_params);
-    if (rc) return rc;
-    return snerf_adam_step_f32(adam, ranges_host, n_ranges, nets_host, n_nets, stream);
+    TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream, a.aux_stream = aux_stream;
+    a.comm = comm, a.flat_g = const_cast<float *>(adam->grads), a.flat_n = adam->n_params;
+    if (int rc = nerf_train_grads(a)) return rc;
+    return finish_step(a, {adam, ranges_host, n_ranges, nets_host, n_nets});
 }
 
 extern "C" int snerf_nerf_train_step_dp_ig_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
@@ -673,24 +840,16 @@ extern "C" int snerf_nerf_train_step_dp_ig_f32(const snerf_mlp_desc *desc_coarse
     using namespace snerf;
     if (!comm) return fail(SNERF_E_BADARG, "nerf_train_step_dp_ig: comm is null (the single-GPU step is snerf_nerf_train_step_ig_f32)");
     if (!adam || !adam->grads || adam->n_params < 1) return fail(SNERF_E_BADARG, "nerf_train_step_dp_ig: adam / adam->grads is null");
+    TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream, a.aux_stream = aux_stream;
+    a.comm = comm, a.flat_g = const_cast<float *>(adam->grads), a.flat_n = adam->n_params;
+    a.input_grads = input_grads;
     // (the contraction reads the parameters and the stored d Y: inside the gradient half, before the average and before Adam)
-    int rc = nerf_train_grads_impl(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, precision, batch,
-                                   rays_per_chunk, workspace, grad_coarse, grad_fine, loss, rgb, rgb_fine, stream, aux_stream, comm,
-                                   const_cast<float *>(adam->grads), adam->n_params, input_grads);
-    if (rc) return rc;
-    return snerf_adam_step_f32(adam, ranges_host, n_ranges, nets_host, n_nets, stream);
-}
-
-extern "C" int snerf_nerf_train_step_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
-                                         const snerf_mlp_desc *desc_fine, const void *packed_fine, const void *packed_t_fine,
-                                         int precision, const snerf_nerf_batch *batch, int64_t rays_per_chunk, void *workspace,
-                                         float *grad_coarse, float *grad_fine, float *loss, float *rgb, float *rgb_fine,
-                                         const snerf_adam_state *adam, const snerf_adam_range *ranges_host, int n_ranges,
-                                         const snerf_adam_net *nets_host, int n_nets, snerf_stream_t stream, snerf_stream_t aux_stream) {
-    int rc = snerf_nerf_train_grads_f32(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, precision,
-                                        batch, rays_per_chunk, workspace, grad_coarse, grad_fine, loss, rgb, rgb_fine, stream, aux_stream);
-    if (rc) return rc;
-    return snerf_adam_step_f32(adam, ranges_host, n_ranges, nets_host, n_nets, stream);
+    if (int rc = nerf_train_grads(a)) return rc;
+    return finish_step(a, {adam, ranges_host, n_ranges, nets_host, n_nets});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -778,136 +937,132 @@ extern "C" int64_t snerf_smpl_nerf_train_workspace_bytes(const snerf_mlp_desc *d
     return w.total;
 }
 
-// aux_stream (may be NULL): small chunks run the coarse chain there beside the fine chain on `stream` - same results either way
-static int smpl_nerf_train_grads_impl(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
-                                      const snerf_mlp_desc *desc_fine, const void *packed_fine, const void *packed_t_fine,
-                                      const snerf_warp_desc *desc_warp, const float *packed_warp, const float *packed_t_warp,
-                                      int precision, const snerf_nerf_batch *batch, const float *pose_enc, int64_t rays_per_chunk,
-                                      void *workspace, float *grad_coarse, float *grad_fine, float *grad_warp, float *loss, float *rgb,
-                                      float *rgb_fine, snerf_stream_t stream, snerf_stream_t aux_stream) {
-    using namespace snerf;
-    const bool refsum = (precision & SNERF_REFERENCE_SUM) != 0;
-    precision &= ~SNERF_REFERENCE_SUM;
-    if (precision != 0 && !split_code(precision))
-        return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)");
-    if (!batch) return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: batch is null");
-    const int64_t B = batch->B;
-    const int Nc = batch->Nc, Nf = batch->Nf, N = Nc + Nf;
-    if (B < 1 || Nc < 1 || Nf < 0) return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: need B >= 1, Nc >= 1, Nf >= 0");
-    if (!desc_coarse || !packed_coarse || !packed_t_coarse || !desc_warp || !packed_warp || !packed_t_warp || !batch->ray_samples ||
-        !batch->rays_o || !batch->rays_d || !batch->z_vals || !batch->rgb_truth || !pose_enc || !workspace || !grad_coarse || !grad_warp ||
-        !loss || !rgb || !rgb_fine)
-        return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: null pointer");
-    if (Nf > 0 && (!desc_fine || !packed_fine || !packed_t_fine || !grad_fine || !batch->u))
-        return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: the fine pass needs desc_fine, its streams, grad_fine and u");
-    if (desc_coarse->add_dim || (Nf > 0 && desc_fine->add_dim)) return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: nets with additional inputs are not covered");
-    if (!desc_coarse->use_dir || (Nf > 0 && !desc_fine->use_dir))
-        return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: the nets read per-sample view directions (use_dir = 1)");
-    if (!aligned(workspace, 256)) return fail(SNERF_E_ALIGN, "smpl_nerf_train_grads: workspace must be 256-byte aligned");
-    if (precision != 0 && (desc_coarse->width != 256 || (Nf > 0 && desc_fine->width != 256)))
-        return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: the split-precision kernels exist for width 256");
-    const int64_t chunk = effective_chunk(B, rays_per_chunk);
-    SmplTrainWs w{};
+namespace snerf {
+
+// typed view of the smpl_nerf workspace.  set[0] / set[1] as in TrainBufs: set[1] is the coarse chain's own (base.concurrent)
+struct WarpBwdSet {
+    float *d_x, *d_dirs, *d_warp, *dy_w, *gpart_w;
+};
+struct SmplTrainBufs {
+    TrainBufs base;
+    float *warp_c, *warped_c, *sdirs_c, *warp_f, *warped_f, *sdirs_f, *act_wc, *act_wf, *d_cdirs, *grad_warp2;
+    WarpBwdSet set[2];
+};
+static SmplTrainBufs carve(const SmplTrainWs &w, void *ws) {
+    SmplTrainBufs m;
+    m.base = carve(w.base, ws);
+    m.warp_c = at(ws, w.warp_c), m.warped_c = at(ws, w.warped_c), m.sdirs_c = at(ws, w.sdirs_c), m.warp_f = at(ws, w.warp_f);
+    m.warped_f = at(ws, w.warped_f), m.sdirs_f = at(ws, w.sdirs_f), m.act_wc = at(ws, w.act_wc), m.act_wf = at(ws, w.act_wf);
+    m.d_cdirs = at(ws, w.d_cdirs), m.grad_warp2 = at(ws, w.grad_warp2);
+    m.set[0] = {at(ws, w.d_x), at(ws, w.d_dirs), at(ws, w.d_warp), at(ws, w.dy_w), at(ws, w.gpart_w)};
+    m.set[1] = {at(ws, w.d_x2), at(ws, w.d_dirs2), at(ws, w.d_warp2), at(ws, w.dy_w2), at(ws, w.gpart_w2)};
+    return m;
+}
+
+// The gradient half of the smpl_nerf form.  aux_stream (may be NULL): small chunks run the coarse chain there beside the fine chain
+// on `stream` - same results either way.  The step's collective follows in finish_step.
+static int smpl_nerf_train_grads(const TrainArgs &a) {
+    const char *const who = "smpl_nerf_train_grads";
+    const NetArgs &C = a.coarse, &F = a.fine;
+    const WarpArgs &W = a.warp;
+    const snerf_nerf_batch *batch = a.batch;
+    if (a.comm && batch && batch->B == 0) {
+        if (!a.loss) return fail(SNERF_E_BADARG, "smpl_nerf_train_step_dp: loss is null");
+        return dp_empty_shard(a, "smpl_nerf_train_step_dp");
+    }
+    Shape sh;
     int rc;
-    if ((rc = smpl_train_ws(desc_coarse, desc_fine, desc_warp, chunk, Nc, Nf, w))) return rc;
-    char *ws = reinterpret_cast<char *>(workspace);
-    auto f = [&](int64_t off) { return reinterpret_cast<float *>(ws + off); };
-    const TrainWs &b0 = w.base;
-    float *raw_c = f(b0.raw_c), *weights_c = f(b0.weights_c), *z_fine = f(b0.z_fine), *pts_f = f(b0.pts_f), *raw_f = f(b0.raw_f);
-    float *d_rgb_c = f(b0.d_rgb_c), *d_rgb_f = f(b0.d_rgb_f), *d_raw = f(b0.d_raw), *act_c = f(b0.act_c), *act_f = f(b0.act_f);
-    float *dy = f(b0.dy), *gpart = f(b0.gpart);
-    double *loss_acc = reinterpret_cast<double *>(ws + b0.loss_acc);
-    float *warp_c = f(w.warp_c), *warped_c = f(w.warped_c), *sdirs_c = f(w.sdirs_c), *warp_f = f(w.warp_f), *warped_f = f(w.warped_f);
-    float *sdirs_f = f(w.sdirs_f), *act_wc = f(w.act_wc), *act_wf = f(w.act_wf), *d_x = f(w.d_x), *d_dirs = f(w.d_dirs);
-    float *d_cdirs = f(w.d_cdirs), *d_warp = f(w.d_warp), *dy_w = f(w.dy_w), *gpart_w = f(w.gpart_w);
-    hipStream_t s = (hipStream_t)stream;
-    // small chunks with an auxiliary stream: the coarse chain beside the fine chain, on its own scratch set
-    const bool concurrent = b0.concurrent && aux_stream && aux_stream != stream;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    if (concurrent && (rc = fork_join_events(ev_fork, ev_join))) return rc;
-    const snerf_stream_t stream_c = concurrent ? aux_stream : stream;
-    float *d_raw_c = concurrent ? f(b0.d_raw2) : d_raw, *dy_c = concurrent ? f(b0.dy2) : dy, *gpart_c = concurrent ? f(b0.gpart2) : gpart;
-    float *d_x_c = concurrent ? f(w.d_x2) : d_x, *d_dirs_c = concurrent ? f(w.d_dirs2) : d_dirs, *d_warp_c = concurrent ? f(w.d_warp2) : d_warp;
-    float *dy_w_c = concurrent ? f(w.dy_w2) : dy_w, *gpart_w_c = concurrent ? f(w.gpart_w2) : gpart_w;
-    float *grad_warp_c = concurrent ? f(w.grad_warp2) : grad_warp;
-    const int64_t n_warp = snerf_warp_param_floats(desc_warp);
+    if ((rc = decode_shape(a, 1, who, sh))) return rc;
+    const int64_t B = sh.B;
+    const int Nc = sh.Nc, Nf = sh.Nf, N = sh.N, precision = sh.precision;
+    if (!C.desc || !C.packed || !C.packed_t || !W.desc || !W.packed || !W.packed_t || !batch->ray_samples || !batch->rays_o ||
+        !batch->rays_d || !batch->z_vals || !batch->rgb_truth || !W.pose_enc || !a.workspace || !C.grad || !W.grad || !a.loss || !a.rgb ||
+        !a.rgb_fine)
+        return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: null pointer");
+    if (Nf > 0 && (!F.desc || !F.packed || !F.packed_t || !F.grad || !batch->u))
+        return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: the fine pass needs desc_fine, its streams, grad_fine and u");
+    if (C.desc->add_dim || (Nf > 0 && F.desc->add_dim)) return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: nets with additional inputs are not covered");
+    if (!C.desc->use_dir || (Nf > 0 && !F.desc->use_dir))
+        return fail(SNERF_E_BADARG, "smpl_nerf_train_grads: the nets read per-sample view directions (use_dir = 1)");
+    if ((rc = check_workspace_and_width(a, sh, who))) return rc;
+    SmplTrainWs w{};
+    if ((rc = smpl_train_ws(C.desc, F.desc, W.desc, sh.chunk, Nc, Nf, w))) return rc;
+    const SmplTrainBufs ms = carve(w, a.workspace);
+    const TrainBufs &m = ms.base;
+    Concurrent cc;
+    if ((rc = concurrent_setup(a, w.base, cc))) return rc;
+    const bool concurrent = cc.on;
+    const BwdSet &sf = m.set[0], &sc = m.set[concurrent ? 1 : 0];
+    const WarpBwdSet &wf = ms.set[0], &wc = ms.set[concurrent ? 1 : 0];
+    float *grad_warp_c = concurrent ? ms.grad_warp2 : W.grad;
+    const int64_t n_warp = snerf_warp_param_floats(W.desc);
     if (n_warp < 0) return (int)n_warp;
+    const snerf_stream_t stream = a.stream, stream_c = cc.stream_c;
     const int wb = batch->white_background ? 1 : 0;
-    const float norm = (float)(2.0 / (3.0 * (double)B));
-    const double inv_total = 1.0 / (3.0 * (double)B);
-    const int pose_dim = desc_warp->pose_dim;
-    auto fwd_train = [&](const snerf_mlp_desc *d, const void *packed, const float *x, const float *sd, int64_t n, int spr, float *raw,
-                         float *act) {
+    const int pose_dim = W.desc->pose_dim;
+    auto fwd_train = [&](const NetArgs &n, const float *x, const float *sd, int64_t cnt, int spr, float *raw, float *act) {
         if (precision == 0)
-            return snerf_mlp_fwd_train_f32(d, reinterpret_cast<const float *>(packed), x, sd, 1, nullptr, n, spr, raw, act, stream);
-        return snerf_mlp_fwd_train_bf16_f32(d, packed, precision, x, sd, 1, nullptr, n, spr, raw, act, stream);
+            return snerf_mlp_fwd_train_f32(n.desc, reinterpret_cast<const float *>(n.packed), x, sd, 1, nullptr, cnt, spr, raw, act, stream);
+        return snerf_mlp_fwd_train_bf16_f32(n.desc, n.packed, precision, x, sd, 1, nullptr, cnt, spr, raw, act, stream);
     };
-    auto bwd_inputs = [&](const snerf_mlp_desc *d, const void *packed_t, const float *act, const float *d_raw_, const float *x,
-                          const float *sd, int64_t n, int spr, float *dy_, float *gpart_, float *grad, float *d_x_, float *d_dirs_,
-                          bool accumulate, snerf_stream_t st) {
+    auto bwd_inputs = [&](const NetArgs &n, const float *act, const BwdSet &t, const float *x, const float *sd, int64_t cnt, int spr,
+                          const WarpBwdSet &u, bool accumulate, snerf_stream_t st) {
         if (precision == 0)
-            return launch_bwd(d, reinterpret_cast<const float *>(packed_t), act, d_raw_, n, dy_, gpart_, grad, x, sd, 1, spr, d_x_, d_dirs_,
-                              st, accumulate, concurrent, b0.concurrent ? (spr == Nc ? n / Nc * N : n / N * Nc) : 0);
-        return launch_bwd_bf16(d, packed_t, precision, act, d_raw_, n, dy_, gpart_, grad, x, sd, 1, spr, d_x_, d_dirs_, st, accumulate);
+            return launch_bwd(n.desc, reinterpret_cast<const float *>(n.packed_t), act, t.d_raw, cnt, t.dy, t.gpart, n.grad, x, sd, 1, spr,
+                              u.d_x, u.d_dirs, st, accumulate, concurrent, w.base.concurrent ? (spr == Nc ? cnt / Nc * N : cnt / N * Nc) : 0);
+        return launch_bwd_bf16(n.desc, n.packed_t, precision, act, t.d_raw, cnt, t.dy, t.gpart, n.grad, x, sd, 1, spr, u.d_x, u.d_dirs, st,
+                               accumulate);
     };
-    auto sum3 = [&](const float *a, const float *b, const float *c, int64_t n, float *out, snerf_stream_t st) {
-        hipLaunchKernelGGL(sum3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)st, a, b, c, n, out);
+    auto sum3 = [&](const float *p, const float *q, const float *r, int64_t cnt, float *out, snerf_stream_t st) {
+        hipLaunchKernelGGL(sum3_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, (hipStream_t)st, p, q, r, cnt, out);
         return check_launch("smpl_nerf_train_grads(sum)");
     };
-    for (int64_t r0 = 0; r0 < B; r0 += chunk) {
-        const int64_t b = (B - r0 < chunk) ? B - r0 : chunk;
-        const float *x = batch->ray_samples + r0 * Nc * 3, *o = batch->rays_o + r0 * 3, *d = batch->rays_d + r0 * 3;
-        const float *z = batch->z_vals + r0 * Nc, *gt = batch->rgb_truth + r0 * 3, *pe = pose_enc + r0 * pose_dim;
-        const float *nz_c = batch->noise_coarse ? batch->noise_coarse + r0 * Nc : nullptr;
-        const float *nz_f = batch->noise_fine ? batch->noise_fine + r0 * N : nullptr;
-        float *rgb_c = rgb + r0 * 3, *rgb_fo = rgb_fine + r0 * 3;
+    for (int64_t r0 = 0; r0 < B; r0 += sh.chunk) {
+        const Chunk c = chunk_of(a, sh, r0);
+        const int64_t b = c.b;
+        const float *pe = W.pose_enc + r0 * pose_dim;
         const bool acc = r0 > 0;
         // coarse stage: warp the given samples, net on (x', x' - o), compositing scaled per sample by |x' - o| (:38-63)
-        if ((rc = snerf_warp_fwd_train_f32(desc_warp, packed_warp, x, pe, o, b * Nc, Nc, warp_c, warped_c, sdirs_c, act_wc, stream))) return rc;
-        if ((rc = fwd_train(desc_coarse, packed_coarse, warped_c, sdirs_c, b * Nc, Nc, raw_c, act_c))) return rc;
-        if ((rc = snerf_composite_fwd_f32(raw_c, z, sdirs_c, 1, nz_c, b, Nc, wb, rgb_c, Nf > 0 ? weights_c : nullptr, nullptr, stream))) return rc;
+        if ((rc = snerf_warp_fwd_train_f32(W.desc, W.packed, c.x, pe, c.o, b * Nc, Nc, ms.warp_c, ms.warped_c, ms.sdirs_c, ms.act_wc, stream)))
+            return rc;
+        if ((rc = fwd_train(C, ms.warped_c, ms.sdirs_c, b * Nc, Nc, m.raw_c, m.act_c))) return rc;
+        if ((rc = snerf_composite_fwd_f32(m.raw_c, c.z, ms.sdirs_c, 1, c.nz_c, b, Nc, wb, c.rgb_c, Nf > 0 ? m.weights_c : nullptr, nullptr, stream)))
+            return rc;
         if (Nf > 0) {   // hierarchical samples on the un-warped ray (:68), then the fine stage (:71-98)
-            if ((rc = sample_pdf_merged(refsum, z, weights_c, batch->u, o, d, b, Nc, Nf, nullptr, nullptr, z_fine, pts_f, stream))) return rc;
-            if ((rc = snerf_warp_fwd_train_f32(desc_warp, packed_warp, pts_f, pe, o, b * N, N, warp_f, warped_f, sdirs_f, act_wf, stream))) return rc;
-            if ((rc = fwd_train(desc_fine, packed_fine, warped_f, sdirs_f, b * N, N, raw_f, act_f))) return rc;
-            if ((rc = snerf_composite_fwd_f32(raw_f, z_fine, d, 0, nz_f, b, N, wb, rgb_fo, nullptr, nullptr, stream))) return rc;
+            if ((rc = sample_pdf_merged(sh.refsum, c.z, m.weights_c, batch->u, c.o, c.d, b, Nc, Nf, nullptr, nullptr, m.z_fine, m.pts_f, stream)))
+                return rc;
+            if ((rc = snerf_warp_fwd_train_f32(W.desc, W.packed, m.pts_f, pe, c.o, b * N, N, ms.warp_f, ms.warped_f, ms.sdirs_f, ms.act_wf, stream)))
+                return rc;
+            if ((rc = fwd_train(F, ms.warped_f, ms.sdirs_f, b * N, N, m.raw_f, m.act_f))) return rc;
+            if ((rc = snerf_composite_fwd_f32(m.raw_f, m.z_fine, c.d, 0, c.nz_f, b, N, wb, c.rgb_f, nullptr, nullptr, stream))) return rc;
         }
-        hipLaunchKernelGGL(mse_grad_kernel, dim3(1), dim3(MSE_THREADS), 0, s, rgb_c, Nf > 0 ? rgb_fo : nullptr, gt, b * 3, norm,
-                           d_rgb_c, d_rgb_f, loss_acc, r0 == 0 ? 1 : 0, r0 + b >= B ? 1 : 0, inv_total, loss);
-        if ((rc = check_launch("smpl_nerf_train_grads(mse)"))) return rc;
-        if (concurrent && (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent((hipStream_t)aux_stream, ev_fork, 0) != hipSuccess))
-            return fail(SNERF_E_LAUNCH, "smpl_nerf_train_grads: cannot fork onto the auxiliary stream");
+        if ((rc = launch_loss(a, sh, m, c, "smpl_nerf_train_grads(mse)"))) return rc;
+        if ((rc = cc.fork(who))) return rc;
         bool warp_acc = acc;
         if (Nf > 0) {   // fine: the compositing is scaled by the ray direction (an input), the net back-propagates into x' and x' - o
-            if ((rc = snerf_composite_bwd_f32(raw_f, z_fine, d, 0, nz_f, b, N, wb, d_rgb_f, d_raw, nullptr, stream))) return rc;
-            if ((rc = bwd_inputs(desc_fine, packed_t_fine, act_f, d_raw, warped_f, sdirs_f, b * N, N, dy, gpart, grad_fine, d_x, d_dirs, acc,
-                                 stream)))
-                return rc;
-            if ((rc = sum3(d_x, d_dirs, nullptr, b * N * 3, d_warp, stream))) return rc;
-            if ((rc = launch_warp_bwd(desc_warp, packed_t_warp, act_wf, d_warp, b * N, dy_w, gpart_w, grad_warp, stream, warp_acc))) return rc;
+            if ((rc = snerf_composite_bwd_f32(m.raw_f, m.z_fine, c.d, 0, c.nz_f, b, N, wb, m.d_rgb_f, sf.d_raw, nullptr, stream))) return rc;
+            if ((rc = bwd_inputs(F, m.act_f, sf, ms.warped_f, ms.sdirs_f, b * N, N, wf, acc, stream))) return rc;
+            if ((rc = sum3(wf.d_x, wf.d_dirs, nullptr, b * N * 3, wf.d_warp, stream))) return rc;
+            if ((rc = launch_warp_bwd(W.desc, W.packed_t, ms.act_wf, wf.d_warp, b * N, wf.dy_w, wf.gpart_w, W.grad, stream, warp_acc))) return rc;
             warp_acc = true;
         }
         // coarse: the compositing's distance scale |x' - o| depends on the warp as well (:63)
-        if ((rc = snerf_composite_bwd_f32(raw_c, z, sdirs_c, 1, nz_c, b, Nc, wb, d_rgb_c, d_raw_c, d_cdirs, stream_c))) return rc;
-        if ((rc = bwd_inputs(desc_coarse, packed_t_coarse, act_c, d_raw_c, warped_c, sdirs_c, b * Nc, Nc, dy_c, gpart_c, grad_coarse, d_x_c,
-                             d_dirs_c, acc, stream_c)))
-            return rc;
-        if ((rc = sum3(d_x_c, d_dirs_c, d_cdirs, b * Nc * 3, d_warp_c, stream_c))) return rc;
-        if ((rc = launch_warp_bwd(desc_warp, packed_t_warp, act_wc, d_warp_c, b * Nc, dy_w_c, gpart_w_c, grad_warp_c, stream_c,
+        if ((rc = snerf_composite_bwd_f32(m.raw_c, c.z, ms.sdirs_c, 1, c.nz_c, b, Nc, wb, m.d_rgb_c, sc.d_raw, ms.d_cdirs, stream_c))) return rc;
+        if ((rc = bwd_inputs(C, m.act_c, sc, ms.warped_c, ms.sdirs_c, b * Nc, Nc, wc, acc, stream_c))) return rc;
+        if ((rc = sum3(wc.d_x, wc.d_dirs, ms.d_cdirs, b * Nc * 3, wc.d_warp, stream_c))) return rc;
+        if ((rc = launch_warp_bwd(W.desc, W.packed_t, ms.act_wc, wc.d_warp, b * Nc, wc.dy_w, wc.gpart_w, grad_warp_c, stream_c,
                                   concurrent ? false : warp_acc)))
             return rc;
         if (concurrent) {   // (concurrent implies Nf > 0: grad_warp holds the fine chain's sum by now)
-            if (hipEventRecord(ev_join, (hipStream_t)aux_stream) != hipSuccess || hipStreamWaitEvent(s, ev_join, 0) != hipSuccess)
-                return fail(SNERF_E_LAUNCH, "smpl_nerf_train_grads: cannot join the auxiliary stream");
-            hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n_warp + 255) / 256)), dim3(256), 0, s, grad_warp, grad_warp_c, n_warp);
+            if ((rc = cc.join(who))) return rc;
+            hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n_warp + 255) / 256)), dim3(256), 0, cc.s, W.grad, grad_warp_c, n_warp);
             if ((rc = check_launch("smpl_nerf_train_grads(add)"))) return rc;
         }
     }
-    if (Nf == 0 && rgb_fine != rgb &&
-        hipMemcpyAsync(rgb_fine, rgb, (size_t)B * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return fail(SNERF_E_LAUNCH, "smpl_nerf_train_grads: device copy failed");
-    return SNERF_OK;
+    return copy_rgb_fine(a, sh, who);
 }
+
+}  // namespace snerf
 
 extern "C" int snerf_smpl_nerf_train_grads_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
                                                const snerf_mlp_desc *desc_fine, const void *packed_fine, const void *packed_t_fine,
@@ -915,9 +1070,14 @@ extern "C" int snerf_smpl_nerf_train_grads_f32(const snerf_mlp_desc *desc_coarse
                                                int precision, const snerf_nerf_batch *batch, const float *pose_enc,
                                                int64_t rays_per_chunk, void *workspace, float *grad_coarse, float *grad_fine,
                                                float *grad_warp, float *loss, float *rgb, float *rgb_fine, snerf_stream_t stream) {
-    return smpl_nerf_train_grads_impl(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, desc_warp,
-                                      packed_warp, packed_t_warp, precision, batch, pose_enc, rays_per_chunk, workspace, grad_coarse,
-                                      grad_fine, grad_warp, loss, rgb, rgb_fine, stream, nullptr);
+    snerf::TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    // (the gradient half only reads the warp net's streams)
+    a.warp = {desc_warp, const_cast<float *>(packed_warp), const_cast<float *>(packed_t_warp), grad_warp, pose_enc};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream;
+    return snerf::smpl_nerf_train_grads(a);
 }
 
 extern "C" int snerf_smpl_nerf_train_grads_aux_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse,
@@ -927,21 +1087,15 @@ extern "C" int snerf_smpl_nerf_train_grads_aux_f32(const snerf_mlp_desc *desc_co
                                                    const float *pose_enc, int64_t rays_per_chunk, void *workspace, float *grad_coarse,
                                                    float *grad_fine, float *grad_warp, float *loss, float *rgb, float *rgb_fine,
                                                    snerf_stream_t stream, snerf_stream_t aux_stream) {
-    return smpl_nerf_train_grads_impl(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, desc_warp,
-                                      packed_warp, packed_t_warp, precision, batch, pose_enc, rays_per_chunk, workspace, grad_coarse,
-                                      grad_fine, grad_warp, loss, rgb, rgb_fine, stream, aux_stream);
+    snerf::TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    // (the gradient half only reads the warp net's streams)
+    a.warp = {desc_warp, const_cast<float *>(packed_warp), const_cast<float *>(packed_t_warp), grad_warp, pose_enc};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream, a.aux_stream = aux_stream;
+    return snerf::smpl_nerf_train_grads(a);
 }
-
-namespace snerf {
-// a rank of a data-parallel step whose shard ran out (B == 0): zero gradient, zero loss; the caller goes on to the collective
-static int dp_empty_batch(const snerf_adam_state *adam, float *loss, snerf_stream_t stream) {
-    if (!loss) return fail(SNERF_E_BADARG, "smpl_nerf_train_step_dp: loss is null");
-    if (hipMemsetAsync(const_cast<float *>(adam->grads), 0, (size_t)adam->n_params * sizeof(float), (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(loss, 0, 3 * sizeof(float), (hipStream_t)stream) != hipSuccess)
-        return fail(SNERF_E_LAUNCH, "smpl_nerf_train_step_dp: memset failed");
-    return SNERF_OK;
-}
-}  // namespace snerf
 
 // comm (may be NULL): the flat gradient buffer is averaged over the ranks between the backward and Adam
 extern "C" int snerf_smpl_nerf_train_step_aux_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
@@ -956,18 +1110,15 @@ extern "C" int snerf_smpl_nerf_train_step_aux_f32(const snerf_mlp_desc *desc_coa
     using namespace snerf;
     if (comm && (!adam || !adam->grads || adam->n_params < 1))
         return fail(SNERF_E_BADARG, "smpl_nerf_train_step_aux: the data-parallel step needs adam->grads");
-    int rc = (comm && batch && batch->B == 0)
-                 ? dp_empty_batch(adam, loss, stream)
-                 : smpl_nerf_train_grads_impl(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, desc_warp,
-                                              packed_warp, packed_t_warp, precision, batch, pose_enc, rays_per_chunk, workspace, grad_coarse,
-                                              grad_fine, grad_warp, loss, rgb, rgb_fine, stream, aux_stream);
-    if (rc) return rc;
-    if (comm && (rc = dp_allreduce_avg(comm, const_cast<float *>(adam->grads), 0, adam->n_params, 0, 0, (hipStream_t)stream,
-                                       "smpl_nerf_train_step_aux")))
-        return rc;
-    if ((rc = snerf_adam_step_f32(adam, ranges_host, n_ranges, nets_host, n_nets, stream))) return rc;
-    return snerf_warp_repack_f32(desc_warp, adam ? adam->params : nullptr, adam ? adam->n_params : 0, warp_param_offset, packed_warp,
-                                 packed_t_warp, stream);
+    TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.warp = {desc_warp, packed_warp, packed_t_warp, grad_warp, pose_enc};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream, a.aux_stream = aux_stream;
+    if (comm) a.comm = comm, a.flat_g = const_cast<float *>(adam->grads), a.flat_n = adam->n_params;
+    if (int rc = smpl_nerf_train_grads(a)) return rc;
+    return finish_step(a, {adam, ranges_host, n_ranges, nets_host, n_nets}, "smpl_nerf_train_step_aux", warp_param_offset);
 }
 
 extern "C" int snerf_smpl_nerf_train_step_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
@@ -978,13 +1129,15 @@ extern "C" int snerf_smpl_nerf_train_step_f32(const snerf_mlp_desc *desc_coarse,
                                               float *rgb, float *rgb_fine, const snerf_adam_state *adam,
                                               const snerf_adam_range *ranges_host, int n_ranges, const snerf_adam_net *nets_host,
                                               int n_nets, int64_t warp_param_offset, snerf_stream_t stream) {
-    int rc = snerf_smpl_nerf_train_grads_f32(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, desc_warp,
-                                             packed_warp, packed_t_warp, precision, batch, pose_enc, rays_per_chunk, workspace, grad_coarse,
-                                             grad_fine, grad_warp, loss, rgb, rgb_fine, stream);
-    if (rc) return rc;
-    if ((rc = snerf_adam_step_f32(adam, ranges_host, n_ranges, nets_host, n_nets, stream))) return rc;
-    return snerf_warp_repack_f32(desc_warp, adam ? adam->params : nullptr, adam ? adam->n_params : 0, warp_param_offset, packed_warp,
-                                 packed_t_warp, stream);
+    using namespace snerf;
+    TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.warp = {desc_warp, packed_warp, packed_t_warp, grad_warp, pose_enc};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream;
+    if (int rc = smpl_nerf_train_grads(a)) return rc;
+    return finish_step(a, {adam, ranges_host, n_ranges, nets_host, n_nets}, "smpl_nerf_train_step", warp_param_offset);
 }
 
 extern "C" int snerf_smpl_nerf_train_step_dp_f32(const snerf_mlp_desc *desc_coarse, const void *packed_coarse, const void *packed_t_coarse,
@@ -998,16 +1151,15 @@ extern "C" int snerf_smpl_nerf_train_step_dp_f32(const snerf_mlp_desc *desc_coar
     using namespace snerf;
     if (!comm) return fail(SNERF_E_BADARG, "smpl_nerf_train_step_dp: comm is null (the single-GPU step is snerf_smpl_nerf_train_step_f32)");
     if (!adam || !adam->grads || adam->n_params < 1) return fail(SNERF_E_BADARG, "smpl_nerf_train_step_dp: adam / adam->grads is null");
-    int rc = (batch && batch->B == 0)
-                 ? dp_empty_batch(adam, loss, stream)
-                 : snerf_smpl_nerf_train_grads_f32(desc_coarse, packed_coarse, packed_t_coarse, desc_fine, packed_fine, packed_t_fine, desc_warp,
-                                                   packed_warp, packed_t_warp, precision, batch, pose_enc, rays_per_chunk, workspace,
-                                                   grad_coarse, grad_fine, grad_warp, loss, rgb, rgb_fine, stream);
-    if (rc) return rc;
-    if ((rc = dp_allreduce_avg(comm, const_cast<float *>(adam->grads), 0, adam->n_params, 0, 0, (hipStream_t)stream, "smpl_nerf_train_step_dp")))
-        return rc;
-    if ((rc = snerf_adam_step_f32(adam, ranges_host, n_ranges, nets_host, n_nets, stream))) return rc;
-    return snerf_warp_repack_f32(desc_warp, adam->params, adam->n_params, warp_param_offset, packed_warp, packed_t_warp, stream);
+    TrainArgs a{};
+    a.coarse = {desc_coarse, packed_coarse, packed_t_coarse, grad_coarse};
+    a.fine = {desc_fine, packed_fine, packed_t_fine, grad_fine};
+    a.warp = {desc_warp, packed_warp, packed_t_warp, grad_warp, pose_enc};
+    a.precision = precision, a.batch = batch, a.rays_per_chunk = rays_per_chunk, a.workspace = workspace;
+    a.loss = loss, a.rgb = rgb, a.rgb_fine = rgb_fine, a.stream = stream;
+    a.comm = comm, a.flat_g = const_cast<float *>(adam->grads), a.flat_n = adam->n_params;
+    if (int rc = smpl_nerf_train_grads(a)) return rc;
+    return finish_step(a, {adam, ranges_host, n_ranges, nets_host, n_nets}, "smpl_nerf_train_step_dp", warp_param_offset);
 }
 
 extern "C" int snerf_warp_repack_f32(const snerf_warp_desc *desc_warp, const float *params, int64_t n_params, int64_t warp_param_offset,

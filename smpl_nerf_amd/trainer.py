@@ -21,6 +21,7 @@ from __future__ import annotations
 import ctypes
 import os
 import time
+from types import SimpleNamespace
 
 import torch
 
@@ -198,6 +199,26 @@ class HipAdam:
         self._host_steps = steps
         self.steps.copy_(torch.tensor(steps, dtype=torch.int64))
         self._range_cache = (None, None, 0)
+
+
+# ---- the entries of the one-call training step -----------------------------------------------------------------------------
+# How a rank steps: alone; as one of several with RCCL's all-reduce inside the call (_init_comm); or as three calls - the
+# gradient entry, torch.distributed's all-reduce of the flat buffer, snerf_adam_step_f32 (and snerf_warp_repack_f32).
+_ALONE, _RCCL_INSIDE, _THREE_CALL = "alone", "RCCL inside", "three-call"
+_NERF_GRADS, _SMPL_GRADS = ("nets", "batch", "out"), ("nets", "warp", "batch", "out")
+_SMPL_STEP = ("snerf_smpl_nerf_train_step_aux_f32", _SMPL_GRADS + ("adam", "warp_offset", "comm", "streams"))      # comm may be None
+# (warp stage, input gradients, mode) -> (entry, the parts of its argument list in order; _step_one_call_impl builds the parts)
+_ENTRIES = {
+    (False, False, _ALONE): ("snerf_nerf_train_step_f32", _NERF_GRADS + ("adam", "streams")),
+    (False, True, _ALONE): ("snerf_nerf_train_step_ig_f32", _NERF_GRADS + ("adam", "ig", "streams")),
+    (True, False, _ALONE): _SMPL_STEP,
+    (False, False, _RCCL_INSIDE): ("snerf_nerf_train_step_dp_f32", _NERF_GRADS + ("adam", "comm", "streams")),
+    (False, True, _RCCL_INSIDE): ("snerf_nerf_train_step_dp_ig_f32", _NERF_GRADS + ("adam", "ig", "comm", "streams")),
+    (True, False, _RCCL_INSIDE): _SMPL_STEP,
+    (False, False, _THREE_CALL): ("snerf_nerf_train_grads_f32", _NERF_GRADS + ("streams",)),
+    (False, True, _THREE_CALL): ("snerf_nerf_train_grads_ig_f32", _NERF_GRADS + ("ig", "streams")),
+    (True, False, _THREE_CALL): ("snerf_smpl_nerf_train_grads_aux_f32", _SMPL_GRADS + ("streams",)),
+}
 
 
 class DataParallelTrainer:
@@ -490,39 +511,31 @@ class DataParallelTrainer:
             raise RuntimeError("DataParallelTrainer: the pose rows do not match the nets' additional_input_dim")
         return add.float()
 
-    def _step_one_call_impl(self, oc, batch, add_graph):
-        from . import ops
+    # -- marshalling for the call: one job each ---------------------------------------------------------------------------
+    def _oc_unpack(self, oc, batch, add_graph):
+        """The batch tensors by name (contiguous; detached where autograd was on for the rows) and the per-ray rows the nets read."""
+        ts = [(t.detach() if oc["posed"] else t).contiguous() for t in batch]
+        return SimpleNamespace(ray_samples=ts[0], rays_o=ts[1], rays_d=ts[2], z_vals=ts[3], rgb_truth=ts[-1],
+                               goal_pose=ts[4] if oc["warp"] is not None else None,
+                               add=add_graph.detach() if oc["posed"] else None)
+
+    def _oc_nets(self, oc, Nf):
+        """The two nets' descriptors, weight streams and snerf_adam_net records (slot tables cached in oc["slots"]).  With the warp
+        stage the nets back-propagate into their inputs (input_grad = 1 streams)."""
         from .nets import _split_code
-        lib = oc["lib"]
-        pipe, args = self.pipeline, self.pipeline.args
-        W = oc["warp"]
-        goal_pose = add = None
-        want_d_add = add_graph is not None and add_graph.requires_grad
-        if oc["verts"]:
-            ray_samples, rays_o, rays_d, z_vals, images, rgb_truth = (t.detach().contiguous() for t in batch)
-            add = add_graph.detach()
-        elif oc["posed"]:
-            ray_samples, rays_o, rays_d, z_vals, goal_pose, rgb_truth = (t.detach().contiguous() for t in batch)
-            add = add_graph.detach()
-        elif W is not None:
-            ray_samples, rays_o, rays_d, z_vals, goal_pose, rgb_truth = (t.contiguous() for t in batch)
-        else:
-            ray_samples, rays_o, rays_d, z_vals, rgb_truth = (t.contiguous() for t in batch)
-        dev = self._flat_p.device
-        B, Nc = z_vals.shape
-        Nf = int(args.number_fine_samples) if args.run_fine else 0
+        pipe = self.pipeline
         mc, mf = oc["nets"]
         ns = _split_code(mc, 0)
         if Nf and _split_code(mf, 0) != ns:
             raise RuntimeError("DataParallelTrainer: both nets must use the same precision mode")
-        descs, packed, packed_t, nets_c = [], [], [], (_lib.AdamNet * 2)()
+        ig = oc["warp"] is not None
+        descs, packed, packed_t, adam = [], [], [], (_lib.AdamNet * 2)()
         for k, m in enumerate((mc, mf)):
             d = m.desc_for_rows() if oc["verts"] else m.desc_for_encoders(pipe.position_encoder, pipe.direction_encoder, bool(oc["posed"]))
             descs.append(d)
             if k == 1 and not Nf:          # run_fine = 0: the fine net takes no part (models/nerf_pipeline.py:43-44)
                 packed.append(None), packed_t.append(None)
                 continue
-            ig = W is not None          # the warp stage: the nets back-propagate into their inputs (input_grad = 1 streams)
             if ns:
                 packed.append(m.packed_weights_bf16(d, ns, training=True))
                 packed_t.append(m.packed_weights_t_bf16(d, ns, ig))
@@ -531,164 +544,182 @@ class DataParallelTrainer:
                 packed.append(m.packed_weights(d, training=True))
                 packed_t.append(m.packed_weights_t(d, ig))
                 sf, st = self._slot_tables(oc, m, d, ig)
-            nets_c[k] = _lib.AdamNet(ctypes.pointer(d), oc["seg"][k][0], ns, packed[k].data_ptr(), packed_t[k].data_ptr(),
-                                     _lib.ptr(sf), _lib.ptr(st))
-        n_nets = 2 if Nf else 1
-        if W is not None:
-            mw, pe_ = W["net"], pipe.position_encoder
-            wdesc = _lib.WarpDesc(mw.width, pe_.number_frequencies, 1 if pe_.include_identity else 0, mw.direcions_dim)
-            packed_w = mw._packed(wdesc, training=True)
-            if W["packed_t"] is None or W["packed_t"][0] is not packed_w:      # (a re-built forward stream = the weights changed behind the step)
-                sizes = [ctypes.c_int64() for _ in range(4)]
-                _lib.check(lib.snerf_warp_train_sizes(wdesc, 0, *[ctypes.byref(v) for v in sizes]), "snerf_warp_train_sizes")
-                pt = torch.empty(sizes[2].value, device=dev, dtype=torch.float32)
-                seg_w = self._flat_p[W["seg"][0]:W["seg"][0] + W["seg"][1]]
-                with torch.cuda.device(dev):
-                    _lib.check(lib.snerf_warp_pack_t_f32(wdesc, seg_w.data_ptr(), pt.data_ptr(), _lib.current_stream()), "snerf_warp_pack_t_f32")
-                W["packed_t"] = (packed_w, pt)
-            packed_t_w = W["packed_t"][1]
-            two = torch.stack([goal_pose[:, 38], goal_pose[:, 41]], axis=-1).contiguous()          # models/smpl_nerf_pipeline.py:28
-            pose_enc = pipe.human_pose_encoder.encode(two).contiguous()                              # :30
-            need = int(lib.snerf_smpl_nerf_train_workspace_bytes(descs[0], descs[1] if Nf else None, wdesc, B, Nc, Nf, self.rays_per_chunk))
+            adam[k] = _lib.AdamNet(ctypes.pointer(d), oc["seg"][k][0], ns, packed[k].data_ptr(), packed_t[k].data_ptr(),
+                                   _lib.ptr(sf), _lib.ptr(st))
+        return SimpleNamespace(ns=ns, descs=descs, packed=packed, packed_t=packed_t, adam=adam, n_adam=2 if Nf else 1)
+
+    def _oc_warp(self, oc, goal_pose):
+        """The warp net's descriptor, its streams (the transposed one is kept in oc["warp"] until the forward stream is re-built: the
+        weights changed behind the step) and the encoded pose rows."""
+        lib, pipe, W, dev = oc["lib"], self.pipeline, oc["warp"], self._flat_p.device
+        mw, pe_ = W["net"], pipe.position_encoder
+        wdesc = _lib.WarpDesc(mw.width, pe_.number_frequencies, 1 if pe_.include_identity else 0, mw.direcions_dim)
+        packed_w = mw._packed(wdesc, training=True)
+        if W["packed_t"] is None or W["packed_t"][0] is not packed_w:
+            sizes = [ctypes.c_int64() for _ in range(4)]
+            _lib.check(lib.snerf_warp_train_sizes(wdesc, 0, *[ctypes.byref(v) for v in sizes]), "snerf_warp_train_sizes")
+            pt = torch.empty(sizes[2].value, device=dev, dtype=torch.float32)
+            seg_w = self._flat_p[W["seg"][0]:W["seg"][0] + W["seg"][1]]
+            with torch.cuda.device(dev):
+                _lib.check(lib.snerf_warp_pack_t_f32(wdesc, seg_w.data_ptr(), pt.data_ptr(), _lib.current_stream()), "snerf_warp_pack_t_f32")
+            W["packed_t"] = (packed_w, pt)
+        two = torch.stack([goal_pose[:, 38], goal_pose[:, 41]], axis=-1).contiguous()          # models/smpl_nerf_pipeline.py:28
+        pose_enc = pipe.human_pose_encoder.encode(two).contiguous()                              # :30
+        return SimpleNamespace(desc=wdesc, packed=packed_w, packed_t=W["packed_t"][1], pose_enc=pose_enc, off=W["seg"][0])
+
+    def _oc_workspace(self, oc, nets, warp, B, Nc, Nf):
+        """oc["ws"], grown to what this batch needs."""
+        lib, fine = oc["lib"], nets.descs[1] if Nf else None
+        if warp is not None:
+            need = int(lib.snerf_smpl_nerf_train_workspace_bytes(nets.descs[0], fine, warp.desc, B, Nc, Nf, self.rays_per_chunk))
         else:
-            need = int(lib.snerf_nerf_train_workspace_bytes(descs[0], descs[1] if Nf else None, B, Nc, Nf, self.rays_per_chunk))
+            need = int(lib.snerf_nerf_train_workspace_bytes(nets.descs[0], fine, B, Nc, Nf, self.rays_per_chunk))
         if need < 0:
             _lib.check(need, "snerf_nerf_train_workspace_bytes")
         if oc["ws"] is None or oc["ws"].numel() < need:
             oc["ws"] = None
-            oc["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        out = torch.empty(4 + 6 * B, dtype=torch.float32, device=dev)
-        loss, rgb, rgb_fine = out[:3], out[4:4 + 3 * B].view(B, 3), out[4 + 3 * B:].view(B, 3)
+            oc["ws"] = torch.empty(need, dtype=torch.uint8, device=self._flat_p.device)
+        return oc["ws"]
+
+    def _oc_batch(self, t, B, Nc, Nf):
+        """The snerf_nerf_batch record, and the tensors only it points at (u, the sigma noise): the caller keeps them until the call."""
+        pipe, dev = self.pipeline, self._flat_p.device
         u = ops.uniform_u(Nf, dev) if Nf else None
         nz_c = pipe._noise((B, Nc), dev)
         nz_f = pipe._noise((B, Nc + Nf), dev) if Nf else None
-        cb = _lib.NerfBatch(ray_samples.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), z_vals.data_ptr(),
-                            rgb_truth.data_ptr(), _lib.ptr(u), _lib.ptr(nz_c), _lib.ptr(nz_f), _lib.ptr(add), B, Nc, Nf,
-                            1 if args.white_background else 0)
-        (oc_off, oc_n), (of_off, of_n) = oc["seg"]
-        g_c = self._flat_g.data_ptr() + 4 * oc_off
-        g_f = self._flat_g.data_ptr() + 4 * of_off
-        # the precision argument of the entries: the nets' code, with SNERF_REFERENCE_SUM for the strict sampler (nets_c keeps ns)
-        prec = ns | (_lib.REFERENCE_SUM if getattr(args, "strict_cumsum", 0) else 0)
-        head = (descs[0], packed[0].data_ptr(), packed_t[0].data_ptr(), descs[1] if Nf else None, _lib.ptr(packed[1]),
-                _lib.ptr(packed_t[1]), prec, ctypes.byref(cb), self.rays_per_chunk, oc["ws"].data_ptr(), g_c, g_f if Nf else None,
-                loss.data_ptr(), rgb.data_ptr(), rgb_fine.data_ptr())
-        opt = self.optim
-        aux = oc["aux"].cuda_stream if oc["aux"] is not None else None
-        live = oc["tensors"][0] | (oc["tensors"][1] if Nf or self._sync else frozenset())
-        if W is not None:
-            live = live | W["tensors"]
-        flags = [i in live for i in range(len(self.params))]
-        # the call(s): one entry when this rank steps alone; its two halves around the all-reduce otherwise
-        stream = _lib.current_stream
-        if W is not None:
-            w_off = W["seg"][0]
-            g_w = self._flat_g.data_ptr() + 4 * w_off
-            head = head[:6] + (wdesc, packed_w.data_ptr(), packed_t_w.data_ptr(), prec, ctypes.byref(cb), pose_enc.data_ptr(),
-                               self.rays_per_chunk, oc["ws"].data_ptr(), g_c, g_f if Nf else None, g_w, loss.data_ptr(), rgb.data_ptr(),
-                               rgb_fine.data_ptr())
-            # (the _aux_ forms, 0.1.8: small chunks run the coarse chain of the backward on the auxiliary stream; comm may be None)
-            name, tail = "snerf_smpl_nerf_train", (aux,)
-            step_tail = lambda st, ranges, nr, comm=None: (ctypes.byref(st), ranges, nr, nets_c, n_nets, w_off, comm, stream(), aux)
-        else:
-            name, tail = "snerf_nerf_train", (aux,)
-            step_tail = lambda st, ranges, nr: (ctypes.byref(st), ranges, nr, nets_c, n_nets, stream(), aux)
+        cb = _lib.NerfBatch(t.ray_samples.data_ptr(), t.rays_o.data_ptr(), t.rays_d.data_ptr(), t.z_vals.data_ptr(),
+                            t.rgb_truth.data_ptr(), _lib.ptr(u), _lib.ptr(nz_c), _lib.ptr(nz_f), _lib.ptr(t.add), B, Nc, Nf,
+                            1 if pipe.args.white_background else 0)
+        return cb, (u, nz_c, nz_f)
+
+    def _oc_input_grads(self, oc, add, Nf):
+        """d loss / d additional rows comes back from the call (include/smplnerf.h: snerf_input_grads): the record and the rows' gradient."""
+        d_add = torch.empty_like(add)
+        pc, pf = (self._flat_p.data_ptr() + 4 * off for off, _ in oc["seg"])
+        return _lib.InputGrads(d_add.data_ptr(), pc, pf if Nf else None), d_add
+
+    def _step_one_call_impl(self, oc, batch, add_graph):
+        args, dev = self.pipeline.args, self._flat_p.device
+        t = self._oc_unpack(oc, batch, add_graph)
+        B, Nc = t.z_vals.shape
+        Nf = int(args.number_fine_samples) if args.run_fine else 0
+        nets = self._oc_nets(oc, Nf)
+        warp = self._oc_warp(oc, t.goal_pose) if oc["warp"] is not None else None
+        ws = self._oc_workspace(oc, nets, warp, B, Nc, Nf)
+        out = torch.empty(4 + 6 * B, dtype=torch.float32, device=dev)
+        loss, rgb, rgb_fine = out[:3], out[4:4 + 3 * B].view(B, 3), out[4 + 3 * B:].view(B, 3)
+        cb, _keep = self._oc_batch(t, B, Nc, Nf)
         ig = d_add = None
-        if want_d_add:      # d loss / d additional rows comes back from the call (include/smplnerf.h: snerf_input_grads)
-            d_add = torch.empty_like(add)
-            pc = self._flat_p.data_ptr() + 4 * oc_off
-            pf = self._flat_p.data_ptr() + 4 * of_off
-            ig = _lib.InputGrads(d_add.data_ptr(), pc, pf if Nf else None)
-        with torch.cuda.device(dev), _lib.timed(f"train_step{'_smpl' if W is not None else ''}[B={B}]"):
-            comm = self._rccl_comm(dev) if self._sync else None
-            if not self._sync and ig is not None:
-                ranges, nr = opt.c_ranges(flags)
-                st = opt.c_state()
-                _lib.check(lib.snerf_nerf_train_step_ig_f32(*head, ctypes.byref(st), ranges, nr, nets_c, n_nets, ctypes.byref(ig), stream(), aux),
-                           "snerf_nerf_train_step_ig_f32")
-                opt.commit_step()
-            elif not self._sync:
-                ranges, nr = opt.c_ranges(flags)
-                st = opt.c_state()
-                entry = name + ("_step_aux_f32" if W is not None else "_step_f32")
-                _lib.check(getattr(lib, entry)(*head, *step_tail(st, ranges, nr)), entry)
-                opt.commit_step()
-            elif comm is not None:
-                # more than one rank, one call all the same: the gradient average is RCCL's ncclAllReduce(ncclAvg) of the flat
-                # buffer inside the call, on the compute stream between the backward and Adam (include/smplnerf.h 8(e))
-                if not Nf:      # every rank contributes the same shape: zeros for the net that took no part
-                    self._flat_g[of_off:of_off + of_n].zero_()
-                ranges, nr = opt.c_ranges(flags)
-                st = opt.c_state()
-                if ig is not None:
-                    # ... and with d loss / d additional rows coming back (r06: snerf_nerf_train_step_dp_ig_f32; the rows are this
-                    # rank's own rays - the estimator's gradient is averaged below, behind its autograd)
-                    _lib.check(lib.snerf_nerf_train_step_dp_ig_f32(*head, ctypes.byref(st), ranges, nr, nets_c, n_nets, ctypes.byref(ig),
-                                                                   comm.handle, stream(), aux), "snerf_nerf_train_step_dp_ig_f32")
-                else:
-                    if W is not None:
-                        t, entry = step_tail(st, ranges, nr, comm.handle), name + "_step_aux_f32"
-                    else:
-                        t = step_tail(st, ranges, nr)
-                        t, entry = t[:-2] + (comm.handle,) + t[-2:], name + "_step_dp_f32"
-                    _lib.check(getattr(lib, entry)(*head, *t), entry)
-                opt.commit_step()
-                self.collective_calls = getattr(self, "collective_calls", 0) + 1
-            else:
-                if ig is not None:
-                    _lib.check(lib.snerf_nerf_train_grads_ig_f32(*head, ctypes.byref(ig), stream(), aux), "snerf_nerf_train_grads_ig_f32")
-                else:
-                    entry = name + ("_grads_aux_f32" if W is not None else "_grads_f32")
-                    _lib.check(getattr(lib, entry)(*head, stream(), *tail), entry)
-                if ig is not None and oc["upstream"]:      # the upstream modules' gradients must be in the flat buffer before it is averaged
-                    self._upstream_backward(oc, add_graph, d_add)
-                if not Nf:      # every rank contributes the same shape: zeros for the net that took no part
-                    self._flat_g[of_off:of_off + of_n].zero_()
-                self._allreduce_flat()
-                if ig is not None and oc["upstream"]:
-                    flags = [f or (i in oc["upstream_tensors"]) for i, f in enumerate(flags)]
-                ranges, nr = opt.c_ranges(flags)
-                st = opt.c_state()
-                _lib.check(lib.snerf_adam_step_f32(ctypes.byref(st), ranges, nr, nets_c, n_nets, stream()), "snerf_adam_step_f32")
-                opt.commit_step()
-                if W is not None:
-                    _lib.check(lib.snerf_warp_repack_f32(wdesc, self._flat_p.data_ptr(), self._flat_p.numel(), w_off, packed_w.data_ptr(),
-                                                         packed_t_w.data_ptr(), stream()), "snerf_warp_repack_f32")
-        if self._sync and not Nf and hasattr(mf, "mark_weights_changed"):
-            #  run_fine = 0 with more than one rank: the fine net's parameters are live in the ranges (zero gradients:
-            # weight decay and resumed moments still move them) but its streams were not among the nets the call refreshed
-            mf.mark_weights_changed()
-        if ig is not None and not (self._sync and comm is None and oc["upstream"]):
-            # back through what produced the rows: a goal_pose that wants its gradient gets it here; a trained estimator's parameter
-            # gradients land in the flat buffer and its tensors take their optimiser step (a second, small C-ABI call)
-            self._upstream_backward(oc, add_graph, d_add)
-            if oc["upstream"]:
-                uflags = [i in oc["upstream_tensors"] for i in range(len(self.params))]
-                if comm is not None:      # more than one rank: the upstream tensors' stretches of the flat gradient, averaged
-                    idx = sorted(oc["upstream_tensors"])
-                    k = 0
-                    while k < len(idx):
-                        j = k
-                        while j + 1 < len(idx) and idx[j + 1] == idx[j] + 1:
-                            j += 1
-                        comm.allreduce_avg_(self._flat_g[opt.offsets[idx[k]]:opt.offsets[idx[j] + 1]])
-                        k = j + 1
-                with torch.cuda.device(dev):
-                    ranges, nr = opt.c_ranges(uflags)
-                    if nr:
-                        st = opt.c_state()
-                        _lib.check(lib.snerf_adam_step_f32(ctypes.byref(st), ranges, nr, None, 0, stream()), "snerf_adam_step_f32")
-                        opt.commit_step()
-                flags = [a or b for a, b in zip(flags, uflags)]
-        elif ig is not None:
-            flags = [f or (i in oc["upstream_tensors"]) for i, f in enumerate(flags)]
+        if add_graph is not None and add_graph.requires_grad:
+            ig, d_add = self._oc_input_grads(oc, t.add, Nf)
+        comm = self._rccl_comm(dev) if self._sync else None
+        mode = _ALONE if not self._sync else (_RCCL_INSIDE if comm is not None else _THREE_CALL)
+        live = oc["tensors"][0] | (oc["tensors"][1] if Nf or self._sync else frozenset())
+        if warp is not None:
+            live = live | oc["warp"]["tensors"]
+        # the parts the entries' argument lists are made of (_ENTRIES); the Adam part and the streams are added at the call
+        d, g = nets.descs, self._flat_g.data_ptr()
+        g_c, g_f = g + 4 * oc["seg"][0][0], (g + 4 * oc["seg"][1][0] if Nf else None)
+        # the precision argument of the entries: the nets' code, with SNERF_REFERENCE_SUM for the strict sampler (the AdamNets keep ns)
+        prec = nets.ns | (_lib.REFERENCE_SUM if getattr(args, "strict_cumsum", 0) else 0)
+        parts = {"nets": (d[0], nets.packed[0].data_ptr(), nets.packed_t[0].data_ptr(), d[1] if Nf else None, _lib.ptr(nets.packed[1]),
+                          _lib.ptr(nets.packed_t[1])),
+                 "batch": (prec, ctypes.byref(cb), self.rays_per_chunk, ws.data_ptr(), g_c, g_f),
+                 "out": (loss.data_ptr(), rgb.data_ptr(), rgb_fine.data_ptr()),
+                 "ig": (ctypes.byref(ig) if ig is not None else None,),
+                 "comm": (comm.handle if comm is not None else None,)}
+        if warp is not None:
+            parts["warp"] = (warp.desc, warp.packed.data_ptr(), warp.packed_t.data_ptr())
+            parts["batch"] = (prec, ctypes.byref(cb), warp.pose_enc.data_ptr(), self.rays_per_chunk, ws.data_ptr(), g_c, g_f, g + 4 * warp.off)
+            parts["warp_offset"] = (warp.off,)
+        s = SimpleNamespace(oc=oc, mode=mode, comm=comm, Nf=Nf, nets=nets, warp=warp, ig=ig, d_add=d_add, add_graph=add_graph,
+                            flags=[i in live for i in range(len(self.params))],
+                            # three-call form with trained modules in front of the nets: their gradients must be in the flat buffer
+                            # before it is averaged, so their backward runs ahead of the all-reduce instead of behind the step
+                            upstream_first=mode == _THREE_CALL and ig is not None and bool(oc["upstream"]))
+        with torch.cuda.device(dev), _lib.timed(f"train_step{'_smpl' if warp is not None else ''}[B={B}]"):
+            self._oc_call(s, parts)
+        self._oc_after_call(s)
         # p.grad = what autograd would have left: views of the flat gradient buffer (None for a net that took no part)
         for i, (p, v) in enumerate(zip(self.params, self._views)):
-            want = v if flags[i] else None
+            want = v if s.flags[i] else None
             if p.grad is not want:
                 p.grad = want
         self.last_outputs = (rgb, rgb_fine)
         return loss[0]
+
+    def _zero_idle_fine_segment(self, s):
+        """run_fine = 0 on a rank of several: every rank contributes the same shape, zeros for the net that took no part."""
+        if not s.Nf:
+            off, n = s.oc["seg"][1]
+            self._flat_g[off:off + n].zero_()
+
+    def _oc_call(self, s, parts):
+        """The entry _ENTRIES names for this configuration; in three-call mode the gradient entry, then the all-reduce of the flat
+        buffer, Adam and the warp net's re-pack as calls of their own."""
+        lib, opt, stream = s.oc["lib"], self.optim, _lib.current_stream()
+        entry, order = _ENTRIES[s.warp is not None, s.ig is not None, s.mode]
+        parts["streams"] = (stream, s.oc["aux"].cuda_stream if s.oc["aux"] is not None else None)
+        if s.mode != _THREE_CALL:
+            if s.mode == _RCCL_INSIDE:
+                # more than one rank, one call all the same: the gradient average is RCCL's ncclAllReduce(ncclAvg) of the flat
+                # buffer inside the call, on the compute stream between the backward and Adam (include/smplnerf.h 8(e))
+                self._zero_idle_fine_segment(s)
+            ranges, nr = opt.c_ranges(s.flags)
+            st = opt.c_state()
+            parts["adam"] = (ctypes.byref(st), ranges, nr, s.nets.adam, s.nets.n_adam)
+        _lib.check(getattr(lib, entry)(*[a for name in order for a in parts[name]]), entry)
+        if s.mode != _THREE_CALL:
+            opt.commit_step()
+            if s.mode == _RCCL_INSIDE:
+                self.collective_calls = getattr(self, "collective_calls", 0) + 1
+            return
+        if s.upstream_first:
+            self._upstream_backward(s.oc, s.add_graph, s.d_add)
+        self._zero_idle_fine_segment(s)
+        self._allreduce_flat()
+        if s.upstream_first:
+            s.flags = [f or (i in s.oc["upstream_tensors"]) for i, f in enumerate(s.flags)]
+        ranges, nr = opt.c_ranges(s.flags)
+        st = opt.c_state()
+        _lib.check(lib.snerf_adam_step_f32(ctypes.byref(st), ranges, nr, s.nets.adam, s.nets.n_adam, stream), "snerf_adam_step_f32")
+        opt.commit_step()
+        if s.warp is not None:
+            _lib.check(lib.snerf_warp_repack_f32(s.warp.desc, self._flat_p.data_ptr(), self._flat_p.numel(), s.warp.off,
+                                                 s.warp.packed.data_ptr(), s.warp.packed_t.data_ptr(), stream), "snerf_warp_repack_f32")
+
+    def _oc_after_call(self, s):
+        """What follows the call(s) of a step in every mode: the idle fine net's streams, then the autograd of what produced the
+        rows - a goal_pose that wants its gradient gets it here; a trained estimator's parameter gradients land in the flat buffer,
+        are averaged over the ranks and its tensors take their optimiser step (a second, small C-ABI call).  Updates s.flags."""
+        oc, opt, mf = s.oc, self.optim, s.oc["nets"][1]
+        if self._sync and not s.Nf and hasattr(mf, "mark_weights_changed"):
+            # (ADVICE r04) run_fine = 0 with more than one rank: the fine net's parameters are live in the ranges (zero gradients:
+            # weight decay and resumed moments still move them) but its streams were not among the nets the call refreshed
+            mf.mark_weights_changed()
+        if s.ig is None or s.upstream_first:
+            return
+        self._upstream_backward(oc, s.add_graph, s.d_add)
+        if not oc["upstream"]:
+            return
+        if s.comm is not None:      # more than one rank: the upstream tensors' stretches of the flat gradient, averaged
+            idx = sorted(oc["upstream_tensors"])
+            k = 0
+            while k < len(idx):
+                j = k
+                while j + 1 < len(idx) and idx[j + 1] == idx[j] + 1:
+                    j += 1
+                s.comm.allreduce_avg_(self._flat_g[opt.offsets[idx[k]]:opt.offsets[idx[j] + 1]])
+                k = j + 1
+        uflags = [i in oc["upstream_tensors"] for i in range(len(self.params))]
+        with torch.cuda.device(self._flat_p.device):
+            ranges, nr = opt.c_ranges(uflags)
+            if nr:
+                st = opt.c_state()
+                _lib.check(oc["lib"].snerf_adam_step_f32(ctypes.byref(st), ranges, nr, None, 0, _lib.current_stream()), "snerf_adam_step_f32")
+                opt.commit_step()
+        s.flags = [a or b for a, b in zip(s.flags, uflags)]
+
 
     def step(self, batch):
         """One optimisation step on this rank's batch (list of tensors, rgb_truth last). Returns the
