@@ -10,13 +10,15 @@
 //   * v_mfma_f32_16x16x4_f32: exact fp32 products and accumulation (bitwise an fmaf chain), so the
 //     result sits at the fp32 round-off floor of the reference's MKL sgemm path (parity 1e-4 on RGB
 //     needs this: plain bf16 misses it by 100x).  Peak 157.3 TFLOP/s on MI355X;
-//   * the weights of all layers form one contiguous stream of 17 KiB slabs in consumption order
-//     (packed once per weight update by mlp_pack_kernel).  The NWAVES waves of a workgroup stream
-//     it from L2 through a 3-slot LDS ring: slab p is consumed from LDS while slab p+1 already
-//     sits in LDS and slab p+2 is in flight in registers - one workgroup barrier per slab
-//     (64 MFMAs per wave);
-//   * several independent workgroups per CU (2 waves per SIMD) keep the matrix pipe busy while
-//     one of them is at its barrier or evaluating sin/cos;
+//   * the weights of all layers form one contiguous stream of 33 KiB slabs (32 A tiles of 1 KiB and a bias block) in
+//     consumption order (packed once per weight update by mlp_pack_kernel).  The waves of a workgroup stream it from L2
+//     through an LDS ring, one workgroup barrier per slab (128 MFMAs per wave at width 256): the 8-wave inference kernel of
+//     width 256 and every kernel of the widths above 256 by LDS-DMA into a 4-slot ring - slab p consumed, p+1 resident, p+2
+//     landing and p+3 being issued ACROSS the slab barrier, i.e. two periods for a slab to land (mlp_device.h: SlabPipeDma) -, the
+//     others through registers into a 3-slot ring (SlabPipe);
+//   * one persistent workgroup per CU (the ring leaves LDS for no second one; 8 waves = 2 per SIMD at width 256, which keep the
+//     matrix pipe busy while one of them is at its barrier or evaluating sin/cos), walking the sample tiles with the ring
+//     rolling on from tile to tile;
 //   * positional encodings are evaluated in registers, straight into B-operand layout, with
 //     full-range sincosf (arguments reach 2^9*|x|); they are recomputed at the skip layer instead of
 //     being kept live.
@@ -68,7 +70,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     const int enc_pos_off = A.add_first ? A.add_dim : 0, enc_add_off = A.add_first ? 0 : A.pos_dim;
     const int enc_dir_off = A.enc_stride - A.dir_dim;  // directions = x[..., -dir_dim:] (:43)
 
-    // Persistent workgroups: one per CU (the 99 KiB ring allows no more), each walking the sample tiles blockIdx.x,
+    // Persistent workgroups: one per CU (the 99 / 132 KiB ring allows no more), each walking the sample tiles blockIdx.x,
     // blockIdx.x + gridDim.x, ...  The weight ring keeps rolling from one tile into the next (the stream wraps around),
     // so only the first tile of a workgroup pays the pipeline fill and no CU idles between two workgroups.
     using Pipe = std::conditional_t<(!TRAIN && WIDTH == 256 && NWAVES == 8), SlabPipeDma<NT>, PipeFor<WIDTH, NT>>;
@@ -82,15 +84,14 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     auto load_raw = [&](int64_t t) __attribute__((always_inline)) {
         const int64_t s0 = (t * NWAVES + wave) * 16 + (lane & 15);
         const int64_t s1 = s0 < A.n ? s0 : A.n - 1;
-        raw_in[0] = A.x[s1 * 3 + 0];
-        raw_in[1] = A.x[s1 * 3 + 1];
-        raw_in[2] = A.x[s1 * 3 + 2];
-        if (A.use_dir) {
-            const float *dp = A.dirs + (A.dirs_per_sample ? s1 : s1 / A.spr) * 3;
-            raw_in[3] = dp[0], raw_in[4] = dp[1], raw_in[5] = dp[2];
-        }
+        // no branch around the loads (a net without directions re-reads the position, unused): behind a branch hipcc merges the
+        // loaded values with the old ones in other registers, which waits for them - and for the weight ring's DMA - on the spot
+        const float *xp = A.x + s1 * 3;
+        const float *dp = A.use_dir ? A.dirs + (A.dirs_per_sample ? s1 : s1 / A.spr) * 3 : xp;
+        raw_in[0] = xp[0], raw_in[1] = xp[1], raw_in[2] = xp[2];
+        raw_in[3] = dp[0], raw_in[4] = dp[1], raw_in[5] = dp[2];
     };
-    if (PREFETCH && blockIdx.x < A.n_tiles) load_raw(blockIdx.x);
+    if (PREFETCH) load_raw(blockIdx.x);   // (a tile of this launch: launch_fwd_nw keeps the grid at most n_tiles; the sample index is clamped)
     int64_t tile = blockIdx.x;
     do {
     const int64_t sample = (tile * NWAVES + wave) * 16 + (lane & 15);
@@ -106,6 +107,9 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
         c.enc = A.x + sc * A.enc_stride;
     } else {
         if (!PREFETCH) load_raw(tile);
+        // the one point of a tile that waits for plain loads (the prefetched inputs: a full drain, once per 77 slabs); without it
+        // hipcc waits at every use of a position in the encoder loops, draining the weight ring's DMA there
+        if (PREFETCH) asm volatile("" : "+v"(raw_in[0]), "+v"(raw_in[1]), "+v"(raw_in[2]), "+v"(raw_in[3]), "+v"(raw_in[4]), "+v"(raw_in[5]));
         c.px = raw_in[0];
         c.py = raw_in[1];
         c.pz = raw_in[2];
@@ -221,7 +225,8 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
         run.finish();
         copy_into(ind, accd);
         if (TRAIN && valid) store_tiles(A.act, A.act_h1, A.n, sample, c.g, ind);
-        if (PREFETCH && tile + gridDim.x < A.n_tiles) load_raw(tile + gridDim.x);   // lands behind the last two layers
+        // lands behind the last two layers (a workgroup's last tile fetches its own inputs again: no branch around the loads)
+        if (PREFETCH) load_raw(tile + gridDim.x < A.n_tiles ? tile + gridDim.x : tile);
     }
     {  // directional_net[0] + relu (:58-59)
         LayerRun<TD, NT, Pipe> run(pipe, lane);
@@ -338,6 +343,7 @@ static int launch_fwd_nw(const Plan &P, const FwdArgs &A, hipStream_t s, int64_t
     if (B.n_tiles > 0x7fffffffLL) return fail(SNERF_E_BADARG, "mlp_fwd: n too large");
     const int n_cu = device_cu_count("mlp_fwd");  // one persistent workgroup per CU
     if (n_cu < 1) return n_cu;
+    // grid <= n_tiles, always: the inference kernels fetch the inputs of tile blockIdx.x unconditionally (mlp_fwd_body: load_raw)
     const int64_t grid = (!TRAIN && B.n_tiles > n_cu) ? n_cu : B.n_tiles;
     if constexpr (FOLD) {
         if (P.width == 256) {

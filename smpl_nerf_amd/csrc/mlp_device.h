@@ -238,35 +238,83 @@ struct SlabPipe {
     __device__ __forceinline__ void drain() {}   // (loads into registers: nothing of this pipe can land after the kernel)
 };
 
-// The same interface with the slabs copied global -> LDS by DMA (`global_load_lds`, 16 B per lane: one instruction moves a 1 KiB
-// piece) into a 4-slot ring: no staging registers and half the instructions per slab of the register-staged pipe.  For the
-// kernels that run ONE wave per SIMD (widths above 256): there nobody issues MFMAs while a wave sits in its refill instructions
-// (each blocks the issuing wave for ~60 cycles, DESIGN_HISTORY 3.1), so their number is what the refill costs.
-// Ring: slab p consumed, p+1 resident and visible (as above), p+2 landing or landed, p+3 being issued into the slot slab p-1 left
-// at the last barrier.  A wave's pieces of a slab are complete before the barrier TWO slabs later (vmcnt leaves only the
-// newest slab's pieces in flight), i.e. a slab has two periods to arrive.
+// The same interface with the slabs copied global -> LDS by DMA (`global_load_lds_dwordx4`, 16 B per lane: one instruction moves
+// a 1 KiB piece) into a 4-slot ring: no staging registers and a fraction of the instructions per slab of the register-staged
+// pipe.  Each issued piece blocks the issuing wave for ~60 cycles (DESIGN_HISTORY 3.1).
+//
+// The DMA instructions are inline asm, and so are the waits and the barrier that end a slab.  Issued through the builtin, hipcc
+// counts every piece as a pending LDS write: `__syncthreads()` then drains the ring with `s_waitcnt vmcnt(0)` at every slab, and
+// with a raw barrier instead every LDS-read wait of the kernel degrades to `lgkmcnt(0)` (the pending "flat" operation makes the
+// counter unordered for the compiler), which serialises the A-operand prefetch of kblock() - as it did behind stage() in every
+// slab of the builtin form, which also spent a v_readfirstlane and a 64-bit add per piece.  Hidden from the compiler, a slab's
+// pieces are one M0 write and four instructions with immediate offsets, cost it no wait and no register (the 8-wave kernel:
+// 223 -> 199 VGPRs); their completion is counted here by hand.  That, not the longer landing time, is what the headline kernel
+// gained (37.3 -> 35.9 ms per frame; with `vmcnt(0)` at the barrier the asm form measures the same: DESIGN_HISTORY 3.1).
+// tests/test_weight_ring_isa.py holds the compiled kernel to the waits described here.
+//
+// Ring, while slab p is consumed (period p, barrier to barrier): p+1 resident, p+2 landing (issued in period p-1), p+3 issued
+// by stage() into the slot of p-1.  advance() ends period p with `s_waitcnt vmcnt(N)`, N = this wave's pieces of ONE slab
+// (PPW, + 1 for wave 0: the aux block), `s_waitcnt lgkmcnt(0)` and a raw `s_barrier`.  The safety argument, in counts:
+//   * vmcnt counts a wave's outstanding vector memory operations, loads and stores alike.  All the argument needs of the
+//     hardware is that LOADS (LDS-DMA pieces included) complete in issue order among themselves; stores may complete in any
+//     order.  Every period issues exactly one stage() (LayerRun::step / skip / finish: one stage() per advance(), partial slabs
+//     of the sigma / rgb / directional layers included), so at advance() of period p the N pieces of slab p+3 have been issued
+//     behind the pieces of slab p+2.  If a piece of p+2 were still outstanding, so would be all N newer pieces of p+3, and the
+//     count would be at least N + 1: `vmcnt(N)` cannot pass.  Whatever else the kernel body has outstanding (the next tile's
+//     inputs, the result store, additional-input or encoded operands, activation stores of a training forward) only adds to
+//     the count: the wait can then last longer than slab p+2 needs (it also waits for some pieces of p+3: slower, never wrong),
+//     never shorter.  A hipcc wait for one of ITS loads is `vmcnt(k)` with k counting only the later operations it knows:
+//     the pieces it does not know only add to the count, so that is an over-wait, too.
+//   * RAW: slab p+2 is complete in LDS once EVERY wave has passed its vmcnt(N) of period p, i.e. behind the barrier ending period
+//     p.  Its first read is the peek_next() prefetch (A pair, and the second bias block of 32-tile layers) in period p+1.  The
+//     prologue waits for slabs 0 .. 2 with vmcnt(0) before its barrier.
+//   * WAR: slot (p-1) & 3 is overwritten by pieces issued in period p.  The last LDS reads of slab p-1 are issued in period p-1
+//     (program order: LDS reads and the asm statements do not cross, "memory"), and `lgkmcnt(0)` ahead of the barrier ending p-1
+//     retires them in every wave - wherever hipcc put the MFMAs that consume them.  The pair prefetched across the barrier reads
+//     slab p, which is not overwritten before period p+1.
+//   * The stream of a persistent kernel wraps around (issue(): src == total) with the ring rolling on: the same counts hold across
+//     tiles.  drain() waits for the slabs issued ahead of the last one consumed before the workgroup's LDS is given back.
 template <int NT>
 struct SlabPipeDma {
     static constexpr int NW = NT / 64;
     static constexpr int PIECES = SLAB_A_FLOATS / 256;   // 1 KiB pieces of the A region (32); the aux block is one more (wave 0)
     static constexpr int PPW = PIECES / NW;
-    static_assert(PIECES % NW == 0, "pieces divide over the waves");
+    static_assert(PIECES % NW == 0 && PPW % 4 == 0, "pieces divide over the waves, in groups of four");
     const float *g, *g0;   // this lane's cursor in the stream (slab `src`, piece wave * PPW, lane's 16 B) and its position at slab 0
     int src, total;
     float *ring;
     f4 pa0, pa1;
     int tid, rd, wr;
+    unsigned lds0;   // LDS byte address of this wave's first piece in slot 0
     bool w0;
 
+    // NP (1 or 4) consecutive 1 KiB pieces, global `src` (this lane's 16 B) -> LDS byte address `dst` (wave-uniform; the hardware adds
+    // lane * 16 B, and the instruction offset moves both addresses).  M0 carries the LDS address; the compiler owns it, so it is
+    // written in the statement that reads it and restored.
+    template <int NP>
+    __device__ __forceinline__ static void dma(const float *src, unsigned dst) {
+        static_assert(NP == 1 || NP == 4, "one piece or four");
+        unsigned keep;
+        if constexpr (NP == 4)
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                         "global_load_lds_dwordx4 %1, off\n\t"
+                         "global_load_lds_dwordx4 %1, off offset:1024\n\t"
+                         "global_load_lds_dwordx4 %1, off offset:2048\n\t"
+                         "global_load_lds_dwordx4 %1, off offset:3072\n\t"
+                         "s_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+        else
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                         "global_load_lds_dwordx4 %1, off\n\t"
+                         "s_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+    }
     __device__ __forceinline__ void issue(int slot) {
-        float *dst = ring + slot * SLAB_FLOATS + (tid >> 6) * PPW * 256;   // wave-uniform; the hardware adds lane * 16 B
+        // this wave's first piece in the slot (wave-uniform; said so where hipcc cannot prove it of `slot`)
+        const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + slot * (SLAB_FLOATS * 4));
 #pragma unroll
-        for (int i = 0; i < PPW; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(g + i * 256),
-                                             (__attribute__((address_space(3))) void *)(dst + i * 256), 16, 0, 0);
-        if (w0)   // wave-uniform
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(g + SLAB_A_FLOATS),
-                                             (__attribute__((address_space(3))) void *)(ring + slot * SLAB_FLOATS + SLAB_A_FLOATS), 16, 0, 0);
+        for (int i = 0; i < PPW; i += 4) dma<4>(g + i * 256, dst + i * 1024);
+        if (w0) dma<1>(g + SLAB_A_FLOATS, dst + SLAB_A_FLOATS * 4);   // wave-uniform (wave 0: dst is the slot's first byte)
         g += SLAB_FLOATS;
         if (++src == total) {
             src = 0;
@@ -277,6 +325,8 @@ struct SlabPipeDma {
         ring = ring_;
         tid = tid_;
         w0 = __builtin_amdgcn_readfirstlane(tid_ >> 6) == 0;
+        lds0 = __builtin_amdgcn_readfirstlane(
+            (unsigned)(size_t)(__attribute__((address_space(3))) float *)ring_ + (unsigned)(tid_ >> 6) * (PPW * 1024));
         g = g0 = packed + (tid_ >> 6) * PPW * 256 + (tid_ & 63) * 4;   // (wave 0: the slab's first byte + the lane's 16)
         src = 0;
         total = total_slabs;
@@ -286,7 +336,7 @@ struct SlabPipeDma {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         rd = 0;
         wr = 3;
-        __syncthreads();
+        __syncthreads();   // (a bare s_barrier: hipcc knows of no pending operation)
         const f4 *np = reinterpret_cast<const f4 *>(ring) + (tid & 63);
         pa0 = np[0];
         pa1 = np[64];
@@ -295,10 +345,10 @@ struct SlabPipeDma {
     __device__ __forceinline__ const float *peek_next() const { return ring + ((rd + 1) & 3) * SLAB_FLOATS; }
     __device__ __forceinline__ void stage() { issue(wr); }
     __device__ __forceinline__ void advance() {
-        // everything but this wave's newest slab (PPW pieces, + 1 for wave 0) has landed: the slab issued one period ago is complete
+        // all but this wave's newest slab has landed (see above); never vmcnt(0), never __syncthreads() here
         if (w0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW + 1) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-        __syncthreads();
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         rd = (rd + 1) & 3;
         wr = (wr + 1) & 3;
     }
@@ -306,8 +356,7 @@ struct SlabPipeDma {
         stage();
         advance();
     }
-    // end of the kernel: the slabs issued ahead of the last one consumed are still landing in this workgroup's LDS (s_endpgm waits
-    // for a wave's outstanding memory operations by itself; said here so that it does not rest on that)
+    // end of the kernel: the slabs issued ahead of the last one consumed are still landing in this workgroup's LDS
     __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 };
 // the pipe of a kernel of WIDTH features on NT threads
