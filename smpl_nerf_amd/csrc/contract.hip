@@ -195,11 +195,9 @@ extern "C" int snerf_dy_contract_f32(const float *dy, int64_t n, int first_row, 
     auto run = [&](auto tiles_c, auto kb_c, int c0) -> int {
         constexpr int TILES = decltype(tiles_c)::value, KB = decltype(kb_c)::value;
         constexpr int lds = TILES * 16 * (KB * 16 + CT_PITCH_PAD) * (int)sizeof(float);
-        static LdsRaised raised;
-        if (int rc = raise_dynamic_lds(reinterpret_cast<const void *>(dy_contract_kernel<TILES, KB>), lds, raised, "dy_contract")) return rc;
         const int64_t per_cu = lds <= 72 * 1024 ? 2 : 1;
         const unsigned grid = (unsigned)(wgs < per_cu * n_cu ? wgs : per_cu * n_cu);
-        hipLaunchKernelGGL((dy_contract_kernel<TILES, KB>), dim3(grid), dim3(CT_WAVES * 64), lds, s, A, c0);
+        if (int rc = launch_lds<dy_contract_kernel<TILES, KB>>("dy_contract", dim3(grid), dim3(CT_WAVES * 64), lds, s, A, c0)) return rc;
         return check_launch("dy_contract");
     };
     auto run_kb = [&](auto tiles_c, int c0) -> int {

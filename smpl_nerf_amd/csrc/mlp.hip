@@ -62,7 +62,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     constexpr int NT = NWAVES * 64;
     constexpr int T = WIDTH / 16;   // tiles of the trunk
     constexpr int TD = WIDTH / 32;  // tiles of the directional branch
-    extern __shared__ __attribute__((aligned(16))) float ring[];  // RING4_BYTES (DMA pipe: SNERF_LAUNCH_RING4) or RING_BYTES (SNERF_LAUNCH_RING)
+    extern __shared__ __attribute__((aligned(16))) float ring[];  // Pipe::RING_BYTES (launch_fwd_nw)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -73,7 +73,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     // Persistent workgroups: one per CU (the 99 / 132 KiB ring allows no more), each walking the sample tiles blockIdx.x,
     // blockIdx.x + gridDim.x, ...  The weight ring keeps rolling from one tile into the next (the stream wraps around),
     // so only the first tile of a workgroup pays the pipeline fill and no CU idles between two workgroups.
-    using Pipe = std::conditional_t<(!TRAIN && WIDTH == 256 && NWAVES == 8), SlabPipeDma<NT>, PipeFor<WIDTH, NT>>;
+    using Pipe = FwdPipe<WIDTH, NWAVES, TRAIN>;
     Pipe pipe;
     // raw inputs of a tile (positions, direction), fetched while the previous tile's last layers run so that a tile
     // never starts by waiting on HBM (inference variant; the training variant sits at the register limit)
@@ -294,8 +294,6 @@ int launch_pack(const Plan &P, const float *params_flat, float *packed, hipStrea
     return check_launch(what);
 }
 
-constexpr int FWD_WAVES = 8;  // 128 samples per workgroup, one workgroup per CU (2 waves per SIMD)
-
 // FOLD pre-pass: out[(ray * slots + slot) * W + o] = sum_c W_l[o, additional column c] * add[ray][c], l = layer 0 and the
 // skip layers in order, read from the packed stream (A tile (kb, to) of a layer: lane m + 16 g, value r  <->
 // W[16 to + m][column of slot (kb, g, r)]).  One thread per (ray, slot, output feature); W = 16 * t_out of the trunk.
@@ -333,7 +331,6 @@ __global__ __launch_bounds__(256) void mlp_add_fold_kernel(Plan P, const float *
     out[e] = sum;
 }
 
-#define SNERF_LAUNCH_WIDE SNERF_LAUNCH_RING4
 template <int NW, bool ENCODED, bool TRAIN, bool FOLD = false>
 static int launch_fwd_nw(const Plan &P, const FwdArgs &A, hipStream_t s, int64_t n_limit = -1) {
     const int64_t tile = NW * 16;
@@ -344,32 +341,20 @@ static int launch_fwd_nw(const Plan &P, const FwdArgs &A, hipStream_t s, int64_t
     const int n_cu = device_cu_count("mlp_fwd");  // one persistent workgroup per CU
     if (n_cu < 1) return n_cu;
     // grid <= n_tiles, always: the inference kernels fetch the inputs of tile blockIdx.x unconditionally (mlp_fwd_body: load_raw)
-    const int64_t grid = (!TRAIN && B.n_tiles > n_cu) ? n_cu : B.n_tiles;
-    if constexpr (FOLD) {
-        if (P.width == 256) {
-            if constexpr (NW == 8) SNERF_LAUNCH_RING4((mlp_fwd_fold_kernel<256, NW>), dim3((unsigned)grid), dim3(NW * 64), s, B);
-            else SNERF_LAUNCH_RING((mlp_fwd_fold_kernel<256, NW>), dim3((unsigned)grid), dim3(NW * 64), s, B);
-        }
-        else if (P.width == 128) SNERF_LAUNCH_RING((mlp_fwd_fold_kernel<128, NW>), dim3((unsigned)grid), dim3(NW * 64), s, B);
-        else SNERF_LAUNCH_RING((mlp_fwd_fold_kernel<64, NW>), dim3((unsigned)grid), dim3(NW * 64), s, B);
-    } else {
-        if (P.width > 256) {   // one wave per SIMD (20 .. 32-tile chains need the whole register file): 4-wave workgroups only
-            if constexpr (NW == 4 && !FOLD) {
-                if (P.width == 320) SNERF_LAUNCH_WIDE((mlp_fwd_kernel<320, 4, ENCODED, TRAIN>), dim3((unsigned)grid), dim3(256), s, B);
-                else if (P.width == 384) SNERF_LAUNCH_WIDE((mlp_fwd_kernel<384, 4, ENCODED, TRAIN>), dim3((unsigned)grid), dim3(256), s, B);
-                else if (P.width == 448) SNERF_LAUNCH_WIDE((mlp_fwd_kernel<448, 4, ENCODED, TRAIN>), dim3((unsigned)grid), dim3(256), s, B);
-                else SNERF_LAUNCH_WIDE((mlp_fwd_kernel<512, 4, ENCODED, TRAIN>), dim3((unsigned)grid), dim3(256), s, B);
-            } else {
-                return fail(SNERF_E_BADARG, "mlp_fwd: widths above 256 run 4-wave workgroups");
-            }
-        } else if (P.width == 256) {
-            if constexpr (!TRAIN && NW == 8) SNERF_LAUNCH_RING4((mlp_fwd_kernel<256, NW, ENCODED, TRAIN>), dim3((unsigned)grid), dim3(NW * 64), s, B);
-            else SNERF_LAUNCH_RING((mlp_fwd_kernel<256, NW, ENCODED, TRAIN>), dim3((unsigned)grid), dim3(NW * 64), s, B);
-        }
-        else if (P.width == 128) SNERF_LAUNCH_RING((mlp_fwd_kernel<128, NW, ENCODED, TRAIN>), dim3((unsigned)grid), dim3(NW * 64), s, B);
-        else SNERF_LAUNCH_RING((mlp_fwd_kernel<64, NW, ENCODED, TRAIN>), dim3((unsigned)grid), dim3(NW * 64), s, B);
-    }
-    return check_launch("mlp_fwd");
+    const dim3 grid((unsigned)((!TRAIN && B.n_tiles > n_cu) ? n_cu : B.n_tiles)), block(NW * 64);
+    const int rc = with_mlp_width(P.width, [&](auto w) -> int {
+        constexpr int W = decltype(w)::value;
+        using Pipe = FwdPipe<W, NW, TRAIN>;   // (the pipe of the kernel body: mlp_fwd_body)
+        if constexpr (W > 256 && NW != 4)   // one wave per SIMD (20 .. 32-tile chains need the whole register file)
+            return fail(SNERF_E_BADARG, "mlp_fwd: widths above 256 run 4-wave workgroups");
+        else if constexpr (W > 256 && FOLD)   // (fold_table_bytes: no table above 256)
+            return fail(SNERF_E_BADARG, "mlp_fwd: the per-ray fold runs up to width 256");
+        else if constexpr (FOLD)
+            return launch_lds<mlp_fwd_fold_kernel<W, NW>>("mlp_fwd_fold_kernel", grid, block, Pipe::RING_BYTES, s, B);
+        else
+            return launch_lds<mlp_fwd_kernel<W, NW, ENCODED, TRAIN>>("mlp_fwd_kernel", grid, block, Pipe::RING_BYTES, s, B);
+    });
+    return rc ? rc : check_launch("mlp_fwd");
 }
 
 // slots (layers with an additional-input segment) and bytes of the per-ray fold table of a call, 0 when the fold does not apply
@@ -411,7 +396,7 @@ template <bool ENCODED, bool TRAIN>
 static int launch_fwd(const Plan &P, const FwdArgs &A, hipStream_t s) {
     // 8 waves (128 samples) per workgroup = one workgroup per CU, 2 waves per SIMD (two independent 4-wave workgroups per CU
     // measured 83.1 % against 85.7 % of the fp32 MFMA peak on the 128 x 128 frame, at twice the L2 -> LDS weight traffic: r02)
-    if (P.width > 256) return launch_fwd_nw<4, ENCODED, TRAIN>(P, A, s);   // (--netwidth above 256: mlp_plan.h make_plan)
+    if (P.width > 256) return launch_fwd_nw<4, ENCODED, TRAIN>(P, A, s);   // (--netwidth above 256: mlp_plan.h make_plan; tile_waves)
     if (!ENCODED && !TRAIN) {   // per-ray additional inputs + a workspace: the folded form (8-wave tiles)
         const int rc = launch_fwd_folded<FWD_WAVES>(P, A, s);
         if (rc != 1) return rc;
@@ -426,13 +411,22 @@ static int launch_fwd(const Plan &P, const FwdArgs &A, hipStream_t s) {
             return launch_fwd_lat<TRAIN>(P, A, s, c.n_main);
         }
     }
-    // Small calls (the README's 64-ray batches: 4096 + 12 288 samples): while 64-sample tiles still fit one round of the chip,
-    // the 4-wave form finishes in half the time of a 128-sample tile's pass through the weight stream - a call of up to
-    // 64 x CUs samples is one tile's latency, not throughput (same per-sample arithmetic: bit-identical results).
     const int n_cu = device_cu_count("mlp_fwd");
     if (n_cu < 1) return n_cu;
-    if (A.n <= (int64_t)64 * n_cu) return launch_fwd_nw<4, ENCODED, TRAIN>(P, A, s);
+    if (tile_waves(P.width, A.n, n_cu) == 4) return launch_fwd_nw<4, ENCODED, TRAIN>(P, A, s);   // (small calls, widths above 256)
     return launch_fwd_nw<FWD_WAVES, ENCODED, TRAIN>(P, A, s);
+}
+
+// the activation buffer of a training forward (mlp_plan.h TrainLayout)
+static void set_train_layout(FwdArgs &A, const TrainLayout &L) {
+    A.act_pe = L.pe;
+    A.act_add = L.add;
+    A.act_dpe = L.dpe;
+    A.act_x1 = L.x[1];
+    A.act_o = L.o;
+    A.act_h1 = L.h1;
+    A.act_h2 = L.h2;
+    A.act_mask = L.mask;
 }
 
 }  // namespace snerf
@@ -578,14 +572,7 @@ extern "C" int snerf_mlp_fwd_train_f32(const snerf_mlp_desc *desc, const float *
     A.spr = samples_per_ray;
     A.dirs_per_sample = dirs_per_sample ? 1 : 0;
     A.act = act;
-    A.act_pe = L.pe;
-    A.act_add = L.add;
-    A.act_dpe = L.dpe;
-    A.act_x1 = L.x[1];
-    A.act_o = L.o;
-    A.act_h1 = L.h1;
-    A.act_h2 = L.h2;
-    A.act_mask = L.mask;
+    set_train_layout(A, L);
     return launch_fwd<false, true>(P, A, (hipStream_t)stream);
 }
 
@@ -613,14 +600,7 @@ extern "C" int snerf_mlp_fwd_encoded_train_f32(const snerf_mlp_desc *desc, const
     A.n = n;
     A.spr = 1;
     A.act = act;
-    A.act_pe = L.pe;
-    A.act_add = L.add;
-    A.act_dpe = L.dpe;
-    A.act_x1 = L.x[1];
-    A.act_o = L.o;
-    A.act_h1 = L.h1;
-    A.act_h2 = L.h2;
-    A.act_mask = L.mask;
+    set_train_layout(A, L);
     return launch_fwd<true, true>(P, A, (hipStream_t)stream);
 }
 

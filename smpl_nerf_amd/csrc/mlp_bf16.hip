@@ -430,15 +430,11 @@ template <int NS, bool TRAIN, int FMT = FMT_BF16>
 static int launch_bf16(const FwdArgs &A, hipStream_t s) {
     constexpr int NW = 8;
     const int lds = 3 * slab16_bytes(NS);
-    static LdsRaised raised;   // per device
-    if (int rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_fwd_bf16_kernel<256, NW, NS, TRAIN, FMT>), lds, raised,
-                                   "mlp_fwd_bf16"))
-        return rc;
     const int n_cu = device_cu_count("mlp_fwd_bf16");  // one persistent workgroup per CU
     if (n_cu < 1) return n_cu;
     const int64_t grid = A.n_tiles > n_cu ? n_cu : A.n_tiles;
     if (grid > 0x7fffffffLL) return fail(SNERF_E_BADARG, "mlp_fwd_bf16: n too large");
-    hipLaunchKernelGGL((mlp_fwd_bf16_kernel<256, NW, NS, TRAIN, FMT>), dim3((unsigned)grid), dim3(NW * 64), lds, s, A);
+    if (int rc = launch_lds<mlp_fwd_bf16_kernel<256, NW, NS, TRAIN, FMT>>("mlp_fwd_bf16", dim3((unsigned)grid), dim3(NW * 64), lds, s, A)) return rc;
     return check_launch("mlp_fwd_bf16");
 }
 

@@ -85,14 +85,9 @@ struct FwdArgs {
     int64_t n_tiles;   // sample tiles (NWAVES x 16 samples)
 };
 
-#ifndef SNERF_EXP_NOSTORE
-#define SNERF_EXP_NOSTORE 0
-#endif
 // one tile (16 features of this lane's sample) <-> the tile-row-major activation buffer
 __device__ __forceinline__ void store_tile(float *buf, int row, int64_t n, int64_t sample, int g, f4 v) {
-#if SNERF_EXP_NOSTORE != 1   // (diagnostic build: the training forward without its activation stores - DESIGN 6)
     __builtin_nontemporal_store(v, reinterpret_cast<f4 *>(buf + ((int64_t)row * n + sample) * 16 + 4 * g));
-#endif
 }
 template <int N>
 __device__ __forceinline__ void store_tiles(float *buf, int row0, int64_t n, int64_t sample, int g, const f4 (&tiles)[N]) {
@@ -136,45 +131,20 @@ __device__ __forceinline__ void store_mask(float *buf, int mask_row, int idx, in
     if constexpr (N <= 16 && ROW_PER_MASK) {
         *reinterpret_cast<uint2 *>(mask_ptr4(buf, mask_row, idx, n, sample, g)) = uint2{w[0], w[1]};
     } else if constexpr (N <= 16) {
-#if SNERF_EXP_NOSTORE != 2   // (diagnostic build: without the sign-mask stores)
         *mask_ptr(buf, mask_row, idx, n, sample, g) = uint2{w[0], w[1]};
-#else
-        asm volatile("" ::"v"(w[0]), "v"(w[1]));
-#endif
     } else {   // 32 tiles: four words per lane, one mask per tile-row (TrainLayout::mask)
         *mask_ptr4(buf, mask_row, idx, n, sample, g) = uint4{w[0], w[1], w[2], w[3]};
     }
 }
 
-// The 3-slot ring (99 KiB) is dynamic LDS: a launch gets 64 KiB unless the limit is raised per kernel once.
-constexpr int RING_BYTES = 3 * SLAB_FLOATS * 4;
-#define SNERF_LAUNCH_RING(kernel, grid, block, stream, ...)                                                            \
-    do {                                                                                                               \
-        static ::snerf::LdsRaised snerf_lds_raised_; /* per device (snerf_common.h) */                                 \
-        if (int snerf_rc_ = ::snerf::raise_dynamic_lds(reinterpret_cast<const void *>(kernel), ::snerf::RING_BYTES,    \
-                                                       snerf_lds_raised_, #kernel))                                    \
-            return snerf_rc_;                                                                                          \
-        hipLaunchKernelGGL(kernel, grid, block, ::snerf::RING_BYTES, stream, __VA_ARGS__);                             \
-    } while (0)
-
-// ... the 4-slot ring of the LDS-DMA pipe (SlabPipeDma below: the widths above 256), 132 KiB
-constexpr int RING4_BYTES = 4 * SLAB_FLOATS * 4;
-#define SNERF_LAUNCH_RING4(kernel, grid, block, stream, ...)                                                           \
-    do {                                                                                                               \
-        static ::snerf::LdsRaised snerf_lds_raised_; /* per device (snerf_common.h) */                                 \
-        if (int snerf_rc_ = ::snerf::raise_dynamic_lds(reinterpret_cast<const void *>(kernel), ::snerf::RING4_BYTES,   \
-                                                       snerf_lds_raised_, #kernel))                                    \
-            return snerf_rc_;                                                                                          \
-        hipLaunchKernelGGL(kernel, grid, block, ::snerf::RING4_BYTES, stream, __VA_ARGS__);                            \
-    } while (0)
-// Which kernels take which pipe (r05 measurements, DESIGN_HISTORY.md; the A/B switches that selected them are gone - the patches
-// under tools/ab/ are the record): the widths above 256 (one wave per SIMD) and the 8-wave inference kernel of width 256 stream
-// their slabs global -> LDS by DMA into the 4-slot ring (SlabPipeDma, below); the training forward and the dgrad of the widths up
-// to 256 measured no gain from it and keep the register-staged 3-slot ring (SlabPipe).
+// The weight ring of a kernel is dynamic LDS, 99 or 132 KiB: a launch gets 64 KiB unless the limit is raised per kernel once
+// (snerf_common.h: launch_lds).  A kernel names its pipe through the traits behind the two pipes (FwdPipe / BwdPipe / WarpPipe), and
+// its launch takes the LDS size from the same type.
 
 // Streams the slab sequence global -> registers -> LDS ring (3 slots).
 template <int NT>
 struct SlabPipe {
+    static constexpr int RING_BYTES = 3 * SLAB_FLOATS * 4;   // 99 KiB
     static constexpr int NA = SLAB_A_FLOATS / 4 / NT;  // f4 per thread in the A region (NT=256: 4, 512: 2)
     const f4 *g;   // this thread's read cursor in the packed stream
     const f4 *g0;  // ... and its position at slab 0: persistent kernels run the stream once per sample tile and wrap
@@ -276,6 +246,7 @@ struct SlabPipe {
 //     tiles.  drain() waits for the slabs issued ahead of the last one consumed before the workgroup's LDS is given back.
 template <int NT>
 struct SlabPipeDma {
+    static constexpr int RING_BYTES = 4 * SLAB_FLOATS * 4;   // 132 KiB
     static constexpr int NW = NT / 64;
     static constexpr int PIECES = SLAB_A_FLOATS / 256;   // 1 KiB pieces of the A region (32); the aux block is one more (wave 0)
     static constexpr int PPW = PIECES / NW;
@@ -359,9 +330,21 @@ struct SlabPipeDma {
     // end of the kernel: the slabs issued ahead of the last one consumed are still landing in this workgroup's LDS
     __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 };
-// the pipe of a kernel of WIDTH features on NT threads
-template <int WIDTH, int NT>
-using PipeFor = std::conditional_t<(WIDTH > 256), SlabPipeDma<NT>, SlabPipe<NT>>;
+
+// Which kernel takes which pipe - stated here once, for the kernel bodies (the type of their `pipe`) and for their launches (the
+// dynamic LDS they ask for is Pipe::RING_BYTES of the same alias).  r05 measurements, DESIGN_HISTORY.md; the A/B switches that
+// selected the pipes are gone, the patches under tools/ab/ are the record.
+// Forward, training forward (TRAIN) and the per-ray fold kernel (TRAIN = false) - mlp.hip: the widths above 256 (one wave per SIMD)
+// and the 8-wave inference kernels of width 256 stream their slabs by DMA into the 4-slot ring; the others - the training forward
+// and the 4-wave tiles of small calls up to width 256 - measured no gain from it and keep the register-staged 3-slot ring.
+template <int WIDTH, int NWAVES, bool TRAIN>
+using FwdPipe = std::conditional_t<(WIDTH > 256 || (!TRAIN && WIDTH == 256 && NWAVES == 8)), SlabPipeDma<NWAVES * 64>, SlabPipe<NWAVES * 64>>;
+// dgrad (mlp_train.hip): DMA for the widths above 256 only
+template <int WIDTH, int NWAVES>
+using BwdPipe = std::conditional_t<(WIDTH > 256), SlabPipeDma<NWAVES * 64>, SlabPipe<NWAVES * 64>>;
+// the slab-streaming warp forward (warp.hip)
+template <int NWAVES>
+using WarpPipe = SlabPipe<NWAVES * 64>;
 
 // per-lane view of the sample this lane works for
 struct SampleCtx {
@@ -478,11 +461,12 @@ __device__ __forceinline__ void kblock(const float *a_kb, const float *a_next, f
     }
 }
 
-// Walks the k-blocks of one layer through the slab pipe.  A slab is released (staged slab written to LDS,
-// next global loads issued, workgroup barrier) as soon as its last k-block has been issued; the first A
-// pair of the following slab was read before that barrier - legal because slab p+1 has been resident and
-// visible since the barrier that ended slab p-1 (the ring holds p, p+1 and the slot being filled with p+2).
-template <int T_OUT, int NT, class PIPE = SlabPipe<NT>>
+// Walks the k-blocks of one layer through the slab pipe (either one: PIPE).  A slab is released (the next slab staged - SlabPipe: the
+// registers written to LDS and the next global loads issued; SlabPipeDma: the DMA pieces of slab p+3 issued -, workgroup barrier)
+// as soon as its last k-block has been issued; the first A pair of the following slab was read before that barrier - legal
+// because slab p+1 has been resident and visible since the barrier that ended slab p-1 (the 3-slot ring holds p, p+1 and the slot
+// being filled with p+2; the 4-slot ring p, p+1, p+2 landing and the slot of p+3).
+template <int T_OUT, int NT, class PIPE>
 struct LayerRun {
     static constexpr int KPS = SLAB_TILES / T_OUT;
     PIPE &pipe;

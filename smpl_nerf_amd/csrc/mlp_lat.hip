@@ -566,10 +566,8 @@ static int launch_fwd_lat_s(const Plan &P, const TrainLayout &L, const FwdArgs &
     const LatLds Lo = lat_lds_fwd(S, P);
     LatTable T;
     lat_table_fwd(P, L, Lo, T);
-    static LdsRaised raised;   // per device, per instantiation
-    if (int rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_fwd_lat_kernel<S, TRAIN>), Lo.total, raised, "mlp_fwd_lat")) return rc;
     const LatGeom G{Q.tile_off, Q.tile_end, Q.passes};
-    hipLaunchKernelGGL((mlp_fwd_lat_kernel<S, TRAIN>), dim3((unsigned)Q.grid), dim3(LAT_THREADS), Lo.total, s, T, A, G, Lo);
+    if (int rc = launch_lds<mlp_fwd_lat_kernel<S, TRAIN>>("mlp_fwd_lat", dim3((unsigned)Q.grid), dim3(LAT_THREADS), Lo.total, s, T, A, G, Lo)) return rc;
     return check_launch("mlp_fwd_lat");
 }
 
@@ -619,11 +617,11 @@ int launch_fwd_lat(const Plan &P, const FwdArgs &A, hipStream_t s, int64_t first
             const LatLds Lo = lat_lds_fwd(2, P);
             LatTable T;
             lat_table_fwd(P, L, Lo, T);
-            static LdsRaised raised;   // per device, per instantiation
-            if ((rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_fwd_lat_mixed_kernel<TRAIN>), Lo.total, raised, "mlp_fwd_lat"))) return rc;
             const int64_t split = Q[i].tile_off + 2 * (int64_t)Q[i].mixed_a;
             const LatGeom GA{Q[i].tile_off, split, 1}, GB{split, Q[i].tile_end, 1};
-            hipLaunchKernelGGL((mlp_fwd_lat_mixed_kernel<TRAIN>), dim3((unsigned)Q[i].grid), dim3(LAT_THREADS), Lo.total, s, T, A, GA, GB, Lo, Q[i].mixed_a);
+            if ((rc = launch_lds<mlp_fwd_lat_mixed_kernel<TRAIN>>("mlp_fwd_lat", dim3((unsigned)Q[i].grid), dim3(LAT_THREADS), Lo.total, s, T, A, GA, GB, Lo,
+                                                                  Q[i].mixed_a)))
+                return rc;
             if ((rc = check_launch("mlp_fwd_lat"))) return rc;
             continue;
         }
@@ -645,10 +643,8 @@ static int launch_bwd_lat_s(const Plan &P, const BwdPlan &B, const TrainLayout &
     const LatLds Lo = lat_lds(S, 0, 0, (P.n_hidden + 2) * 512);
     LatTable T;
     lat_table_bwd(P, B, L, Lo, T);
-    static LdsRaised raised;
-    if (int rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_bwd_lat_kernel<S, IG>), Lo.total, raised, "mlp_bwd_lat")) return rc;
     const LatGeom G{Q.tile_off, Q.tile_end, Q.passes};
-    hipLaunchKernelGGL((mlp_bwd_lat_kernel<S, IG>), dim3((unsigned)Q.grid), dim3(LAT_THREADS), Lo.total, s, T, A, G, Lo);
+    if (int rc = launch_lds<mlp_bwd_lat_kernel<S, IG>>("mlp_bwd_lat", dim3((unsigned)Q.grid), dim3(LAT_THREADS), Lo.total, s, T, A, G, Lo)) return rc;
     return check_launch("mlp_bwd_lat");
 }
 

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(NWAVES * 64) void mlp_bwd_kernel(BwdArgs A) {
     constexpr int NT = NWAVES * 64;
     constexpr int T = WIDTH / 16;
     constexpr int TD = WIDTH / 32;
-    extern __shared__ __attribute__((aligned(16))) float ring[];  // RING_BYTES (SNERF_LAUNCH_RING)
+    extern __shared__ __attribute__((aligned(16))) float ring[];  // Pipe::RING_BYTES (launch_bwd)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(NWAVES * 64) void mlp_bwd_kernel(BwdArgs A) {
         store_tile(A.dy, A.dy_sig, A.n, sample, g, g == 0 ? f4{dr[3], 0.f, 0.f, 0.f} : zero);
     }
 
-    using Pipe = PipeFor<WIDTH, NT>;
+    using Pipe = BwdPipe<WIDTH, NWAVES>;
     Pipe pipe;
     pipe.prologue(A.packed_t, ring, tid);
 
@@ -950,14 +950,12 @@ int launch_wgrad(const Plan &P, const TrainLayout &L, const float *act, const fl
     W.chunk = (((n + G - 1) / G) + 15) / 16 * 16;
     G = (int)((n + W.chunk - 1) / W.chunk);   // rounding the chunk up to whole k-steps may leave trailing chunks empty: not launched
     W.fold = fold;
-    static LdsRaised raised;   // per device
     int rc;
-    if ((rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_wgrad_kernel), WL_LDS_BYTES, raised, "wgrad"))) return rc;
     if (const int jobs = wgrad_jobs(P)) {
         if (wide_nsplit) {   // the wide jobs on the bf16 matrix cores (mlp_train_bf16.hip)
             if ((rc = launch_wgrad_wide_bf16(P, L, W, jobs, G, wide_nsplit, s))) return rc;
         } else {
-            hipLaunchKernelGGL(mlp_wgrad_kernel, dim3(jobs, G), dim3(WL_THREADS), WL_LDS_BYTES, s, P, L, W);
+            if ((rc = launch_lds<mlp_wgrad_kernel>("wgrad", dim3(jobs, G), dim3(WL_THREADS), WL_LDS_BYTES, s, P, L, W))) return rc;
             if ((rc = check_launch("wgrad"))) return rc;
         }
     }
@@ -1052,13 +1050,10 @@ int launch_bwd(const snerf_mlp_desc *desc, const float *packed_t, const float *a
     A.dir_id = desc->dir_identity ? 1 : 0;
     A.dir_nkb = P.dir_nkb;
     A.use_dir = desc->use_dir ? 1 : 0;
-    // 8 waves = 128 samples per workgroup, like the forward; calls of <= 64 x CUs samples (the README's 64-ray batches) run
-    // 4-wave workgroups on 64-sample tiles like the forward does (mlp.hip: launch_fwd): below one tile per CU the launch is
-    // the latency of one tile's pass through the weight stream, and a wave that has its SIMD's matrix pipe to itself
-    // passes in two thirds of the time (r04: 290 -> 190 us at 4096 samples)
+    // the waves of a sample tile as in the forward (snerf_common.h tile_waves: small calls and the widths above 256 run 4-wave workgroups)
     const int n_cu = device_cu_count("mlp_bwd");
     if (n_cu < 1) return n_cu;
-    const bool small = P.width > 256 || n <= (int64_t)64 * n_cu;
+    const bool small = tile_waves(P.width, n, n_cu) == 4;
     const bool wide_pe = input_grad && bwd_pe_tiles(P).pos == 8;
     // calls of a few 16-sample tiles per CU: the latency-class dgrad (mlp_lat.hip; bit-identical d Y); a call of a few rounds and a
     // fraction: whole rounds here, the fraction there
@@ -1070,39 +1065,20 @@ int launch_bwd(const snerf_mlp_desc *desc, const float *packed_t, const float *a
     const int64_t n_dgrad = lc.mode == 2 ? lc.n_main : n;   // samples of the throughput kernel below
     auto launch = [&](auto bw_c) -> int {
         constexpr int BW = decltype(bw_c)::value;
-        const int64_t grid = (n_dgrad + BW * 16 - 1) / (BW * 16);
-        if (grid > 0x7fffffffLL) return fail(SNERF_E_BADARG, "mlp_bwd: n too large");
-        if (P.width > 256) {   // one wave per SIMD, like the forward
-            if constexpr (BW == 4) {
-#define SNERF_LAUNCH_WIDE SNERF_LAUNCH_RING4
-#define SNERF_BWD_WIDE(W_)                                                                                                          \
-    do {                                                                                                                            \
-        if (wide_pe) SNERF_LAUNCH_WIDE((mlp_bwd_kernel<W_, 4, true, 8, 8>), dim3((unsigned)grid), dim3(256), s, A);                 \
-        else if (input_grad) SNERF_LAUNCH_WIDE((mlp_bwd_kernel<W_, 4, true>), dim3((unsigned)grid), dim3(256), s, A);               \
-        else SNERF_LAUNCH_WIDE((mlp_bwd_kernel<W_, 4, false>), dim3((unsigned)grid), dim3(256), s, A);                              \
-    } while (0)
-                if (P.width == 320) SNERF_BWD_WIDE(320);
-                else if (P.width == 384) SNERF_BWD_WIDE(384);
-                else if (P.width == 448) SNERF_BWD_WIDE(448);
-                else SNERF_BWD_WIDE(512);
-#undef SNERF_BWD_WIDE
-            } else {
+        const int64_t tiles = (n_dgrad + BW * 16 - 1) / (BW * 16);
+        if (tiles > 0x7fffffffLL) return fail(SNERF_E_BADARG, "mlp_bwd: n too large");
+        const dim3 grid((unsigned)tiles), block(BW * 64);
+        return with_mlp_width(P.width, [&](auto w) -> int {
+            constexpr int W = decltype(w)::value;
+            if constexpr (W > 256 && BW != 4) {   // one wave per SIMD, like the forward
                 return fail(SNERF_E_BADARG, "mlp_bwd: widths above 256 run 4-wave workgroups");
+            } else {
+                constexpr int lds = BwdPipe<W, BW>::RING_BYTES;   // (the pipe of the kernel body)
+                if (wide_pe) return launch_lds<mlp_bwd_kernel<W, BW, true, 8, 8>>("mlp_bwd_kernel", grid, block, lds, s, A);
+                if (input_grad) return launch_lds<mlp_bwd_kernel<W, BW, true>>("mlp_bwd_kernel", grid, block, lds, s, A);
+                return launch_lds<mlp_bwd_kernel<W, BW, false>>("mlp_bwd_kernel", grid, block, lds, s, A);
             }
-        } else if (P.width == 256) {
-            if (wide_pe) SNERF_LAUNCH_RING((mlp_bwd_kernel<256, BW, true, 8, 8>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-            else if (input_grad) SNERF_LAUNCH_RING((mlp_bwd_kernel<256, BW, true>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-            else SNERF_LAUNCH_RING((mlp_bwd_kernel<256, BW, false>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-        } else if (P.width == 128) {
-            if (wide_pe) SNERF_LAUNCH_RING((mlp_bwd_kernel<128, BW, true, 8, 8>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-            else if (input_grad) SNERF_LAUNCH_RING((mlp_bwd_kernel<128, BW, true>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-            else SNERF_LAUNCH_RING((mlp_bwd_kernel<128, BW, false>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-        } else {
-            if (wide_pe) SNERF_LAUNCH_RING((mlp_bwd_kernel<64, BW, true, 8, 8>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-            else if (input_grad) SNERF_LAUNCH_RING((mlp_bwd_kernel<64, BW, true>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-            else SNERF_LAUNCH_RING((mlp_bwd_kernel<64, BW, false>), dim3((unsigned)grid), dim3(BW * 64), s, A);
-        }
-        return SNERF_OK;
+        });
     };
     if (int lrc = small ? launch(std::integral_constant<int, 4>{}) : launch(std::integral_constant<int, 8>{})) return lrc;
     int rc = check_launch("mlp_bwd(dgrad)");

@@ -890,19 +890,12 @@ __global__ __launch_bounds__(WC_THREADS) void mlp_wgrad_f16_kernel(Plan P, Train
 }
 
 int launch_wgrad_wide_bf16(const Plan &P, const TrainLayout &L, const WgradArgs &W, int jobs, int G, int nsplit, hipStream_t s) {
-    static LdsRaised r2, r3, rc16;   // per device
+    const dim3 grid(jobs, G);
     int rc;
-    if (nsplit == SNERF_SPLIT_F16X3) {
-        if ((rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_wgrad_f16_kernel), WC_LDS_BYTES, rc16, "wgrad_f16"))) return rc;
-        hipLaunchKernelGGL(mlp_wgrad_f16_kernel, dim3(jobs, G), dim3(WC_THREADS), WC_LDS_BYTES, s, P, L, W);
-    } else if (nsplit == 3) {
-        if ((rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_wgrad_bf16_kernel<3>), WB_LDS_BYTES, r3, "wgrad_bf16"))) return rc;
-        hipLaunchKernelGGL(mlp_wgrad_bf16_kernel<3>, dim3(jobs, G), dim3(WB_THREADS), WB_LDS_BYTES, s, P, L, W);
-    } else {
-        if ((rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_wgrad_bf16_kernel<2>), WB_LDS_BYTES, r2, "wgrad_bf16"))) return rc;
-        hipLaunchKernelGGL(mlp_wgrad_bf16_kernel<2>, dim3(jobs, G), dim3(WB_THREADS), WB_LDS_BYTES, s, P, L, W);
-    }
-    return check_launch("wgrad_bf16");
+    if (nsplit == SNERF_SPLIT_F16X3) rc = launch_lds<mlp_wgrad_f16_kernel>("wgrad_f16", grid, dim3(WC_THREADS), WC_LDS_BYTES, s, P, L, W);
+    else if (nsplit == 3) rc = launch_lds<mlp_wgrad_bf16_kernel<3>>("wgrad_bf16", grid, dim3(WB_THREADS), WB_LDS_BYTES, s, P, L, W);
+    else rc = launch_lds<mlp_wgrad_bf16_kernel<2>>("wgrad_bf16", grid, dim3(WB_THREADS), WB_LDS_BYTES, s, P, L, W);
+    return rc ? rc : check_launch("wgrad_bf16");
 }
 
 static int plans_t(const snerf_mlp_desc *desc, Plan &P, const char *what) {
@@ -917,15 +910,11 @@ template <int NS, bool INPUT_GRAD, int FMT = FMT_BF16>
 static int launch_dgrad_bf16(const BwdArgs &A, hipStream_t s) {
     constexpr int NW = 8;
     const int lds = 3 * slab16_bytes(NS);
-    static LdsRaised raised;   // per device
-    if (int rc = raise_dynamic_lds(reinterpret_cast<const void *>(mlp_bwd_bf16_kernel<256, NW, NS, INPUT_GRAD, FMT>), lds, raised,
-                                   "mlp_bwd_bf16"))
-        return rc;
     const int n_cu = device_cu_count("mlp_bwd_bf16");  // one persistent workgroup per CU
     if (n_cu < 1) return n_cu;
     const int64_t grid = (!INPUT_GRAD && A.n_tiles > n_cu) ? n_cu : A.n_tiles;
     if (grid > 0x7fffffffLL) return fail(SNERF_E_BADARG, "mlp_bwd_bf16: n too large");
-    hipLaunchKernelGGL((mlp_bwd_bf16_kernel<256, NW, NS, INPUT_GRAD, FMT>), dim3((unsigned)grid), dim3(NW * 64), lds, s, A);
+    if (int rc = launch_lds<mlp_bwd_bf16_kernel<256, NW, NS, INPUT_GRAD, FMT>>("mlp_bwd_bf16", dim3((unsigned)grid), dim3(NW * 64), lds, s, A)) return rc;
     return check_launch("mlp_bwd_bf16(dgrad)");
 }
 

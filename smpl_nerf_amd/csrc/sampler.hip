@@ -459,12 +459,10 @@ extern "C" int snerf_sample_pdf_bins_bwd_f32(const float *bins, const float *wei
     if (B == 0) return SNERF_OK;
     if (!bins || !weights || !u || !inds || !d_z_samples || !d_bins || !d_weights) return fail(SNERF_E_BADARG, "sample_pdf_bins_bwd: null pointer");
     const size_t lds = (size_t)SP_WAVES * (sp_round4(2 * Nb) + 4 * sp_round4(Nf)) * sizeof(float);     // <= 4 * (2048 + 4096) * 4 = 96 KiB
-    static LdsRaised raised;
-    if (lds > 64 * 1024)
-        if (int rc = raise_dynamic_lds(reinterpret_cast<const void *>(sample_pdf_bwd_kernel), 128 * 1024, raised, "sample_pdf_bins_bwd")) return rc;
     const int64_t grid = (B + SP_WAVES - 1) / SP_WAVES;
     if (grid > 0x7fffffffLL) return fail(SNERF_E_BADARG, "sample_pdf_bins_bwd: B too large");
-    hipLaunchKernelGGL(sample_pdf_bwd_kernel, dim3((unsigned)grid), dim3(SP_THREADS), lds, (hipStream_t)stream, bins, weights, u, inds,
-                       tot, d_z_samples, B, Nb, Nf, d_bins, d_weights);
+    if (int rc = launch_lds_limit<sample_pdf_bwd_kernel>("sample_pdf_bins_bwd", dim3((unsigned)grid), dim3(SP_THREADS), (int)lds, lds > 64 * 1024 ? 128 * 1024 : 0,
+                                                         (hipStream_t)stream, bins, weights, u, inds, tot, d_z_samples, B, Nb, Nf, d_bins, d_weights))
+        return rc;
     return check_launch("sample_pdf_bins_bwd");
 }

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/smplnerf.h"
 
@@ -38,6 +39,48 @@ struct LdsRaised {
 };
 // raises the limit once per (kernel, device); idempotent, a race only repeats the driver call.  Returns 0 or SNERF_E_LAUNCH.
 int raise_dynamic_lds(const void *kernel, int bytes, LdsRaised &state, const char *what);
+// The launch of a kernel whose dynamic LDS may exceed the 64 KiB every launch gets: raises the limit of `Kernel` to `limit_bytes`
+// (once per device: the LdsRaised is a static of the instantiation, i.e. of the kernel; 0 = this launch needs no raise) and launches
+// with `lds_bytes`.  A kernel whose launches differ in size passes ONE constant limit, so that every raise of a kernel asks for the
+// same value and threads that race only repeat the driver call.  Returns SNERF_OK or the error of the raise (`what` names the
+// caller in its text); the launch itself is checked by the caller's check_launch(), which may stand behind several launches.
+template <auto Kernel, class... Args>
+int launch_lds_limit(const char *what, dim3 grid, dim3 block, int lds_bytes, int limit_bytes, hipStream_t s, const Args &...args) {
+    static LdsRaised raised;
+    if (limit_bytes > 0)
+        if (int rc = raise_dynamic_lds(reinterpret_cast<const void *>(Kernel), limit_bytes, raised, what)) return rc;
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+    return SNERF_OK;
+}
+// ... for a kernel whose launches all ask for the same size: the limit is that size
+template <auto Kernel, class... Args>
+int launch_lds(const char *what, dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args &...args) {
+    return launch_lds_limit<Kernel>(what, grid, block, lds_bytes, lds_bytes, s, args...);
+}
+
+// ---- host: which instantiation a call runs ----------------------------------------------------------------------------------------
+// f(std::integral_constant<int, W>{}) for the W of the list that is `width`
+template <int W0, int... Ws, class F>
+int with_width(int width, F &&f) {
+    if (width == W0) return f(std::integral_constant<int, W0>{});
+    if constexpr (sizeof...(Ws) > 0) return with_width<Ws...>(width, f);
+    else return fail(SNERF_E_BADARG, "no kernel of width %d", width);
+}
+// the kernel widths of a RenderRayNet plan (mlp_plan.h make_plan: P.width) and of a WarpFieldNet plan (make_warp_plan).  (The order
+// of a list is the order in which a translation unit emits its kernels: the one the hand-written ladders had.)
+template <class F>
+int with_mlp_width(int width, F &&f) { return with_width<320, 384, 448, 512, 256, 128, 64>(width, f); }
+template <class F>
+int with_warp_width(int width, F &&f) { return with_width<256, 128>(width, f); }
+
+// Waves per sample tile (16 samples per wave) of a forward or dgrad call of a net of kernel width `width` on the throughput
+// kernels.  8 waves = 128 samples per workgroup, one workgroup per CU, 2 waves per SIMD.  The widths above 256 run one wave per SIMD
+// (20 .. 32-tile chains need the whole register file).  Small calls (the README's 64-ray batches: 4096 + 12 288 samples): while
+// 64-sample tiles still fit one round of the chip the 4-wave form finishes in about half the time of a 128-sample tile's pass
+// through the weight stream - a call of up to 64 x CUs samples is one tile's latency, not throughput (same per-sample
+// arithmetic: bit-identical results; r04: dgrad 290 -> 190 us at 4096 samples).
+constexpr int FWD_WAVES = 8;
+inline int tile_waves(int width, int64_t n, int n_cu) { return (width > 256 || n <= (int64_t)64 * n_cu) ? 4 : FWD_WAVES; }
 
 // Tuning knobs: environment variables read ONCE, at the first call that consults them (INTEGRATION.md lists every knob of the
 // library and of the Python host).  r06: the A/B switches of rounds 2-5 whose experiments are decided are gone (their patches

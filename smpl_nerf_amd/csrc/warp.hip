@@ -39,7 +39,7 @@ template <int WIDTH, int NWAVES, bool TRAIN>
 __global__ __launch_bounds__(NWAVES * 64) void warp_fwd_kernel(WarpArgs A) {
     constexpr int NT = NWAVES * 64;
     constexpr int T = WIDTH / 16;
-    extern __shared__ __attribute__((aligned(16))) float ring[];  // RING_BYTES (SNERF_LAUNCH_RING)
+    extern __shared__ __attribute__((aligned(16))) float ring[];  // Pipe::RING_BYTES (launch_warp_fwd)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t sample = ((int64_t)blockIdx.x * NWAVES + wave) * 16 + (lane & 15);
     const bool valid = sample < A.n;
@@ -56,11 +56,12 @@ __global__ __launch_bounds__(NWAVES * 64) void warp_fwd_kernel(WarpArgs A) {
     }
     c.add = A.add_dim ? A.add + ray * A.add_dim : nullptr;
 
-    SlabPipe<NT> pipe;
+    using Pipe = WarpPipe<NWAVES>;
+    Pipe pipe;
     pipe.prologue(A.packed, ring, tid);
     f4 in[T], acc[T];
     {
-        LayerRun<T, NT> run(pipe, lane);
+        LayerRun<T, NT, Pipe> run(pipe, lane);
         run.init(acc);
         for (int kb = 0; kb < A.pos_nkb; ++kb) {
             const f4 b = pe_operand<false>(c, false, A.pos_L, A.pos_id, kb, 0);
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(NWAVES * 64) void warp_fwd_kernel(WarpArgs A) {
     }
     f4 w[1];
     {
-        LayerRun<1, NT> run(pipe, lane);
+        LayerRun<1, NT, Pipe> run(pipe, lane);
         run.init(w);
 #pragma unroll
         for (int kb = 0; kb < T; ++kb) run.step(in[kb], w);
@@ -488,34 +489,25 @@ static int snerf::launch_warp_fwd(const snerf_warp_desc *desc, const float *pack
                     A.ray_bias = ray_bias;
                 }
             }
-#define SNERF_WARP_RES(W_, RW_, TR_)                                                                                      \
-    do {                                                                                                                  \
-        static LdsRaised raised; /* per device */                                                                         \
-        if (int rc_ = raise_dynamic_lds(reinterpret_cast<const void *>(warp_fwd_resident_kernel<W_, RW_, TR_>), 160 * 1024, \
-                                        raised, "warp_fwd"))                                                              \
-            return rc_;                                                                                                   \
-        hipLaunchKernelGGL((warp_fwd_resident_kernel<W_, RW_, TR_>), dim3((unsigned)g), dim3(RW_ * 64), bytes, s, A);      \
-    } while (0)
-            if (P.width == 256) {
-                if (act) SNERF_WARP_RES(256, 8, true);
-                else SNERF_WARP_RES(256, 16, false);
-            } else {
-                if (act) SNERF_WARP_RES(128, 8, true);
-                else SNERF_WARP_RES(128, 16, false);
-            }
-#undef SNERF_WARP_RES
+            if (int rc = with_warp_width(P.width, [&](auto w) -> int {
+                    constexpr int W = decltype(w)::value;
+                    constexpr int limit = 160 * 1024;   // (what a CU has: one value for nets of every size)
+                    if (act) return launch_lds_limit<warp_fwd_resident_kernel<W, 8, true>>("warp_fwd", dim3((unsigned)g), dim3(8 * 64), bytes, limit, s, A);
+                    return launch_lds_limit<warp_fwd_resident_kernel<W, 16, false>>("warp_fwd", dim3((unsigned)g), dim3(16 * 64), bytes, limit, s, A);
+                }))
+                return rc;
             return check_launch("warp_fwd(resident)");
         }
     }
     constexpr int NW = 4;
     const int64_t grid = (n + NW * 16 - 1) / (NW * 16);
     if (grid > 0x7fffffffLL) return fail(SNERF_E_BADARG, "warp_fwd: n too large");
-    if (P.width == 256) {
-        if (act) SNERF_LAUNCH_RING((warp_fwd_kernel<256, NW, true>), dim3((unsigned)grid), dim3(NW * 64), s, A);
-        else SNERF_LAUNCH_RING((warp_fwd_kernel<256, NW, false>), dim3((unsigned)grid), dim3(NW * 64), s, A);
-    } else {
-        if (act) SNERF_LAUNCH_RING((warp_fwd_kernel<128, NW, true>), dim3((unsigned)grid), dim3(NW * 64), s, A);
-        else SNERF_LAUNCH_RING((warp_fwd_kernel<128, NW, false>), dim3((unsigned)grid), dim3(NW * 64), s, A);
-    }
+    if (int rc = with_warp_width(P.width, [&](auto w) -> int {
+            constexpr int W = decltype(w)::value;
+            const dim3 g((unsigned)grid), b(NW * 64);
+            if (act) return launch_lds<warp_fwd_kernel<W, NW, true>>("warp_fwd_kernel", g, b, WarpPipe<NW>::RING_BYTES, s, A);
+            return launch_lds<warp_fwd_kernel<W, NW, false>>("warp_fwd_kernel", g, b, WarpPipe<NW>::RING_BYTES, s, A);
+        }))
+        return rc;
     return check_launch("warp_fwd");
 }

@@ -140,13 +140,12 @@ extern "C" int snerf_warp_fwd_bf16_f32(const snerf_warp_desc *desc, const void *
     A.add_nkb = P.add_nkb;
     constexpr int NW = 8;
     const int lds = 3 * slab16_bytes(WNS);
-    static LdsRaised raised;   // per device
-    if ((rc = raise_dynamic_lds(reinterpret_cast<const void *>(warp_fwd_bf16_kernel<256, NW>), lds, raised, "warp_fwd_bf16"))) return rc;
     const int n_cu = device_cu_count("warp_fwd_bf16");
     if (n_cu < 1) return n_cu;
     const int64_t n_tiles = (n + NW * 16 - 1) / (NW * 16);
     const int64_t grid = n_tiles < n_cu ? n_tiles : n_cu;
-    hipLaunchKernelGGL((warp_fwd_bf16_kernel<256, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, (hipStream_t)stream, A,
-                       P.total_slabs, n_tiles);
+    if ((rc = launch_lds<warp_fwd_bf16_kernel<256, NW>>("warp_fwd_bf16", dim3((unsigned)grid), dim3(NW * 64), lds, (hipStream_t)stream, A, P.total_slabs,
+                                                        n_tiles)))
+        return rc;
     return check_launch("warp_fwd_bf16");
 }
