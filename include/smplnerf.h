@@ -417,6 +417,27 @@ SNERF_API int snerf_warp_bwd_f32(const snerf_warp_desc *desc, const float *packe
                        const float *d_warp, int64_t n, float *dy, float *gpart, float *flat_grad,
                        snerf_stream_t stream);
 
+/* ---- DynamicPipeline: the vertex-attention warp (models/dynamic_pipeline.py:53-74) --------------------------
+ * samples [B,S,3], goal / canon [B,V,3] (the body model's goal and canonical vertices), ray_o [B,3] ->
+ * warp [B*S,3] = sum_v a_v (canon_v - goal_v) with a = modified_softmax(temperature * relu(radius - |sample - goal_v|))
+ * over the V vertices (utils.py:57-60), warped [B*S,3] = sample + warp (:66), sdirs [B*S,3] = warped - ray_o (:70): the
+ * trio of snerf_warp_fwd_f32.  No [B,S,V] tensor exists: the softmax is taken with the per-sample maximum m removed.
+ * stats [B*S,2] = (m, Z = sum_v exp(x_v - m)) is what the backward reads; NULL when no backward follows.
+ * Any B >= 0 (0: no-op), S >= 1, V >= 1; radius > 0, temperature >= 0 (else SNERF_E_BADARG).  Two calls on the same
+ * inputs give the same bits. */
+SNERF_API int snerf_vertex_warp_fwd_f32(const float *samples, const float *goal, const float *canon, const float *ray_o,
+                              int64_t B, int S, int V, float radius, float temperature, float *warp, float *warped,
+                              float *sdirs, float *stats, snerf_stream_t stream);
+/* Its backward: warp and stats from the forward; d_warp / d_warped / d_sdirs [B*S,3] are the gradients arriving at the
+ * three outputs (each nullable, not all: their sum is d loss / d warp) -> d_goal, d_canon [B,V,3] and, unless NULL,
+ * d_samples [B,S,3] = the part of d loss / d samples that flows through the attention (warped's own identity term is
+ * the caller's).  Every element is written (zeros where nothing is in radius); no atomics: the same bits on every call.
+ * torch's conventions: relu' (0) = 0, no gradient through a zero distance. */
+SNERF_API int snerf_vertex_warp_bwd_f32(const float *samples, const float *goal, const float *canon, const float *warp,
+                              const float *stats, const float *d_warp, const float *d_warped, const float *d_sdirs,
+                              int64_t B, int S, int V, float radius, float temperature, float *d_samples, float *d_goal,
+                              float *d_canon, snerf_stream_t stream);
+
 /* ---- 8(f)-1: on-device ray generation + stratified coarse sampling --------------------------------------
  * Replaces get_rays (utils.py:50-54) + CoarseSampling (datasets/transforms.py:80-89) + ToTensor (:13-21) for a
  * batch of rays.  poses: fp64 [n_frames, 4, 4] camera-to-world; ray_index int64 [B] = frame*H*W + row*W + col;

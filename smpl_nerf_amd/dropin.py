@@ -10,7 +10,7 @@ What it does (INTEGRATION.md sections 1-2 as code):
   * rebinds, in every module of the reference that is (or later gets) imported, the names of the path's operators and
     plugin classes to their HIP-backed mirrors: utils.{raw2outputs, sample_pdf, fine_sampling, searchsorted},
     models.render_ray_net.RenderRayNet, models.warp_field_net.WarpFieldNet, models.append_vertices_net.AppendVerticesNet,
-    models.{nerf,smpl_nerf,append_vertices,append_smpl_params,append_to_nerf}_pipeline.* - including the copies that
+    models.{nerf,smpl_nerf,append_vertices,append_smpl_params,append_to_nerf,dynamic}_pipeline.* - including the copies that
     `from x import y` left in solver/*.py, train.py, inference.py.
   * wraps the reference's render entry point, inference.inference (inference.py:222-265), in torch.no_grad(): the reference
     calls `pipeline(data)` there in eval mode but WITH autograd recording (inference.py:247-253) - the graph is built and
@@ -44,6 +44,7 @@ REPLACEMENTS = {
     "models.append_vertices_pipeline": {"AppendVerticesPipeline": pipelines.AppendVerticesPipeline},
     "models.append_smpl_params_pipeline": {"AppendSmplParamsPipeline": pipelines.AppendSmplParamsPipeline},
     "models.append_to_nerf_pipeline": {"AppendToNerfPipeline": pipelines.AppendToNerfPipeline},
+    "models.dynamic_pipeline": {"DynamicPipeline": pipelines.DynamicPipeline},
 }
 _NAMES = {name: obj for table in REPLACEMENTS.values() for name, obj in table.items()}
 _originals = {}      # name -> the reference's own object (once seen), to recognise `from x import y` copies

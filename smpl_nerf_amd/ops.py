@@ -6,6 +6,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     raw2outputs         utils.py:134-191
     sample_pdf          utils.py:194-228
     fine_sampling       utils.py:231-264
+    vertex_attention_warp   models/dynamic_pipeline.py:51-70 (the attention warp of DynamicPipeline as one operator)
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -408,3 +409,84 @@ def fine_sampling(ray_translation: torch.Tensor, samples_directions: torch.Tenso
     r = hierarchical_samples(ray_translation.detach(), samples_directions.detach(), z_vals.detach(),
                              weights.detach(), args.number_fine_samples, strict=bool(getattr(args, "strict_cumsum", 0)))
     return r["z_fine"], r["pts"]
+
+
+# ------------------------------------------------------------------------------------------------
+# DynamicPipeline's vertex-attention warp (models/dynamic_pipeline.py:53-70)
+# ------------------------------------------------------------------------------------------------
+def _vertex_warp_launch(samples, goal, canon, ray_o, radius, temperature, want_stats):
+    B, S, _ = samples.shape
+    V = goal.shape[1]
+    dev = samples.device
+    warp, warped, sdirs = (torch.empty((B * S, 3), device=dev, dtype=torch.float32) for _ in range(3))
+    stats = torch.empty((B * S, 2), device=dev, dtype=torch.float32) if want_stats else None
+    lib = _lib.load()
+    with torch.cuda.device(dev), _lib.timed(f"vertex_warp_fwd[V={V}]"):
+        check(lib.snerf_vertex_warp_fwd_f32(ptr(samples), ptr(goal), ptr(canon), ptr(ray_o), B, S, V, radius, temperature,
+                                            ptr(warp), ptr(warped), ptr(sdirs), ptr(stats), current_stream()),
+              "snerf_vertex_warp_fwd_f32")
+    return warp, warped, sdirs, stats
+
+
+class _VertexWarpFn(torch.autograd.Function):
+    """snerf_vertex_warp_fwd_f32 / snerf_vertex_warp_bwd_f32 under autograd.  warped = samples + warp and sdirs = warped - o,
+    so the three incoming gradients add up to d loss / d warp; the samples also receive d warped + d sdirs directly and the
+    ray origins -sum_s d sdirs."""
+
+    @staticmethod
+    def forward(ctx, samples, goal, canon, ray_o, radius, temperature):
+        warp, warped, sdirs, stats = _vertex_warp_launch(samples, goal, canon, ray_o, radius, temperature, True)
+        ctx.save_for_backward(samples, goal, canon, warp, stats)
+        ctx.cfg = (radius, temperature)
+        ctx.set_materialize_grads(False)
+        return warp, warped, sdirs
+
+    @staticmethod
+    def backward(ctx, d_warp, d_warped, d_sdirs):
+        if d_warp is None and d_warped is None and d_sdirs is None:
+            return (None,) * 6
+        samples, goal, canon, warp, stats = ctx.saved_tensors
+        radius, temperature = ctx.cfg
+        B, S, _ = samples.shape
+        V = goal.shape[1]
+        d_warp, d_warped, d_sdirs = (None if g is None else g.contiguous().float() for g in (d_warp, d_warped, d_sdirs))
+        want_samples, want_o = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        d_samples = torch.empty_like(samples) if want_samples else None
+        d_goal, d_canon = torch.empty_like(goal), torch.empty_like(canon)
+        lib = _lib.load()
+        with torch.cuda.device(samples.device), _lib.timed(f"vertex_warp_bwd[V={V}]"):
+            check(lib.snerf_vertex_warp_bwd_f32(ptr(samples), ptr(goal), ptr(canon), ptr(warp), ptr(stats), ptr(d_warp),
+                                                ptr(d_warped), ptr(d_sdirs), B, S, V, radius, temperature, ptr(d_samples),
+                                                ptr(d_goal), ptr(d_canon), current_stream()), "snerf_vertex_warp_bwd_f32")
+        d_o = None
+        for g in (d_warped, d_sdirs):          # the identity paths around the attention
+            if g is not None and want_samples:
+                d_samples = d_samples + g.view(B, S, 3)
+        if want_o and d_sdirs is not None:
+            d_o = -d_sdirs.view(B, S, 3).sum(1)
+        return d_samples, d_goal, d_canon, d_o, None, None
+
+
+def vertex_attention_warp(ray_samples, goal_vertices, canonical_vertices, ray_translation, radius, temperature):
+    """models/dynamic_pipeline.py:51-70 in one launch: every sample of ray b moves by the attention-weighted sum of
+    canonical - goal over the vertices of body b within `radius` (modified_softmax of temperature * relu(radius - distance),
+    utils.py:57-60).  ray_samples [B,S,3], goal_vertices / canonical_vertices [B,V,3], ray_translation [B,3] ->
+    (warp, warped, sdirs), each [B*S, 3] like WarpFieldNet.forward_fused.  Differentiable with respect to both vertex
+    tensors and, where they require grad, the samples and the ray origins; with autograd off the call keeps nothing for a
+    backward.  No [B,S,V] tensor is built."""
+    for nm, t in (("ray_samples", ray_samples), ("goal_vertices", goal_vertices), ("canonical_vertices", canonical_vertices),
+                  ("ray_translation", ray_translation)):
+        _need_cuda(nm, t)
+    if ray_samples.dim() != 3 or ray_samples.shape[-1] != 3:
+        raise RuntimeError(f"vertex_attention_warp: ray_samples must be [B, S, 3], got {tuple(ray_samples.shape)}")
+    B, S = ray_samples.shape[:2]
+    if goal_vertices.dim() != 3 or goal_vertices.shape[0] != B or goal_vertices.shape[-1] != 3 or \
+            canonical_vertices.shape != goal_vertices.shape or tuple(ray_translation.shape) != (B, 3):
+        raise RuntimeError(f"vertex_attention_warp: goal {tuple(goal_vertices.shape)}, canonical {tuple(canonical_vertices.shape)} "
+                           f"and ray_translation {tuple(ray_translation.shape)} do not match ray_samples [B={B}, S={S}, 3]")
+    if S < 1 or goal_vertices.shape[1] < 1:
+        raise RuntimeError("vertex_attention_warp: needs at least one sample per ray and one vertex")
+    x, g, c, o = (t.contiguous() for t in (ray_samples, goal_vertices, canonical_vertices, ray_translation))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, g, c, o)):
+        return _VertexWarpFn.apply(x, g, c, o, float(radius), float(temperature))
+    return _vertex_warp_launch(x, g, c, o, float(radius), float(temperature), False)[:3]

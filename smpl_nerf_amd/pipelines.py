@@ -69,6 +69,8 @@ class PipelineArgs:
         self.number_fine_samples = 128
         self.human_pose_encoding = 1
         self.strict_cumsum = 0
+        self.warp_radius = 0.01          # config_parser.py:47-49: DynamicPipeline's attention radius and temperature
+        self.warp_temperature = 10000
         self.u = None  # optional explicit linspace(0, 1, number_fine_samples) buffer (ops.uniform_u)
         self.__dict__.update(kw)
 
@@ -372,6 +374,49 @@ class AppendVerticesPipeline(NerfPipeline):
         rgb_fine, _, densities_fine = ops.composite(raw_f.view(B, N, 4), z_fine, ray_direction, wb,
                                                     self._noise((B, N), dev), want_weights=False)  # :92
         return rgb, rgb_fine, ray_samples_fine, densities_fine                                    # :94
+
+
+class DynamicPipeline(NerfPipeline):
+    """models/dynamic_pipeline.py:10-83 drop-in: the warp comes from the body model itself.  data = [ray_samples,
+    ray_translation, ray_direction, z_vals, images (estimator input), rgb_truth]; `smpl_estimator(images)` returns (goal_poses,
+    betas) and `smpl_model(betas=, return_verts=True, body_pose=, global_orient=)` an object with `.vertices [B, V, 3]` - the
+    contract of AppendVerticesPipeline.  The body is posed twice, in the goal pose and in the zero ("canonical") pose (:45-50),
+    and every sample moves by the attention-weighted canonical - goal of the goal vertices within args.warp_radius
+    (ops.vertex_attention_warp: :51-70 in one launch, no [B, S, V] tensor).  Then the coarse net on the warped samples with
+    per-sample view directions and the compositing that scales distances by |x' - o| (:81) - coarse only, whatever
+    args.run_fine says (:83).  Returns (rgb, rgb, warp [B,S,3], ray_samples, warped [B,S,3], densities).  The loss reaches the
+    estimator's poses through the warp (solver/dynamic_solver.py): both kernels are differentiable."""
+
+    def __init__(self, model_coarse, model_fine, smpl_estimator, smpl_model, args, position_encoder, direction_encoder):
+        super().__init__(model_coarse, model_fine, args, position_encoder, direction_encoder)
+        self.smpl_estimator = smpl_estimator
+        self.smpl_model = smpl_model
+
+    def _single_call_ok(self, data) -> bool:
+        return False      # (estimator and body model are torch modules in front of the warp: no single-call entry)
+
+    def render_rays(self, data):
+        with torch.no_grad():
+            return self._forward_calls(data)
+
+    def _forward_calls(self, data):
+        ray_samples, ray_translation, ray_direction, z_vals, images, _ = data
+        args = self.args
+        B, Nc = z_vals.shape
+        dev = ray_samples.device
+        goal_poses, betas = self.smpl_estimator(images)                                            # :36
+        global_orient = torch.zeros([1, 3], device=dev).expand(B, -1)                              # :18, :42
+        canonical_pose = torch.zeros([1, 69], device=dev).expand(B, -1)                            # :19, :43
+        canonical = self.smpl_model(betas=betas, return_verts=True, body_pose=canonical_pose,
+                                    global_orient=global_orient).vertices                          # :45-47
+        goal = self.smpl_model(betas=betas, return_verts=True, body_pose=goal_poses,
+                               global_orient=global_orient).vertices                               # :48-50
+        warp, warped, sdirs = ops.vertex_attention_warp(ray_samples, goal, canonical.expand_as(goal), ray_translation,
+                                                        args.warp_radius, args.warp_temperature)   # :51-70
+        raw = self.model_coarse.forward_fused(warped, sdirs, Nc, self.position_encoder, self.direction_encoder)   # :68-78
+        rgb, _, densities = ops.composite(raw.view(B, Nc, 4), z_vals, sdirs.view(B, Nc, 3), bool(args.white_background),
+                                          self._noise((B, Nc), dev), want_weights=False)           # :81
+        return rgb, rgb, warp.view(B, Nc, 3), ray_samples, warped.view(B, Nc, 3), densities        # :83
 
 
 class AppendSmplParamsPipeline(NerfPipeline):

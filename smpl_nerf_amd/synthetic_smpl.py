@@ -28,12 +28,15 @@ class LinearBodyModel(torch.nn.Module):
 
 
 class IndexPoseEstimator(torch.nn.Module):
-    """models/dummy_smpl_estimator_model.py:21-27: x are indices into preset goal poses; betas are shared."""
+    """models/dummy_smpl_estimator_model.py:21-27: x are indices into preset goal poses; betas are shared.
+    trainable_poses = True makes goal_poses a trained parameter (the reference's dummy estimator for the dynamic
+    pipelines, solver/dynamic_solver.py: the loss reaches the poses through the warp)."""
 
-    def __init__(self, goal_poses, betas):
+    def __init__(self, goal_poses, betas, trainable_poses: bool = False):
         super().__init__()
         self.betas = torch.nn.Parameter(betas.data, requires_grad=False)
-        self.goal_poses = torch.nn.Parameter(goal_poses.data, requires_grad=False)
+        self.goal_poses = torch.nn.Parameter(goal_poses.data.clone() if trainable_poses else goal_poses.data,
+                                             requires_grad=bool(trainable_poses))
 
     def forward(self, x):
         return self.goal_poses[x], self.betas.expand(len(x), -1)
