@@ -438,6 +438,18 @@ SNERF_API int snerf_vertex_warp_bwd_f32(const float *samples, const float *goal,
                               int64_t B, int S, int V, float radius, float temperature, float *d_samples, float *d_goal,
                               float *d_canon, snerf_stream_t stream);
 
+/* ---- SmplNerfSolver's canonical-density loss: pdf of a Gaussian mixture (utils.py:72-111, solver/smpl_nerf_solver.py:39-41) ----
+ * samples [n,3] (any leading shape, flattened), means [V,3] (one isotropic Gaussian of standard deviation std per canonical body
+ * vertex, equal weights) ->
+ *   pdf[i]    = factor / V * sum_v exp(-|x_i - mu_v|^2 / (2 std^2)),   factor = 1 / sqrt((2 pi)^3 std^6)   (utils.py:84-110)
+ *   dpdf[i,:] = d pdf[i] / d x_i = -factor / (V std^2) * sum_v exp(...) (x_i - mu_v)       [n,3]; NULL: not computed (inference)
+ * One pass over the n*V pairs, one hardware exp per pair, nothing of size n*V in memory; no atomics, fixed summation order: two
+ * calls give the same bits.  Every element of pdf (and dpdf) is written; a pdf that underflows is 0, not NaN.
+ * n >= 0 (0: SNERF_OK whatever the pointers are), V >= 1, std > 0 (NaN refused), V*3 and ceil(n/64) below 2^31; samples, means and
+ * pdf non-null - else SNERF_E_BADARG before anything touches a device; a bad scalar is an error whatever n is. */
+SNERF_API int snerf_gmm_pdf_f32(const float *samples, const float *means, int64_t n, int V, float std, float *pdf, float *dpdf,
+                              snerf_stream_t stream);
+
 /* ---- 8(f)-1: on-device ray generation + stratified coarse sampling --------------------------------------
  * Replaces get_rays (utils.py:50-54) + CoarseSampling (datasets/transforms.py:80-89) + ToTensor (:13-21) for a
  * batch of rays.  poses: fp64 [n_frames, 4, 4] camera-to-world; ray_index int64 [B] = frame*H*W + row*W + col;

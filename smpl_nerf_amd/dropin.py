@@ -8,7 +8,7 @@ What it does (INTEGRATION.md sections 1-2 as code):
   * registers a `torchsearchsorted` package whose `searchsorted` is ops.searchsorted (the reference imports it at
     utils.py:14 and calls it at utils.py:212);
   * rebinds, in every module of the reference that is (or later gets) imported, the names of the path's operators and
-    plugin classes to their HIP-backed mirrors: utils.{raw2outputs, sample_pdf, fine_sampling, searchsorted},
+    plugin classes to their HIP-backed mirrors: utils.{raw2outputs, sample_pdf, fine_sampling, searchsorted, GaussianMixture},
     models.render_ray_net.RenderRayNet, models.warp_field_net.WarpFieldNet, models.append_vertices_net.AppendVerticesNet,
     models.{nerf,smpl_nerf,append_vertices,append_smpl_params,append_to_nerf,dynamic}_pipeline.* - including the copies that
     `from x import y` left in solver/*.py, train.py, inference.py.
@@ -35,7 +35,7 @@ from . import nets, ops, pipelines
 # reference module -> {attribute: replacement}
 REPLACEMENTS = {
     "utils": {"raw2outputs": ops.raw2outputs, "sample_pdf": ops.sample_pdf, "fine_sampling": ops.fine_sampling,
-              "searchsorted": ops.searchsorted},
+              "searchsorted": ops.searchsorted, "GaussianMixture": ops.GaussianMixture},
     "models.render_ray_net": {"RenderRayNet": nets.RenderRayNet},
     "models.warp_field_net": {"WarpFieldNet": nets.WarpFieldNet},
     "models.append_vertices_net": {"AppendVerticesNet": nets.AppendVerticesNet},

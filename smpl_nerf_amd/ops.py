@@ -7,6 +7,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     sample_pdf          utils.py:194-228
     fine_sampling       utils.py:231-264
     vertex_attention_warp   models/dynamic_pipeline.py:51-70 (the attention warp of DynamicPipeline as one operator)
+    GaussianMixture / gaussian_mixture_pdf   utils.py:72-111 (the canonical-density term of SmplNerfSolver's loss)
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -490,3 +491,80 @@ def vertex_attention_warp(ray_samples, goal_vertices, canonical_vertices, ray_tr
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, g, c, o)):
         return _VertexWarpFn.apply(x, g, c, o, float(radius), float(temperature))
     return _vertex_warp_launch(x, g, c, o, float(radius), float(temperature), False)[:3]
+
+
+# ------------------------------------------------------------------------------------------------
+# GaussianMixture.pdf (utils.py:72-111): the canonical-density term of SmplNerfSolver's loss
+# ------------------------------------------------------------------------------------------------
+def _gmm_launch(samples, means, std, want_grad):
+    n, V, dev = samples.numel() // 3, means.shape[0], samples.device
+    pdf = torch.empty(samples.shape[:-1], device=dev, dtype=torch.float32)
+    dpdf = torch.empty(samples.shape, device=dev, dtype=torch.float32) if want_grad else None
+    lib = _lib.load()
+    with torch.cuda.device(dev), _lib.timed(f"gmm_pdf[V={V}]"):
+        check(lib.snerf_gmm_pdf_f32(ptr(samples), ptr(means), n, V, std, ptr(pdf), ptr(dpdf), current_stream()), "snerf_gmm_pdf_f32")
+    return pdf, dpdf
+
+
+class _GmmPdfFn(torch.autograd.Function):
+    """snerf_gmm_pdf_f32 under autograd: the forward also writes dpdf = d pdf / d samples (it is asked for only when this Function
+    runs, i.e. when the samples want a gradient), so the backward is a product per sample and no second pass over the pairs."""
+
+    @staticmethod
+    def forward(ctx, samples, means, std):
+        pdf, dpdf = _gmm_launch(samples, means, std, True)
+        ctx.save_for_backward(dpdf)
+        return pdf
+
+    @staticmethod
+    def backward(ctx, d_pdf):
+        dpdf, = ctx.saved_tensors
+        return d_pdf[..., None] * dpdf, None, None
+
+
+def gaussian_mixture_pdf(samples, means, std):
+    """utils.py:102-111 in one launch: the density of samples [..., 3] under the equal-weight mixture of V isotropic Gaussians
+    with centres means [V, 3] and standard deviation std -> [...].  Differentiable with respect to the samples; the means are
+    constants (as in the reference) and must not require a gradient.  Under no_grad, or when the samples do not require a
+    gradient, the derivative is neither allocated nor computed.  No [..., V, 3] tensor is built."""
+    _need_cuda("samples", samples)
+    _need_cuda("means", means)
+    if means.dim() != 2 or means.shape[-1] != 3 or means.shape[0] < 1:
+        raise RuntimeError(f"gaussian_mixture_pdf: means must be [V >= 1, 3], got {tuple(means.shape)}")
+    if samples.dim() < 1 or samples.shape[-1] != 3:
+        raise RuntimeError(f"gaussian_mixture_pdf: samples must be [..., 3], got {tuple(samples.shape)}")
+    if means.requires_grad:
+        raise RuntimeError("gaussian_mixture_pdf: the means are constants (utils.py:83); `means` must not require a gradient")
+    if means.device != samples.device:
+        raise RuntimeError(f"gaussian_mixture_pdf: samples on {samples.device}, means on {means.device}")
+    x, mu = samples.contiguous(), means.contiguous()
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _GmmPdfFn.apply(x, mu, float(std))
+    return _gmm_launch(x.detach(), mu, float(std), False)[0]
+
+
+class GaussianMixture:
+    """utils.GaussianMixture (utils.py:72-111): the reference's constructor `(means: np.ndarray [V, 3], std, device)` and its
+    attributes `means` (tensor on `device`), `var = std ** 2` and `factor` (computed as in utils.py:85-86); `pdf(samples)` is
+    gaussian_mixture_pdf = snerf_gmm_pdf_f32.  The kernels are fp32: a float64 `means` array (what the reference's SMPL loader
+    hands over) is stored as fp32, where the reference keeps its dtype and then fails on fp32 samples or promotes them.  A
+    tensor is accepted as well as an array."""
+
+    def __init__(self, means, std, device):
+        import numpy as np
+        if isinstance(means, torch.Tensor):
+            means = means.detach().cpu().numpy()
+        means = np.asarray(means)
+        self.means = torch.from_numpy(np.ascontiguousarray(means, dtype=np.float32)).to(device)
+        self._std = float(std)
+        self.var = std ** 2
+        cov_det = self.var ** means.shape[-1]
+        self.factor = 1 / np.sqrt(((2 * np.pi) ** means.shape[-1] * cov_det))
+
+    def pdf(self, samples):
+        if samples.shape[-1] != self.means.shape[-1]:
+            raise ValueError("Dimension of samples is ", samples.shape[-1], " while dimension of gaussians is ",
+                             self.means.shape[-1])
+        if self.means.shape[-1] != 3:
+            raise ValueError(f"GaussianMixture.pdf: the kernel is written for 3-dimensional Gaussians, got {self.means.shape[-1]}")
+        return gaussian_mixture_pdf(samples, self.means, self._std)

@@ -324,6 +324,15 @@ class DataParallelTrainer:
     def loss(self, rgb, rgb_fine, rgb_truth):
         return self.loss_func(rgb, rgb_truth) + self.loss_func(rgb_fine, rgb_truth)  # nerf_solver.py:48-52
 
+    def batch_loss(self, out, batch):
+        """The loss of one batch from the pipeline's WHOLE output tuple and the batch: what step() (autograd path) and validate()
+        call.  Here: loss() of the two colours.  A subclass whose loss reads further outputs overrides this AND _default_batch_loss()."""
+        return self.loss(out[0], out[1], batch[-1])
+
+    def _default_batch_loss(self):
+        """True while batch_loss() is loss() of the two colours - what the one-call step computes inside the library."""
+        return type(self).batch_loss is DataParallelTrainer.batch_loss
+
     def _arm_grad_sinks(self):
         if self._flat_g is None:
             return
@@ -383,7 +392,8 @@ class DataParallelTrainer:
         default MSE loss, the library's optimiser, every parameter trainable."""
         # what the decision below depends on and a caller can change between steps (ADVICE r04: a later requires_grad_(False) or a
         # swapped loss_func used to be ignored): decided again when it changes
-        sig = (tuple(p.requires_grad for p in self.params), type(self.loss_func), getattr(self.loss_func, "reduction", None), self.one_call)
+        sig = (tuple(p.requires_grad for p in self.params), type(self.loss_func), getattr(self.loss_func, "reduction", None), self.one_call,
+               self._default_batch_loss())
         if getattr(self, "_oc_sig", None) != sig:
             self._oc, self._oc_sig = None, sig
         if self._oc is not None:
@@ -428,7 +438,7 @@ class DataParallelTrainer:
             mine.append(mw)
         if len(self.models) != len(mine) or {id(m) for m in self.models} != {id(m) for m in mine}:
             return None
-        if type(self).loss is not DataParallelTrainer.loss or type(self.loss_func) is not torch.nn.MSELoss or \
+        if type(self).loss is not DataParallelTrainer.loss or not self._default_batch_loss() or type(self.loss_func) is not torch.nn.MSELoss or \
                 self.loss_func.reduction != "mean":
             return None
         if (not (posed or verts) and (mc.additional_input_dim or mf.additional_input_dim)) or \
@@ -737,7 +747,7 @@ class DataParallelTrainer:
         self.optim.zero_grad(set_to_none=True)
         self._arm_grad_sinks()
         out = self.pipeline(batch)
-        loss = self.loss(out[0], out[1], batch[-1])
+        loss = self.batch_loss(out, batch)
         loss.backward()
         self.sync_gradients()
         self.optim.step()
@@ -759,7 +769,7 @@ class DataParallelTrainer:
         total, count, renders, truths = 0.0, 0, [], []
         for data in val_loader:
             out = self.pipeline(data)
-            total += float(self.loss(out[0], out[1], data[-1]))
+            total += float(self.batch_loss(out, data))
             count += 1
             renders.append(out[1].detach())
             truths.append(data[-1].detach())
@@ -826,6 +836,41 @@ class DataParallelTrainer:
             if save_dir:
                 self.save_checkpoint(save_dir, model_names, epoch + 1, hist)
         return hist
+
+
+class SmplNerfTrainer(DataParallelTrainer):
+    """SmplNerfSolver's loss (solver/smpl_nerf_solver.py:35-43) on the trainer: the two colour losses plus, with
+    `args.use_gmm_loss` and not `args.restrict_gmm_loss`, the canonical-density term
+
+        loss_func( canonical_mixture.pdf(warped_samples), densities )          # out[4], out[5] of SmplNerfPipeline
+
+    canonical_mixture = ops.GaussianMixture(canonical_smpl, gmm_std) (:23; one Gaussian per canonical body vertex,
+    snerf_gmm_pdf_f32).  Both switches are read from pipeline.args at every step; a missing one counts as 0 (the reference's
+    parser defines no restrict_gmm_loss, so its own --use_gmm_loss 1 raises AttributeError: DESIGN section 8b).  With the term off
+    this IS DataParallelTrainer - the same one-call step, bit for bit; with it on the step runs the autograd path: the term's
+    gradient reaches the nets through the compositing's alpha input and the warp net through warped_samples."""
+
+    def __init__(self, pipeline, models, canonical_smpl, gmm_std: float = 0.07, **kw):
+        super().__init__(pipeline, models, **kw)
+        dev = self.params[0].device if self.params else torch.device("cpu")
+        self.canonical_mixture = ops.GaussianMixture(canonical_smpl, gmm_std, dev)
+        self.last_terms = None     # (colour losses, mixture term or None) of the last batch_loss()
+
+    def gmm_term_on(self) -> bool:
+        args = self.pipeline.args
+        return bool(getattr(args, "use_gmm_loss", 0)) and not bool(getattr(args, "restrict_gmm_loss", 0))      # :39
+
+    def _default_batch_loss(self):
+        return not self.gmm_term_on()
+
+    def batch_loss(self, out, batch):
+        loss = self.loss(out[0], out[1], batch[-1])
+        if not self.gmm_term_on():
+            self.last_terms = (loss.detach(), None)
+            return loss
+        term = self.loss_func(self.canonical_mixture.pdf(out[4]), out[5])                                        # :40
+        self.last_terms = (loss.detach(), term.detach())
+        return loss + term                                                                                       # :41
 
 
 class RayBatchLoader:
