@@ -450,6 +450,49 @@ SNERF_API int snerf_vertex_warp_bwd_f32(const float *samples, const float *goal,
 SNERF_API int snerf_gmm_pdf_f32(const float *samples, const float *means, int64_t n, int V, float std, float *pdf, float *dpdf,
                               snerf_stream_t stream);
 
+/* ---- The SMPL body model: linear blend skinning (Loper et al. 2015) with smplx's conventions --------------------------------
+ * What DynamicPipeline and AppendVerticesPipeline call as smpl_model(betas=, body_pose=, global_orient=).vertices, one pose per
+ * ray.  B poses, V vertices, J joints, NB shape coefficients, P = 9 (J - 1), K = NB + P:
+ *   1  full_pose = [global_orient (3) | body_pose (3 (J - 1))]: J axis-angle vectors r_j
+ *   2  angle = |r + 1e-8| (1e-8 added to each component), dir = r / angle, R = I + sin(angle) K + (1 - cos(angle)) K^2, K = skew(dir)
+ *   3  pose_feature = R[1:] - I, flattened (joint, row, column): P values
+ *   4  v_shaped = v_template + shapedirs betas        5  J_rest = J_regressor v_shaped        6  v_posed = v_shaped + posedirs pose_feature
+ *   7  G_0 = [R_0 | J_0], G_j = G_parent [R_j | J_j - J_parent], A_j = [G_j.R | G_j.t - G_j.R J_j]
+ *   8  T_v = sum_j W[v,j] A_j        9  vertex_v = T_v [v_posed_v; 1]        10  joints_j = G_j.t
+ * The model record: device arrays laid out once at load, and the parent table on the HOST (it is validated before anything is
+ * launched and travels in the kernel arguments).
+ *   v_template [V,3]
+ *   blend      [K, 3V]: row n < NB is shapedirs[:, :, n], row NB + p is posedirs[:, :, p], each flattened (vertex, xyz)
+ *   J_template [J,3] = J_regressor v_template and J_dirs [J,3,NB] = J_regressor shapedirs (steps 4-5 folded, in float64)
+ *   weights    [V,J]   skinning weights, any sparsity
+ *   parents    [J]     HOST int32: parents[0] = -1, 0 <= parents[j] < j
+ * 2 <= J <= 32, NB >= 1, K <= 512, V >= 1 - else SNERF_E_BADARG, as for every argument error here, before anything touches a device. */
+typedef struct snerf_smpl_model {
+    int32_t V, J, NB;
+    const float *v_template, *blend, *J_template, *J_dirs, *weights;
+    const int32_t *parents;
+} snerf_smpl_model;
+/* betas [betas_rows, NB] with betas_rows 1 (shared by the batch) or B; body_pose [B, 3 (J - 1)]; global_orient [B,3] or NULL = zeros
+ * -> vertices [B,V,3]; joints [B,J,3] unless NULL; rig [B, 12 J + K] = per pose the J transforms A_j (3 x 4, row-major), then betas
+ * and pose_feature: the record the vertex stage and the backward read (always written: it is also the forward's own hand-over
+ * between its rig and vertex stages).  Nothing else of size B V is read or written.  Any B >= 0 (0: no-op).  Every element of every
+ * output is written; two calls give the same bits.  fp32 in and out; the per-pose chain (steps 2, 5, 7, 10: B J work) is evaluated in
+ * float64 and rounded once, the sums over K and over the joints are fp32 fused multiply-adds with the template added last. */
+SNERF_API int snerf_smpl_lbs_fwd_f32(const snerf_smpl_model *model, const float *betas, int betas_rows, const float *body_pose,
+                              const float *global_orient, int64_t B, float *vertices, float *joints, float *rig,
+                              snerf_stream_t stream);
+/* Bytes of the backward's workspace for B poses (vertex-slice partial sums, their sum, d_betas rows); -1 on a bad argument. */
+SNERF_API int64_t snerf_smpl_lbs_bwd_workspace_bytes(const snerf_smpl_model *model, int64_t B);
+/* Its backward: the forward's inputs and rig; d_vertices [B,V,3] and d_joints [B,J,3] are the incoming gradients (each nullable, not
+ * both) -> d_betas [betas_rows, NB] (with one row: the sum over the batch), d_body_pose [B, 3 (J - 1)], d_global_orient [B,3]; each
+ * output nullable, every element of a non-NULL one written.  v_posed and T_v are recomputed: the forward keeps no [B,V] tensor.
+ * The sums over the vertices go through vertex slices in the workspace and a fixed-order reduce - no atomics, the same bits on every
+ * call.  The Rodrigues formula is differentiated as written in step 2, 1e-8 included: finite at the zero pose. */
+SNERF_API int snerf_smpl_lbs_bwd_f32(const snerf_smpl_model *model, const float *betas, int betas_rows, const float *body_pose,
+                              const float *global_orient, const float *rig, const float *d_vertices, const float *d_joints,
+                              int64_t B, void *workspace, int64_t workspace_bytes, float *d_betas, float *d_body_pose,
+                              float *d_global_orient, snerf_stream_t stream);
+
 /* ---- 8(f)-1: on-device ray generation + stratified coarse sampling --------------------------------------
  * Replaces get_rays (utils.py:50-54) + CoarseSampling (datasets/transforms.py:80-89) + ToTensor (:13-21) for a
  * batch of rays.  poses: fp64 [n_frames, 4, 4] camera-to-world; ray_index int64 [B] = frame*H*W + row*W + col;

@@ -32,6 +32,12 @@ class WarpDesc(ctypes.Structure):
 _P = c_void_p  # device pointers travel as integers (tensor.data_ptr())
 
 
+class SmplModel(ctypes.Structure):
+    """struct snerf_smpl_model - the body model's device arrays and its parent table (a HOST array of J int32)."""
+    _fields_ = [("V", c_int32), ("J", c_int32), ("NB", c_int32), ("v_template", _P), ("blend", _P), ("J_template", _P),
+                ("J_dirs", _P), ("weights", _P), ("parents", POINTER(c_int32))]
+
+
 class AdamState(ctypes.Structure):
     """struct snerf_adam_state - torch.optim.Adam over one flat fp32 buffer (solver/nerf_solver.py:11-14, 31-33)."""
     _fields_ = [("params", _P), ("grads", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("n_params", c_int64),
@@ -133,6 +139,10 @@ SIGNATURES = {
     "snerf_vertex_warp_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
     # the canonical-density loss of SmplNerfSolver: Gaussian-mixture pdf and its sample gradient (csrc/gmm_pdf.hip)
     "snerf_gmm_pdf_f32": (c_int, [_P, _P, c_int64, c_int, c_float, _P, _P, _P]),
+    # the SMPL body model: linear blend skinning (csrc/smpl_lbs.hip)
+    "snerf_smpl_lbs_fwd_f32": (c_int, [POINTER(SmplModel), _P, c_int, _P, _P, c_int64, _P, _P, _P, _P]),
+    "snerf_smpl_lbs_bwd_workspace_bytes": (c_int64, [POINTER(SmplModel), c_int64]),
+    "snerf_smpl_lbs_bwd_f32": (c_int, [POINTER(SmplModel), _P, c_int, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
     "snerf_raygen_f64": (c_int, [_P, c_int64, c_int, c_int, c_double, _P, _P, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "snerf_mlp_fwd_encoded_f32": (c_int, [POINTER(MlpDesc), _P, _P, c_int64, c_int64, _P, _P]),
     "snerf_render_rays_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),

@@ -8,6 +8,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     fine_sampling       utils.py:231-264
     vertex_attention_warp   models/dynamic_pipeline.py:51-70 (the attention warp of DynamicPipeline as one operator)
     GaussianMixture / gaussian_mixture_pdf   utils.py:72-111 (the canonical-density term of SmplNerfSolver's loss)
+    smpl_lbs            the body model the reference takes from smplx (train.py:214): SMPL linear blend skinning
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -568,3 +569,113 @@ class GaussianMixture:
         if self.means.shape[-1] != 3:
             raise ValueError(f"GaussianMixture.pdf: the kernel is written for 3-dimensional Gaussians, got {self.means.shape[-1]}")
         return gaussian_mixture_pdf(samples, self.means, self._std)
+
+
+# ------------------------------------------------------------------------------------------------
+# The SMPL body model: linear blend skinning (csrc/smpl_lbs.hip; body_model.SmplBodyModel is the module on top)
+# ------------------------------------------------------------------------------------------------
+_SMPL_ARRAYS = ("v_template", "blend", "J_template", "J_dirs", "weights")
+
+
+def _smpl_record(mb):
+    """(struct snerf_smpl_model, what keeps its pointers alive, V, J, NB) of a mapping with the arrays of include/smplnerf.h:
+    v_template [V,3], blend [NB + 9(J-1), 3V], J_template [J,3], J_dirs [J,3,NB], weights [V,J] (fp32, on the GPU, contiguous) and
+    parents (J ints on the host)."""
+    import ctypes
+    arrs = [mb[k] for k in _SMPL_ARRAYS]
+    for k, t in zip(_SMPL_ARRAYS, arrs):
+        _need_cuda(k, t)
+        if not t.is_contiguous():
+            raise RuntimeError(f"smpl_lbs: `{k}` must be contiguous")
+    V, J, NB = arrs[0].shape[0], arrs[4].shape[1], arrs[3].shape[2]
+    K = NB + 9 * (J - 1)
+    want = {"v_template": (V, 3), "blend": (K, 3 * V), "J_template": (J, 3), "J_dirs": (J, 3, NB), "weights": (V, J)}
+    for k, t in zip(_SMPL_ARRAYS, arrs):
+        if tuple(t.shape) != want[k]:
+            raise RuntimeError(f"smpl_lbs: `{k}` has shape {tuple(t.shape)}, expected {want[k]} (V={V}, J={J}, NB={NB})")
+    parents = [int(p) for p in mb["parents"]]
+    if len(parents) != J:
+        raise RuntimeError(f"smpl_lbs: {len(parents)} parents for {J} joints")
+    host = (ctypes.c_int32 * J)(*parents)
+    rec = _lib.SmplModel(V, J, NB, *(ptr(t) for t in arrs), host)
+    return rec, (arrs, host), V, J, NB
+
+
+def _smpl_fwd(mb, betas, body_pose, global_orient):
+    import ctypes
+    rec, keep, V, J, NB = _smpl_record(mb)
+    B, dev = body_pose.shape[0], body_pose.device
+    vertices = torch.empty((B, V, 3), device=dev, dtype=torch.float32)
+    joints = torch.empty((B, J, 3), device=dev, dtype=torch.float32)
+    rig = torch.empty((B, 12 * J + NB + 9 * (J - 1)), device=dev, dtype=torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(dev), _lib.timed(f"smpl_lbs_fwd[V={V}]"):
+        check(lib.snerf_smpl_lbs_fwd_f32(ctypes.byref(rec), ptr(betas), betas.shape[0], ptr(body_pose), ptr(global_orient), B,
+                                         ptr(vertices), ptr(joints), ptr(rig), current_stream()), "snerf_smpl_lbs_fwd_f32")
+    return vertices, joints, rig
+
+
+class _SmplLbsFn(torch.autograd.Function):
+    """snerf_smpl_lbs_fwd_f32 / snerf_smpl_lbs_bwd_f32 under autograd.  What is kept for the backward is the inputs and the
+    per-pose rig record [B, 12 J + K]; nothing of size B V."""
+
+    @staticmethod
+    def forward(ctx, mb, betas, body_pose, global_orient):
+        vertices, joints, rig = _smpl_fwd(mb, betas, body_pose, global_orient)
+        ctx.mb = mb
+        ctx.has_orient = global_orient is not None
+        ctx.save_for_backward(betas, body_pose, rig, *([global_orient] if ctx.has_orient else []))
+        ctx.set_materialize_grads(False)
+        return vertices, joints
+
+    @staticmethod
+    def backward(ctx, d_vertices, d_joints):
+        import ctypes
+        if d_vertices is None and d_joints is None:
+            return None, None, None, None
+        betas, body_pose, rig = ctx.saved_tensors[:3]
+        global_orient = ctx.saved_tensors[3] if ctx.has_orient else None
+        d_vertices, d_joints = (None if g is None else g.contiguous().float() for g in (d_vertices, d_joints))
+        rec, keep, V, J, NB = _smpl_record(ctx.mb)
+        B, dev = body_pose.shape[0], body_pose.device
+        need = ctx.needs_input_grad
+        d_betas = torch.empty_like(betas) if need[1] else None
+        d_pose = torch.empty_like(body_pose) if need[2] else None
+        d_orient = torch.empty_like(global_orient) if ctx.has_orient and need[3] else None
+        if B == 0:
+            return None, None if d_betas is None else torch.zeros_like(betas), d_pose, d_orient
+        lib = _lib.load()
+        nbytes = lib.snerf_smpl_lbs_bwd_workspace_bytes(ctypes.byref(rec), B)
+        if nbytes < 0:
+            check(-1, "snerf_smpl_lbs_bwd_workspace_bytes")
+        ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev), _lib.timed(f"smpl_lbs_bwd[V={V}]"):
+            check(lib.snerf_smpl_lbs_bwd_f32(ctypes.byref(rec), ptr(betas), betas.shape[0], ptr(body_pose), ptr(global_orient),
+                                             ptr(rig), ptr(d_vertices), ptr(d_joints), B, ptr(ws), nbytes, ptr(d_betas), ptr(d_pose),
+                                             ptr(d_orient), current_stream()), "snerf_smpl_lbs_bwd_f32")
+        return None, d_betas, d_pose, d_orient
+
+
+def smpl_lbs(model_buffers, betas, body_pose, global_orient=None):
+    """SMPL linear blend skinning in two launches (include/smplnerf.h lists the ten steps): (vertices [B,V,3], joints [B,J,3]).
+    model_buffers: a mapping with the arrays of struct snerf_smpl_model - v_template, blend, J_template, J_dirs, weights as fp32 GPU
+    tensors and parents as J host ints (SmplBodyModel.kernel_buffers()).  betas [1 or B, NB], body_pose [B, 3(J-1)],
+    global_orient [B,3] or None (= zeros).  Differentiable with respect to betas, body_pose and global_orient; the model arrays
+    are constants.  No [B,V,4,4] transform tensor and no [B,V,3] temporary exists, forward or backward."""
+    for nm, t in (("betas", betas), ("body_pose", body_pose)) + ((("global_orient", global_orient),) if global_orient is not None else ()):
+        _need_cuda(nm, t)
+    J, NB = model_buffers["weights"].shape[1], model_buffers["J_dirs"].shape[2]
+    if body_pose.dim() != 2 or body_pose.shape[1] != 3 * (J - 1):
+        raise RuntimeError(f"smpl_lbs: body_pose must be [B, {3 * (J - 1)}], got {tuple(body_pose.shape)}")
+    B = body_pose.shape[0]
+    if betas.dim() != 2 or betas.shape[1] != NB or betas.shape[0] not in (1, B):
+        raise RuntimeError(f"smpl_lbs: betas must be [1 or {B}, {NB}], got {tuple(betas.shape)}")
+    if global_orient is not None and tuple(global_orient.shape) != (B, 3):
+        raise RuntimeError(f"smpl_lbs: global_orient must be [{B}, 3], got {tuple(global_orient.shape)}")
+    if betas.shape[0] == B and B > 1 and betas.stride(0) == 0:
+        betas = betas[:1]          # one row shared by the batch (estimator.betas.expand(B, -1)): read as such, d_betas summed by the kernel
+    b, p = betas.contiguous(), body_pose.contiguous()
+    g = None if global_orient is None else global_orient.contiguous()
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (b, p, g)):
+        return _SmplLbsFn.apply(model_buffers, b, p, g)
+    return _smpl_fwd(model_buffers, b, p, g)[:2]
