@@ -443,10 +443,9 @@ static int fwd_bf16(const snerf_mlp_desc *desc, const void *packed, int nsplit, 
                     int dirs_per_sample, const float *add, int64_t n, int samples_per_ray, float *raw, float *act,
                     bool train, snerf_stream_t stream, const char *what) {
     Plan P;
-    if (nsplit != 2 && nsplit != 3 && nsplit != SNERF_SPLIT_F16X3)
-        return fail(SNERF_E_BADARG, "%s: nsplit must be 2, 3 or %d (f16x3)", what, SNERF_SPLIT_F16X3);
-    int rc = plan16(desc, P, what);
-    if (rc) return rc;
+    int ns, fmt;
+    int rc = split_format(what, nsplit, &ns, &fmt);
+    if (rc || (rc = plan16(desc, P, what))) return rc;
     if (n < 0 || samples_per_ray < 1) return fail(SNERF_E_BADARG, "%s: bad n/samples_per_ray", what);
     if (n == 0) return SNERF_OK;
     if (!packed || !x || !raw || (train && !act)) return fail(SNERF_E_BADARG, "%s: null pointer", what);
@@ -496,18 +495,18 @@ static int fwd_bf16(const snerf_mlp_desc *desc, const void *packed, int nsplit, 
         A.act_h2 = L.h2;
         A.act_mask = L.mask;
         A.act_rows = L.act_rows;
-        if (nsplit == SNERF_SPLIT_F16X3 &&
+        if (fmt == FMT_F16 &&
             hipMemsetAsync(act + (int64_t)L.act_rows * n * 16, 0x80, STAT_INTS * sizeof(int), (hipStream_t)stream) != hipSuccess)
             return fail(SNERF_E_LAUNCH, "%s: cannot reset the layer statistics", what);
         A.pos_nkb16 = Q.pos_nkb;
         A.add_nkb16 = Q.add_nkb;
         A.dir_nkb16 = Q.dir_nkb;
-        if (nsplit == SNERF_SPLIT_F16X3) return launch_bf16<2, true, FMT_F16>(A, (hipStream_t)stream);
-        if (nsplit == 3) return launch_bf16<3, true>(A, (hipStream_t)stream);
+        if (fmt == FMT_F16) return launch_bf16<2, true, FMT_F16>(A, (hipStream_t)stream);
+        if (ns == 3) return launch_bf16<3, true>(A, (hipStream_t)stream);
         return launch_bf16<2, true>(A, (hipStream_t)stream);
     }
-    if (nsplit == SNERF_SPLIT_F16X3) return launch_bf16<2, false, FMT_F16>(A, (hipStream_t)stream);
-    if (nsplit == 3) return launch_bf16<3, false>(A, (hipStream_t)stream);
+    if (fmt == FMT_F16) return launch_bf16<2, false, FMT_F16>(A, (hipStream_t)stream);
+    if (ns == 3) return launch_bf16<3, false>(A, (hipStream_t)stream);
     return launch_bf16<2, false>(A, (hipStream_t)stream);
 }
 
@@ -516,25 +515,22 @@ static int fwd_bf16(const snerf_mlp_desc *desc, const void *packed, int nsplit, 
 extern "C" int64_t snerf_mlp_packed_bf16_bytes(const snerf_mlp_desc *desc, int nsplit) {
     using namespace snerf;
     Plan P;
-    if (nsplit != 2 && nsplit != 3 && nsplit != SNERF_SPLIT_F16X3)
-        return fail(SNERF_E_BADARG, "mlp_packed_bf16_bytes: nsplit must be 2, 3 or %d (f16x3)", SNERF_SPLIT_F16X3);
-    int rc = plan16(desc, P, "mlp_packed_bf16_bytes");
-    if (rc) return rc;
-    return (int64_t)(P.total_slabs + SLAB_PAD) * slab16_bytes(nsplit == SNERF_SPLIT_F16X3 ? 2 : nsplit);
+    int ns;
+    int rc = split_format("mlp_packed_bf16_bytes", nsplit, &ns, nullptr);
+    if (rc || (rc = plan16(desc, P, "mlp_packed_bf16_bytes"))) return rc;
+    return (int64_t)(P.total_slabs + SLAB_PAD) * slab16_bytes(ns);
 }
 
 extern "C" int snerf_mlp_pack_bf16(const snerf_mlp_desc *desc, const float *params_flat, void *packed, int nsplit,
                                    snerf_stream_t stream) {
     using namespace snerf;
     Plan P;
-    if (nsplit != 2 && nsplit != 3 && nsplit != SNERF_SPLIT_F16X3)
-        return fail(SNERF_E_BADARG, "mlp_pack_bf16: nsplit must be 2, 3 or %d (f16x3)", SNERF_SPLIT_F16X3);
-    int rc = plan16(desc, P, "mlp_pack_bf16");
-    if (rc) return rc;
+    int ns, fmt;
+    int rc = split_format("mlp_pack_bf16", nsplit, &ns, &fmt);
+    if (rc || (rc = plan16(desc, P, "mlp_pack_bf16"))) return rc;
     if (!params_flat || !packed) return fail(SNERF_E_BADARG, "mlp_pack_bf16: null pointer");
     if (!aligned(packed, 16)) return fail(SNERF_E_ALIGN, "mlp_pack_bf16: packed must be 16-byte aligned");
-    if (nsplit == SNERF_SPLIT_F16X3) return launch_pack_bf16(P, 2, params_flat, packed, (hipStream_t)stream, "mlp_pack_bf16", FMT_F16);
-    return launch_pack_bf16(P, nsplit, params_flat, packed, (hipStream_t)stream, "mlp_pack_bf16");
+    return launch_pack_bf16(P, ns, params_flat, packed, (hipStream_t)stream, "mlp_pack_bf16", fmt);
 }
 
 extern "C" int snerf_mlp_fwd_bf16_f32(const snerf_mlp_desc *desc, const void *packed, int nsplit, const float *x,

@@ -195,6 +195,15 @@ struct SlabPipe16 {
 // operands pre-scaled by powers of two (per layer for the weights, per sample for the activations) on
 // v_mfma_f32_16x16x32_f16 (mlp_bf16.hip, "f16x3").  Both take eight 16-bit values per lane: `bf8` is the container.
 enum { FMT_BF16 = 0, FMT_F16 = 1 };
+// host: the `nsplit` of the C ABI (2, 3 or SNERF_SPLIT_F16X3) as (parts per operand, format); either output may be null
+inline int split_format(const char *what, int nsplit, int *ns, int *fmt) {
+    if (nsplit != 2 && nsplit != 3 && nsplit != SNERF_SPLIT_F16X3)
+        return fail(SNERF_E_BADARG, "%s: nsplit must be 2, 3 or %d (f16x3)", what, SNERF_SPLIT_F16X3);
+    const bool f16 = nsplit == SNERF_SPLIT_F16X3;
+    if (ns) *ns = f16 ? 2 : nsplit;
+    if (fmt) *fmt = f16 ? FMT_F16 : FMT_BF16;
+    return SNERF_OK;
+}
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 template <int FMT>
 __device__ __forceinline__ f4 mfma16(const bf8 &a, const bf8 &b, const f4 &c) {

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "mlp_train_device.h"
+#include "mlp_wgrad_jobs.h"
 
 namespace snerf {
 
@@ -255,7 +256,7 @@ constexpr int WL_WAVES = 16, WL_THREADS = WL_WAVES * 64;
 constexpr int WL_STAGE = 16;                      // samples per stage (4 MFMA k-steps)
 constexpr int WL_ROW_FLOATS = WL_STAGE * 16;      // one tile-row of a stage: 1 KiB
 constexpr int WL_XROW0 = 32, WL_YROW0 = 36;         // LDS rows of the folded operands: <= 4 extra X rows, one extra dY row
-constexpr int WL_SLOT_FLOATS = 37 * WL_ROW_FLOATS;  // 16 dY rows + 16 X rows + the folded rows (mlp_train_device.h)
+constexpr int WL_SLOT_FLOATS = 37 * WL_ROW_FLOATS;  // 16 dY rows + 16 X rows + the folded rows (mlp_wgrad_jobs.h)
 constexpr int WL_SLOTS = 4;                          // ring depth: up to WL_SLOTS - 2 stages in flight behind the one awaited
 // (Measured r03: 32-sample stages in a double buffer - half the barriers per MFMA - 4.79 instead of 4.65 ms per launch: the
 // ~20 % of a stage that does not overlap with the MFMAs is not the barrier.  The 8-tile job lasts 0.7 of a 16-tile one for
@@ -264,7 +265,7 @@ constexpr int WL_SLOTS = 4;                          // ring depth: up to WL_SLO
 constexpr int WL_LDS_BYTES = WL_SLOTS * WL_SLOT_FLOATS * 4;
 
 // the stage loop and the epilogue for one wave that owns TI x TJ accumulator tiles
-// what rides with a wide job (mlp_train_device.h: wgrad_kind == 1)
+// what rides with a wide job (mlp_wgrad_jobs.h: wgrad_kind == 1)
 struct WgradFold {
     int ex;            // extra X tile-rows: the folded segment's k-blocks (0 = none)
     int ex_tj0;        // ... whose partial tiles are columns ex_tj0 .. of the SAME layer
@@ -283,9 +284,9 @@ __device__ __forceinline__ void wgrad_wave(const Plan &P, const Layer &Ly, const
     const bool want_bias = bias_job && bj == 0;
     const int kslot = lane >> 4;
     const int64_t n = A.n;
-    const int64_t begin = (int64_t)blockIdx.y * A.chunk;
-    const int64_t end = min(n, begin + A.chunk);
-    const int nstages = begin < end ? (int)((end - begin + WL_STAGE - 1) / WL_STAGE) : 0;
+    const WgradChunk C = wgrad_chunk(A);
+    const int64_t begin = C.begin, end = C.end;
+    const int nstages = C.stages(WL_STAGE);
     // folded tiles of this wave (compile-time variants: the plain jobs keep their instruction stream):
     // (dY rows TI*bi .., extra X row bj) and (extra dY row, X row TJ*bj + bi)
     const bool has3 = (FX || FY) && F.src != nullptr;
@@ -447,11 +448,8 @@ __device__ __forceinline__ void wgrad_wave(const Plan &P, const Layer &Ly, const
             slot = slot == WL_SLOTS - 1 ? 0 : slot + 1;
         }
     };
-    // stages [0, nfast) lie inside the chunk with all their samples
-    // (begin < end: a chunk behind the end of the buffer has no stages at all.  r04: without this the difference went
-    // negative and the masked loop ran stages -k .. -1 - a = 0 against whatever the LDS held, which is 0 unless that is a NaN:
-    // the first process on a freshly booted GPU got NaN gradients, everybody else the right ones.  tools/ab/nan_hunt.py)
-    const int nfast = (begin < end && (!active || n_ti == TI)) ? (int)((end - begin) / WL_STAGE) : 0;
+    // stages [0, nfast) lie inside the chunk with all their samples (none in a chunk behind the end of the buffer: WgradChunk)
+    const int nfast = (!active || n_ti == TI) ? C.whole_stages(WL_STAGE) : 0;
     if (want_bias) run(std::false_type{}, std::true_type{}, 0, nfast);
     else run(std::false_type{}, std::false_type{}, 0, nfast);
     run(std::true_type{}, std::true_type{}, nfast, nstages);
@@ -465,28 +463,18 @@ __device__ __forceinline__ void wgrad_wave(const Plan &P, const Layer &Ly, const
         for (int j = 0; j < TJ; ++j) {
             if (j >= n_tj) continue;
             const int ti = ti0 + TI * bi + i, tj = kb0 + 16 * jb + TJ * bj + j;   // (ti0: the job's first output tile)
-            *reinterpret_cast<f4 *>(part + ((int64_t)(ti * Ly.nkb + tj) * 64 + lane) * 4) = acc[i][j];
+            store_partial_tile(part, Ly.nkb, ti, tj, lane, acc[i][j]);
         }
-        if (want_bias) {
-            float v = bsum[i];
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            if (lane < 16) part[(int64_t)Ly.t_out * Ly.nkb * 256 + (ti0 + TI * bi + i) * 16 + lane] = v;
-        }
+        if (want_bias) store_bias_sums(part, Ly.t_out, Ly.nkb, ti0 + TI * bi + i, lane, bsum[i]);
         if (FX && fx)   // folded segment of the same layer: tile column ex_tj0 + bj
-            *reinterpret_cast<f4 *>(part + ((int64_t)((TI * bi + i) * Ly.nkb + F.ex_tj0 + bj) * 64 + lane) * 4) = accx[i];
+            store_partial_tile(part, Ly.nkb, TI * bi + i, F.ex_tj0 + bj, lane, accx[i]);
     }
     if (FY && fy) {     // the folded layer's (one output tile) partial: tile column = this wave's X row
         const Layer &Le = P.layer[F.ey_layer];
         float *pe = A.part + (int64_t)blockIdx.y * L.gp_floats + L.gp[F.ey_layer];
         const int tj = TJ * bj + bi;
-        *reinterpret_cast<f4 *>(pe + ((int64_t)tj * 64 + lane) * 4) = accy;
-        if (tj == 0) {   // its bias sums
-            float v = ysum;
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            if (lane < 16) pe[(int64_t)Le.t_out * Le.nkb * 256 + lane] = v;
-        }
+        store_partial_tile(pe, Le.nkb, 0, tj, lane, accy);
+        if (tj == 0) store_bias_sums(pe, Le.t_out, Le.nkb, 0, lane, ysum);   // its bias sums
     }
 }
 
@@ -494,46 +482,18 @@ __global__ __launch_bounds__(WL_THREADS) void mlp_wgrad_kernel(Plan P, TrainLayo
     extern __shared__ __attribute__((aligned(16))) float ring[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // ---- decode the job: (layer, segment, group of 16 input k-blocks) --------------------------------
-    int job = blockIdx.x, l = 0, s = 0, kb0 = 0;
-    for (l = 0; l < P.nlayers; ++l) {
-        bool found = false;
-        kb0 = 0;
-        for (s = 0; s < P.layer[l].nseg; ++s) {
-            const int cnt = wgrad_wide_jobs(P.layer[l], s);
-            if (job < cnt) { found = true; break; }
-            job -= cnt;
-            kb0 += P.layer[l].seg[s].nkb;
-        }
-        if (found) break;
-    }
+    // ---- the job: (layer, segment, group of 16 output tiles, group of 16 input k-blocks) ---------------
+    const WgradWideJob J = wgrad_wide_job(P, blockIdx.x);
+    const int l = J.l, s = J.s, kb0 = J.kb0, ib = J.ib, jb = J.jb;
     const Layer &Ly = P.layer[l];
-    const int nkg = (Ly.seg[s].nkb + 15) / 16;
-    const int ib = job / nkg, jb = job - ib * nkg;         // output tiles 16*ib .., k-blocks 16*jb .. of the segment
     const int ti0 = 16 * ib;
     const int n_rows_y = min(16, Ly.t_out - ti0), n_rows_x = min(16, Ly.seg[s].nkb - 16 * jb);
     const int64_t n = A.n;
-    int first_seg = 0;  // the bias sums ride with the first non-empty input segment of the layer
-    while (first_seg < Ly.nseg && Ly.seg[first_seg].nkb == 0) ++first_seg;
-    const bool bias_job = (s == first_seg && jb == 0);
+    const bool bias_job = (s == wgrad_bias_seg(Ly) && jb == 0);
 
-    // ---- stage loader: this wave brings LDS rows 2*wave, 2*wave+1 (rows 0..15 = dY, 16..31 = X) ----------
-    // rows the job does not have re-load row 0 of dY, so that every wave issues exactly two pieces per stage
-    // and one counted vmcnt serves all waves
+    // ---- stage loader: this wave brings LDS rows 2*wave, 2*wave+1: two pieces per stage ----------
     const float *row_src[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int r = 2 * wave + q;
-        int64_t grow = L.dy[l] + ti0;
-        if (r < 16) {
-            if (r < n_rows_y) grow = L.dy[l] + ti0 + r;
-            row_src[q] = A.dy + grow * n * 16;
-        } else if (r - 16 < n_rows_x) {
-            row_src[q] = A.act + (int64_t)(seg_act_row(P, L, l, s) + 16 * jb + (r - 16)) * n * 16;
-        } else {
-            row_src[q] = A.dy + grow * n * 16;
-        }
-    }
+    wgrad_row_sources<2>(P, L, A.dy, A.act, n, l, s, ti0, jb, n_rows_y, n_rows_x, wave, row_src);
     // ---- what rides with this job (first group of the layer's first wide segment only) ------------------------------
     WgradFold F{0, 0, -1, nullptr};
     if (A.fold && jb == 0 && ib == 0 && s == wgrad_first_wide_seg(Ly)) {
@@ -551,7 +511,7 @@ __global__ __launch_bounds__(WL_THREADS) void mlp_wgrad_kernel(Plan P, TrainLayo
     }
     // wave block shape: the job's <=16 x <=16 tiles are cut so that (up to) all 16 waves own a block
     const int ti = n_rows_y > 8 ? 4 : (n_rows_y > 4 ? 2 : 1), tj = n_rows_x > 8 ? 4 : (n_rows_x > 4 ? 2 : 1);
-    // the folding variants (mlp_train_device.h guarantees these shapes: 16 or 8 output tiles, 16 input k-blocks)
+    // the folding variants (mlp_wgrad_jobs.h guarantees these shapes: 16 or 8 output tiles, 16 input k-blocks)
     if (F.ex > 0 || F.ey_layer >= 0) {
         const bool x = F.ex > 0, y = F.ey_layer >= 0;
         if (ti == 2 && tj == 4 && x && y)
@@ -706,15 +666,10 @@ __device__ __forceinline__ void wgrad_direct_block(float *part_chunk, int gp_off
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= n_tj) continue;
-            const int ti = 4 * bi + i, tj = kb0 + 4 * bj + j;
-            *reinterpret_cast<f4 *>(part + ((int64_t)(ti * lnkb + tj) * 64 + lane) * 4) = acc[i][j];
+            // (the store stays here, on the writer's offset: through store_partial_tile mlp_wgrad_direct_kernel spilt 4 more registers)
+            *reinterpret_cast<f4 *>(part + partial_tile_offset(lnkb, 4 * bi + i, kb0 + 4 * bj + j, lane)) = acc[i][j];
         }
-        if (want_bias) {
-            float v = bsum[i];
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            if (lane < 16) part[(int64_t)lt_out * lnkb * 256 + (4 * bi + i) * 16 + lane] = v;
-        }
+        if (want_bias) store_bias_sums(part, lt_out, lnkb, 4 * bi + i, lane, bsum[i]);
     }
 }
 
@@ -737,38 +692,45 @@ struct NarrowTable {
     int n, pad_[7];
     NarrowJob j[MAX_NARROW_JOBS];
 };
-// host: the jobs of wgrad_direct_jobs(P, fold) in the order the f16 twin of this kernel walks them; false: too many for the table
+// host: the jobs of wgrad_direct_jobs(P, fold), in the order of wgrad_narrow_job (the same walk: wgrad_each_pair, then
+// wgrad_narrow_block); false: too many for the table
 static bool make_narrow_table(const Plan &P, const TrainLayout &L, int fold, NarrowTable &T) {
     T.n = 0;
-    for (int l = 0; l < P.nlayers; ++l) {
+    bool fits = true;
+    wgrad_each_pair(P, [&](int l, int sg, int kb0) {
         const Layer &Ly = P.layer[l];
-        int first_seg = 0;   // the bias sums ride with the first non-empty input segment of the layer
-        while (first_seg < Ly.nseg && Ly.seg[first_seg].nkb == 0) ++first_seg;
-        int kb0 = 0;
-        for (int sg = 0; sg < Ly.nseg; ++sg) {
-            if (wgrad_kind(P, l, sg, fold) == 2) {
-                const int nbi = (Ly.t_out + 3) / 4, nbj = (Ly.seg[sg].nkb + 3) / 4;
-                for (int bi = 0; bi < nbi; ++bi)
-                    for (int bj = 0; bj < nbj; ++bj) {
-                        if (T.n >= MAX_NARROW_JOBS || bi > 255 || bj > 255 || kb0 > 32767) return false;
-                        NarrowJob &J = T.j[T.n++];
-                        J.dy_row = L.dy[l] + 4 * bi;
-                        J.x_row = seg_act_row(P, L, l, sg) + 4 * bj;
-                        J.gp = L.gp[l];
-                        J.nkb = Ly.nkb;
-                        J.t_out = Ly.t_out;
-                        J.bi_bj_kb0 = bi | (bj << 8) | (kb0 << 16);
-                        const int n_ti = std::min(4, Ly.t_out - 4 * bi), n_tj = std::min(4, Ly.seg[sg].nkb - 4 * bj);
-                        J.nt_bias = n_ti | (n_tj << 4) | ((sg == first_seg && bj == 0) ? 256 : 0);
-                        J.pad_ = 0;
-                    }
+        const int cnt = wgrad_narrow_jobs(P, l, sg, fold);
+        for (int k = 0; k < cnt; ++k) {
+            int bi, bj;
+            wgrad_narrow_block(Ly, sg, k, bi, bj);
+            if (T.n >= MAX_NARROW_JOBS || bi > 255 || bj > 255 || kb0 > 32767) {
+                fits = false;
+                return true;
             }
-            kb0 += Ly.seg[sg].nkb;
+            NarrowJob &J = T.j[T.n++];
+            J.dy_row = L.dy[l] + 4 * bi;
+            J.x_row = seg_act_row(P, L, l, sg) + 4 * bj;
+            J.gp = L.gp[l];
+            J.nkb = Ly.nkb;
+            J.t_out = Ly.t_out;
+            J.bi_bj_kb0 = bi | (bj << 8) | (kb0 << 16);
+            const int n_ti = std::min(4, Ly.t_out - 4 * bi), n_tj = std::min(4, Ly.seg[sg].nkb - 4 * bj);
+            J.nt_bias = n_ti | (n_tj << 4) | ((sg == wgrad_bias_seg(Ly) && bj == 0) ? 256 : 0);
+            J.pad_ = 0;
         }
-    }
-    return true;
+        return false;
+    });
+    return fits;
 }
 typedef int nj_i8 __attribute__((ext_vector_type(8)));
+
+// this wave's quarter [wb, we) of the workgroup's chunk (multiples of 4 samples)
+__device__ __forceinline__ void wgrad_direct_quarter(const WgradArgs &A, int wave, int64_t &wb, int64_t &we) {
+    const WgradChunk C = wgrad_chunk(A);
+    const int64_t sub = C.begin < C.end ? ((C.end - C.begin + 4 * WG_WAVES - 1) / (4 * WG_WAVES)) * 4 : 0;
+    wb = min(C.end, C.begin + wave * sub);
+    we = min(C.end, wb + sub);
+}
 
 template <int WG_PREFETCH>
 __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void mlp_wgrad_direct_tab_kernel(NarrowTable tab_in_kernarg, WgradArgs A,
@@ -784,11 +746,8 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     const int n_ti = J.nt_bias & 15, n_tj = (J.nt_bias >> 4) & 15;
     const bool want_bias = (J.nt_bias & 256) != 0;
     const int64_t n = A.n;
-    // this wave's quarter of the chunk (multiples of 4 samples)
-    const int64_t begin = (int64_t)blockIdx.y * A.chunk;
-    const int64_t end = min(n, begin + A.chunk);
-    const int64_t sub = begin < end ? ((end - begin + 4 * WG_WAVES - 1) / (4 * WG_WAVES)) * 4 : 0;
-    const int64_t wb = min(end, begin + wave * sub), we = min(end, wb + sub);
+    int64_t wb, we;
+    wgrad_direct_quarter(A, wave, wb, we);
     // wave-uniform row bases at sample wb (rows the block does not have alias row 0: never read)
     const float *ya[4], *xb[4];
 #pragma unroll
@@ -810,33 +769,15 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     __shared__ __attribute__((aligned(16))) float s_acc[(WG_WAVES - 1) * (16 * 256 + 4 * 64)];   // 3 x (16 tiles + 4 bias sums)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // ---- decode the job: (narrow layer, segment, 4x4-tile block) -------------------------------------
-    int job = blockIdx.x, l = 0, s = 0, kb0 = 0, nbj = 1;
-    for (l = 0; l < P.nlayers; ++l) {
-        bool found = false;
-        kb0 = 0;
-        for (s = 0; s < P.layer[l].nseg; ++s) {
-            nbj = (P.layer[l].seg[s].nkb + 3) / 4;
-            const int cnt = wgrad_kind(P, l, s, A.fold) == 2 ? ((P.layer[l].t_out + 3) / 4) * nbj : 0;
-            if (job < cnt) { found = true; break; }
-            job -= cnt;
-            kb0 += P.layer[l].seg[s].nkb;
-        }
-        if (found) break;
-    }
+    // ---- the job: (narrow layer, segment, 4x4-tile block) -------------------------------------
+    const WgradNarrowJob J = wgrad_narrow_job(P, A.fold, blockIdx.x);
+    const int l = J.l, s = J.s, kb0 = J.kb0, bi = J.bi, bj = J.bj;
     const Layer &Ly = P.layer[l];
-    const int bi = job / nbj, bj = job - bi * nbj;
     const int n_ti = min(4, Ly.t_out - 4 * bi), n_tj = min(4, Ly.seg[s].nkb - 4 * bj);
     const int64_t n = A.n;
-    int first_seg = 0;  // the bias sums ride with the first non-empty input segment of the layer
-    while (first_seg < Ly.nseg && Ly.seg[first_seg].nkb == 0) ++first_seg;
-    const bool want_bias = (s == first_seg && bj == 0);
-
-    // this wave's quarter of the chunk (multiples of 4 samples)
-    const int64_t begin = (int64_t)blockIdx.y * A.chunk;
-    const int64_t end = min(n, begin + A.chunk);
-    const int64_t sub = begin < end ? ((end - begin + 4 * WG_WAVES - 1) / (4 * WG_WAVES)) * 4 : 0;
-    const int64_t wb = min(end, begin + wave * sub), we = min(end, wb + sub);
+    const bool want_bias = (s == wgrad_bias_seg(Ly) && bj == 0);
+    int64_t wb, we;
+    wgrad_direct_quarter(A, wave, wb, we);
     // wave-uniform row bases at sample wb (rows the block does not have alias row 0: never read)
     const float *ya[4], *xb[4];
 #pragma unroll
@@ -859,12 +800,9 @@ __global__ __launch_bounds__(256) void mlp_wgrad_reduce_kernel(Plan P, TrainLayo
     const Layer &Ly = P.layer[l];
     int rel = e - L.gp[l];
     int64_t dst = -1;
-    const int nw = Ly.t_out * Ly.nkb * 256;
-    int seg = 0;   // the input segment whose job wrote this element (the bias sums ride with the first non-empty one)
-    while (seg < Ly.nseg && Ly.seg[seg].nkb == 0) ++seg;
-    if (rel < nw) {
-        const int r = rel & 3, lane = (rel >> 2) & 63, tile = rel >> 8;
-        const int ti = tile / Ly.nkb, tj = tile - ti * Ly.nkb;
+    int seg = wgrad_bias_seg(Ly);   // the input segment whose job wrote this element (a bias sum: store_bias_sums' rider)
+    int ti, tj, lane, r;
+    if (partial_tile_element(Ly.t_out, Ly.nkb, rel, ti, tj, lane, r)) {   // (the format: mlp_wgrad_jobs.h)
         int kb0 = 0;
         for (seg = 0; seg + 1 < Ly.nseg && tj >= kb0 + Ly.seg[seg].nkb; ++seg) kb0 += Ly.seg[seg].nkb;
         const int row = 16 * ti + 4 * (lane >> 4) + r;  // MFMA D layout: row = 4*(lane>>4)+r, col = lane&15
@@ -872,11 +810,10 @@ __global__ __launch_bounds__(256) void mlp_wgrad_reduce_kernel(Plan P, TrainLayo
         const int col = slot_to_col(Ly, tj, jj >> 2, jj & 3);
         if (row < Ly.n_out && col >= 0) dst = Ly.w_off + (int64_t)row * Ly.n_in + col;
     } else {
-        const int row = rel - nw;
+        const int row = rel - (int)partial_bias_offset(Ly.t_out, Ly.nkb);
         if (row < Ly.n_out) dst = Ly.b_off + row;
     }
     if (dst < 0) return;
-    // the bias sums of a layer ride with its first non-empty segment; a folded pair was written by the wide job's chunks
     // a folded pair was written by its carrier's (wide) workgroups
     const int G = (seg < Ly.nseg && wgrad_kind(P, l, seg, fold) != 2) ? G_wide : G_narrow;
     // accumulate: this launch is one ray chunk of a larger batch (train_step.hip) - the chunks' sums are added in chunk order
@@ -1007,49 +944,13 @@ int launch_bwd(const snerf_mlp_desc *desc, const float *packed_t, const float *a
     const char *why;
     if (!desc) return fail(SNERF_E_BADARG, "mlp_bwd: desc is null");
     if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp_bwd: %s", why);
-    if (n < 0) return fail(SNERF_E_BADARG, "mlp_bwd: negative n");
+    if (int rc = check_bwd_args("mlp_bwd", desc, P, packed_t, act, d_raw, n, dy, gpart, flat_grad, x, dirs, spr, d_x, d_dirs, 8, 8)) return rc;
     if (n == 0) return SNERF_OK;
-    if (!packed_t || !act || !d_raw || !dy || !gpart || !flat_grad) return fail(SNERF_E_BADARG, "mlp_bwd: null pointer");
-    if (!aligned(packed_t, 16) || !aligned(act, 16) || !aligned(d_raw, 16) || !aligned(dy, 16) || !aligned(gpart, 16))
-        return fail(SNERF_E_ALIGN, "mlp_bwd: buffers must be 16-byte aligned");
     const bool input_grad = d_x != nullptr;
-    if (input_grad) {
-        if (!x || !d_dirs || (desc->use_dir && !dirs) || spr < 1) return fail(SNERF_E_BADARG, "mlp_bwd: input gradients need x, dirs, d_x, d_dirs");
-        if (P.pos_nkb > 8 || P.dir_nkb > 8)
-            return fail(SNERF_E_BADARG, "mlp_bwd: input gradients support at most 8 position / 8 direction encoder k-blocks");
-    }
     hipStream_t s = (hipStream_t)stream;
     TrainLayout L;
     make_train_layout(P, L);
-    const int nh = P.n_hidden;
-    BwdArgs A{};
-    A.packed_t = packed_t;
-    A.act = act;
-    A.d_raw = d_raw;
-    A.dy = dy;
-    A.n = n;
-    A.n_hidden = nh;
-    A.act_x1 = L.x[1];
-    A.act_h2 = L.h2;
-    A.act_mask = L.mask;
-    A.dy_sig = L.dy[nh + 2];
-    A.dy_din = L.dy[nh + 3];
-    A.dy_dn0 = L.dy[nh + 4];
-    A.dy_rgb = L.dy[nh + 5];
-    A.x = x;
-    A.dirs = dirs;
-    A.d_x = d_x;
-    A.d_dirs = d_dirs;
-    A.dirs_per_sample = dirs_per_sample ? 1 : 0;
-    A.spr = spr < 1 ? 1 : spr;
-    A.skip_mask = desc->skip_mask;
-    A.pos_L = desc->pos_freqs;
-    A.pos_id = desc->pos_identity ? 1 : 0;
-    A.pos_nkb = P.pos_nkb;
-    A.dir_L = desc->dir_freqs;
-    A.dir_id = desc->dir_identity ? 1 : 0;
-    A.dir_nkb = P.dir_nkb;
-    A.use_dir = desc->use_dir ? 1 : 0;
+    const BwdArgs A = fill_bwd_args(desc, P, L, packed_t, act, d_raw, n, dy, x, dirs, dirs_per_sample, spr, d_x, d_dirs);
     // the waves of a sample tile as in the forward (snerf_common.h tile_waves: small calls and the widths above 256 run 4-wave workgroups)
     const int n_cu = device_cu_count("mlp_bwd");
     if (n_cu < 1) return n_cu;

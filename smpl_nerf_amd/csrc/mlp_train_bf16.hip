@@ -14,6 +14,7 @@
 
 #include "mlp_bf16_device.h"
 #include "mlp_train_device.h"
+#include "mlp_wgrad_jobs.h"
 
 namespace snerf {
 
@@ -368,63 +369,30 @@ __global__ __launch_bounds__(WB_THREADS) void mlp_wgrad_bf16_kernel(Plan P, Trai
     extern __shared__ __attribute__((aligned(16))) float wring[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // ---- decode the job: (wide layer, segment, group of 16 input k-blocks), like mlp_wgrad_kernel ----
-    int job = blockIdx.x, l = 0, s = 0, kb0 = 0;
-    for (l = 0; l < P.nlayers; ++l) {
-        bool found = false;
-        kb0 = 0;
-        for (s = 0; s < P.layer[l].nseg; ++s) {
-            const int cnt = wgrad_wide(P.layer[l], s) ? (P.layer[l].seg[s].nkb + 15) / 16 : 0;
-            if (job < cnt) { found = true; break; }
-            job -= cnt;
-            kb0 += P.layer[l].seg[s].nkb;
-        }
-        if (found) break;
-    }
+    // ---- the job: (wide layer, segment, group of 16 input k-blocks), like mlp_wgrad_kernel ----
+    // one group of output tiles per pair (J.ib == 0, the job owns all of the layer's output tiles): plans_t admits width 256 only,
+    // i.e. t_out <= 16
+    const WgradWideJob J = wgrad_wide_job<true>(P, blockIdx.x);
+    const int l = J.l, s = J.s, kb0 = J.kb0, jb = J.jb;
     const Layer &Ly = P.layer[l];
-    const int jb = job;
     const int n_rows_y = Ly.t_out, n_rows_x = min(16, Ly.seg[s].nkb - 16 * jb);
     const int64_t n = A.n;
-    int first_seg = 0;
-    while (first_seg < Ly.nseg && Ly.seg[first_seg].nkb == 0) ++first_seg;
     const int bi = wave >> 2, bj = wave & 3;
     const int n_ti = max(0, min(TI, n_rows_y - TI * bi)), n_tj = max(0, min(TJ, n_rows_x - TJ * bj));
     const bool active = n_ti > 0 && n_tj > 0;
-    const bool want_bias = (s == first_seg && jb == 0 && bj == 0);
+    const bool want_bias = (s == wgrad_bias_seg(Ly) && jb == 0 && bj == 0);
     const int i16 = lane & 15, kq = lane >> 4;
 
-    const int64_t begin = (int64_t)blockIdx.y * A.chunk;
-    const int64_t end = min(n, begin + A.chunk);
-    const int nstages = begin < end ? (int)((end - begin + WB_STAGE - 1) / WB_STAGE) : 0;
-    float sx = 1.f, sy = 1.f, unscale = 1.f;   // f16x3: operand scales of the job and the scale of its result
-    if constexpr (F16) {
-        // X scale: the statistic of THIS segment (xstat_index: the layer's hidden input, or the encoder / additional-input
-        // columns).  r04: this read xstat[l] - the hidden input's - for every wide job of the layer; with encoded pose columns
-        // (1380 of them: wide jobs of their own) layer 0 has no hidden input, its statistic is unset and the scale was 2^114
-        // (found by tools/ab/fuzz_train.py in chunked f16x3 steps)
-        const int xi = xstat_index(P, l, s);
-        const int ex = 14 - (xi < 0 ? 0 : min(max(A.xstat[xi], -100), 100)), ey = 14 - min(max(A.ystat[l], -100), 100);
-        sx = __builtin_ldexpf(1.f, ex);
-        sy = __builtin_ldexpf(1.f, ey);
-        unscale = __builtin_ldexpf(1.f, -(ex + ey));
-    }
+    const WgradChunk C = wgrad_chunk(A);
+    const int64_t begin = C.begin, end = C.end;
+    const int nstages = C.stages(WB_STAGE);
+    WgradScales S{1.f, 1.f, 1.f};   // f16x3: operand scales of the job and the scale of its result
+    if constexpr (F16) S = wgrad_f16_scales(P, A, l, s);
+    const float sx = S.sx, sy = S.sy, unscale = S.unscale;
 
-    // ---- stage loader: this wave brings LDS rows 4*wave .. 4*wave+3 (rows 0..15 = dY, 16..31 = X), two 16-sample
-    // pieces each; rows the job does not have re-load row 0 of dY so that every wave issues exactly 8 pieces per stage
+    // ---- stage loader: this wave brings LDS rows 4*wave .. 4*wave+3, two 16-sample pieces each: 8 pieces per stage
     const float *row_src[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r = 4 * wave + q;
-        int64_t grow = L.dy[l];
-        if (r < 16) {
-            if (r < n_rows_y) grow = L.dy[l] + r;
-            row_src[q] = A.dy + grow * n * 16;
-        } else if (r - 16 < n_rows_x) {
-            row_src[q] = A.act + (int64_t)(seg_act_row(P, L, l, s) + 16 * jb + (r - 16)) * n * 16;
-        } else {
-            row_src[q] = A.dy + grow * n * 16;
-        }
-    }
+    wgrad_row_sources<4>(P, L, A.dy, A.act, n, l, s, 0, jb, n_rows_y, n_rows_x, wave, row_src);
     auto issue = [&](int stage, int slot) {
         // lane covers 16 B of a piece: position q = lane >> 2 (of 16), feature quad lane & 3; position q holds sample
         // q ^ ((q >> 3) & 1) of the piece (bank swizzle, see above)
@@ -526,16 +494,11 @@ __global__ __launch_bounds__(WB_THREADS) void mlp_wgrad_bf16_kernel(Plan P, Trai
 #pragma unroll
         for (int j = 0; j < TJ; ++j) {
             if (j >= n_tj) continue;
-            const int ti = TI * bi + i, tj = kb0 + 16 * jb + TJ * bj + j;
             if constexpr (F16) acc[i][j] *= unscale;
-            *reinterpret_cast<f4 *>(part + ((int64_t)(ti * Ly.nkb + tj) * 64 + lane) * 4) = acc[i][j];
+            store_partial_tile(part, Ly.nkb, TI * bi + i, kb0 + 16 * jb + TJ * bj + j, lane, acc[i][j]);
         }
-        if (want_bias) {   // lane (i16, kq) summed samples 8 kq .. of feature i16
-            float v = bsum[i];
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            if (lane < 16) part[(int64_t)Ly.t_out * Ly.nkb * 256 + (TI * bi + i) * 16 + lane] = v;
-        }
+        // lane (i16, kq) summed samples 8 kq .. of feature i16
+        if (want_bias) store_bias_sums(part, Ly.t_out, Ly.nkb, TI * bi + i, lane, bsum[i]);
     }
 }
 
@@ -549,34 +512,19 @@ __global__ __launch_bounds__(WB_THREADS) void mlp_wgrad_bf16_kernel(Plan P, Trai
 __global__ __launch_bounds__(64) void mlp_wgrad_direct_f16_kernel(Plan P, TrainLayout L, WgradArgs A) {
     using Tm = Terms<2>;
     const int lane = threadIdx.x;
-    // ---- decode the job: (narrow layer, segment, 4x4-tile block), like mlp_wgrad_direct_kernel ----
-    int job = blockIdx.x, l = 0, s = 0, kb0 = 0, nbj = 1;
-    for (l = 0; l < P.nlayers; ++l) {
-        bool found = false;
-        kb0 = 0;
-        for (s = 0; s < P.layer[l].nseg; ++s) {
-            nbj = (P.layer[l].seg[s].nkb + 3) / 4;
-            const int cnt = wgrad_wide(P.layer[l], s) ? 0 : ((P.layer[l].t_out + 3) / 4) * nbj;
-            if (job < cnt) { found = true; break; }
-            job -= cnt;
-            kb0 += P.layer[l].seg[s].nkb;
-        }
-        if (found) break;
-    }
+    // ---- the job: (narrow layer, segment, 4x4-tile block), like mlp_wgrad_direct_kernel (fold 0: a split step folds nothing) ----
+    const WgradNarrowJob J = wgrad_narrow_job(P, 0, blockIdx.x);
+    const int l = J.l, s = J.s, kb0 = J.kb0, bi = J.bi, bj = J.bj;
     const Layer &Ly = P.layer[l];
-    const int bi = job / nbj, bj = job - bi * nbj;
     const int n_ti = min(4, Ly.t_out - 4 * bi), n_tj = min(4, Ly.seg[s].nkb - 4 * bj);
     const int64_t n = A.n;
     const int i16 = lane & 15, kq = lane >> 4;
-    int first_seg = 0;  // the bias sums ride with the first non-empty input segment of the layer
-    while (first_seg < Ly.nseg && Ly.seg[first_seg].nkb == 0) ++first_seg;
-    const bool want_bias = (s == first_seg && bj == 0);
-    const int xi = xstat_index(P, l, s);
-    const int ex = 14 - (xi < 0 ? 0 : min(max(A.xstat[xi], -100), 100)), ey = 14 - min(max(A.ystat[l], -100), 100);
-    const float sx = __builtin_ldexpf(1.f, ex), sy = __builtin_ldexpf(1.f, ey), unscale = __builtin_ldexpf(1.f, -(ex + ey));
+    const bool want_bias = (s == wgrad_bias_seg(Ly) && bj == 0);
+    const WgradScales S = wgrad_f16_scales(P, A, l, s);
+    const float sx = S.sx, sy = S.sy, unscale = S.unscale;
 
-    const int64_t begin = (int64_t)blockIdx.y * A.chunk;
-    const int64_t end = min(n, begin + A.chunk);
+    const WgradChunk C = wgrad_chunk(A);
+    const int64_t begin = C.begin, end = C.end;
 
     // ---- stage loader: 32 samples of the block's 4 dY and 4 X tile-rows per stage, by DMA into LDS (two 1 KiB pieces per
     // row, sample s of a piece at position s ^ ((s >> 3) & 1) like the wide kernel; ONE slot of 16 KiB, refilled behind the
@@ -597,7 +545,7 @@ __global__ __launch_bounds__(64) void mlp_wgrad_direct_f16_kernel(Plan P, TrainL
         }
         row_src[r] = base + grow;
     }
-    const int nstages = begin < end ? (int)((end - begin + 31) / 32) : 0;
+    const int nstages = C.stages(32);
     auto issue = [&](int stage) __attribute__((always_inline)) {
         const int q = lane >> 2, sp = q ^ ((q >> 3) & 1);
         float *slot = dring;
@@ -667,15 +615,10 @@ __global__ __launch_bounds__(64) void mlp_wgrad_direct_f16_kernel(Plan P, TrainL
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= n_tj) continue;
-            const int ti = 4 * bi + i, tj = kb0 + 4 * bj + j;
-            *reinterpret_cast<f4 *>(part + ((int64_t)(ti * Ly.nkb + tj) * 64 + lane) * 4) = acc[i][j] * unscale;
+            store_partial_tile(part, Ly.nkb, 4 * bi + i, kb0 + 4 * bj + j, lane, acc[i][j] * unscale);
         }
-        if (want_bias) {   // lane (i16, kq) summed samples 8 kq .. of feature i16
-            float v = bsum[i];
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            if (lane < 16) part[(int64_t)Ly.t_out * Ly.nkb * 256 + (4 * bi + i) * 16 + lane] = v;
-        }
+        // lane (i16, kq) summed samples 8 kq .. of feature i16
+        if (want_bias) store_bias_sums(part, Ly.t_out, Ly.nkb, 4 * bi + i, lane, bsum[i]);
     }
 }
 
@@ -707,54 +650,28 @@ __global__ __launch_bounds__(WC_THREADS) void mlp_wgrad_f16_kernel(Plan P, Train
     extern __shared__ __attribute__((aligned(16))) float wring[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // ---- decode the job: (wide layer, segment, group of 16 input k-blocks), like mlp_wgrad_kernel ----
-    int job = blockIdx.x, l = 0, s = 0, kb0 = 0;
-    for (l = 0; l < P.nlayers; ++l) {
-        bool found = false;
-        kb0 = 0;
-        for (s = 0; s < P.layer[l].nseg; ++s) {
-            const int cnt = wgrad_wide(P.layer[l], s) ? (P.layer[l].seg[s].nkb + 15) / 16 : 0;
-            if (job < cnt) { found = true; break; }
-            job -= cnt;
-            kb0 += P.layer[l].seg[s].nkb;
-        }
-        if (found) break;
-    }
+    // ---- the job: (wide layer, segment, group of 16 input k-blocks), like mlp_wgrad_kernel ----
+    // one group of output tiles per pair (J.ib == 0, the job owns all of the layer's output tiles): plans_t admits width 256 only,
+    // i.e. t_out <= 16
+    const WgradWideJob J = wgrad_wide_job<true>(P, blockIdx.x);
+    const int l = J.l, s = J.s, kb0 = J.kb0, jb = J.jb;
     const Layer &Ly = P.layer[l];
-    const int jb = job;
     const int n_rows_y = Ly.t_out, n_rows_x = min(16, Ly.seg[s].nkb - 16 * jb);   // 16-feature tile-rows of the job
     const int64_t n = A.n;
-    int first_seg = 0;
-    while (first_seg < Ly.nseg && Ly.seg[first_seg].nkb == 0) ++first_seg;
     const int bi = wave >> 2, bj = wave & 3;
     const bool active = 2 * TI * bi < n_rows_y && 2 * TJ * bj < n_rows_x;
     const int m32 = lane & 31, kg = lane >> 5;
 
-    const int64_t begin = (int64_t)blockIdx.y * A.chunk;
-    const int64_t end = min(n, begin + A.chunk);
-    const int nstages = begin < end ? (int)((end - begin + WC_STAGE - 1) / WC_STAGE) : 0;
+    const WgradChunk C = wgrad_chunk(A);
+    const int64_t begin = C.begin, end = C.end;
+    const int nstages = C.stages(WC_STAGE);
     // operand scales of the job (per layer, over all samples) and the scale of its result
-    const int xi = xstat_index(P, l, s);   // (the statistic of this segment, not of the layer's hidden input - see mlp_wgrad_bf16_kernel)
-    const int ex = 14 - (xi < 0 ? 0 : min(max(A.xstat[xi], -100), 100)), ey = 14 - min(max(A.ystat[l], -100), 100);
-    const float sx = __builtin_ldexpf(1.f, ex), sy = __builtin_ldexpf(1.f, ey), unscale = __builtin_ldexpf(1.f, -(ex + ey));
+    const WgradScales S = wgrad_f16_scales(P, A, l, s);
+    const float sx = S.sx, sy = S.sy, unscale = S.unscale;
 
-    // ---- stage loader: this wave brings (and later converts) tile-rows 4*wave .. 4*wave+3 (rows 0..15 = dY, 16..31 =
-    // X); rows the job does not have re-load row 0 of dY (finite filler), so that every wave issues exactly 4 pieces per
-    // stage and one counted vmcnt serves all waves
+    // ---- stage loader: this wave brings (and later converts) tile-rows 4*wave .. 4*wave+3: 4 pieces per stage
     const float *row_src[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r = 4 * wave + q;
-        int64_t grow = L.dy[l];
-        if (r < 16) {
-            if (r < n_rows_y) grow = L.dy[l] + r;
-            row_src[q] = A.dy + grow * n * 16;
-        } else if (r - 16 < n_rows_x) {
-            row_src[q] = A.act + (int64_t)(seg_act_row(P, L, l, s) + 16 * jb + (r - 16)) * n * 16;
-        } else {
-            row_src[q] = A.dy + grow * n * 16;
-        }
-    }
+    wgrad_row_sources<4>(P, L, A.dy, A.act, n, l, s, 0, jb, n_rows_y, n_rows_x, wave, row_src);
     auto issue = [&](int stage) {
         // lane covers 16 B of a piece: position q = lane >> 2 (of 16), feature quad lane & 3; position q of row r holds
         // sample q ^ ((((q >> 3) & 1) << 1) | (r & 1)) (bank swizzle, see above; 4*wave + rr has the parity of rr)
@@ -861,13 +778,13 @@ __global__ __launch_bounds__(WC_THREADS) void mlp_wgrad_f16_kernel(Plan P, Train
     }
     // ---- write the partial of this (block, chunk): the [ti][tj][64 lanes][4] format of mlp_wgrad_kernel ----
     float *part = A.part + (int64_t)blockIdx.y * L.gp_floats + L.gp[l];
-    if (s == first_seg && jb == 0 && wave < 4) {   // bias sums: lane (m32, kg) summed samples 8 kg .. of feature m32
+    if (s == wgrad_bias_seg(Ly) && jb == 0 && wave < 4) {   // bias sums: lane (m32, kg) summed samples 8 kg .. of feature m32
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             float v = bsum[t];
             v += __shfl_xor(v, 32, 64);
             const int feat = 32 * (2 * wave + t) + m32;
-            if (feat < n_rows_y * 16 && lane < 32) part[(int64_t)Ly.t_out * Ly.nkb * 256 + feat] = v;
+            if (feat < n_rows_y * 16 && lane < 32) part[partial_bias_offset(Ly.t_out, Ly.nkb) + feat] = v;
         }
     }
     if (!active) return;
@@ -883,8 +800,8 @@ __global__ __launch_bounds__(WC_THREADS) void mlp_wgrad_f16_kernel(Plan P, Train
                 if (ti >= n_rows_y || tjl >= n_rows_x) continue;
                 const int tj = kb0 + 16 * jb + tjl;
                 const int lane16 = (m32 & 15) + 16 * (2 * (g & 1) + kg);
-                *reinterpret_cast<f4 *>(part + ((int64_t)(ti * Ly.nkb + tj) * 64 + lane16) * 4) =
-                    f4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]} * unscale;
+                store_partial_tile(part, Ly.nkb, ti, tj, lane16,
+                                   f4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]} * unscale);
             }
         }
 }
@@ -923,62 +840,24 @@ int launch_bwd_bf16(const snerf_mlp_desc *desc, const void *packed_t, int nsplit
                     const float *dirs, int dirs_per_sample, int spr, float *d_x, float *d_dirs,
                     snerf_stream_t stream, bool accumulate) {
     Plan P;
-    if (nsplit != 2 && nsplit != 3 && nsplit != SNERF_SPLIT_F16X3)
-        return fail(SNERF_E_BADARG, "mlp_bwd_bf16: nsplit must be 2, 3 or %d (f16x3)", SNERF_SPLIT_F16X3);
-    int rc = plans_t(desc, P, "mlp_bwd_bf16");
-    if (rc) return rc;
-    if (n < 0) return fail(SNERF_E_BADARG, "mlp_bwd_bf16: negative n");
+    int ns, fmt;
+    int rc = split_format("mlp_bwd_bf16", nsplit, &ns, &fmt);
+    if (rc || (rc = plans_t(desc, P, "mlp_bwd_bf16"))) return rc;
+    if ((rc = check_bwd_args("mlp_bwd_bf16", desc, P, packed_t, act, d_raw, n, dy, gpart, flat_grad, x, dirs, spr, d_x, d_dirs, 4, 2))) return rc;
     if (n == 0) return SNERF_OK;
-    if (!packed_t || !act || !d_raw || !dy || !gpart || !flat_grad) return fail(SNERF_E_BADARG, "mlp_bwd_bf16: null pointer");
-    if (!aligned(packed_t, 16) || !aligned(act, 16) || !aligned(d_raw, 16) || !aligned(dy, 16) || !aligned(gpart, 16))
-        return fail(SNERF_E_ALIGN, "mlp_bwd_bf16: buffers must be 16-byte aligned");
     const bool input_grad = d_x != nullptr;
-    if (input_grad) {
-        if (!x || !d_dirs || (desc->use_dir && !dirs) || spr < 1)
-            return fail(SNERF_E_BADARG, "mlp_bwd_bf16: input gradients need x, dirs, d_x, d_dirs");
-        if (P.pos_nkb > 4 || P.dir_nkb > 2)
-            return fail(SNERF_E_BADARG, "mlp_bwd_bf16: input gradients support at most 4 position / 2 direction encoder k-blocks");
-    }
     hipStream_t s = (hipStream_t)stream;
     TrainLayout L;
     make_train_layout(P, L);
-    const int nh = P.n_hidden;
-    BwdArgs A{};
-    A.packed_t = reinterpret_cast<const float *>(packed_t);
-    A.act = act;
-    A.d_raw = d_raw;
-    A.dy = dy;
-    A.n = n;
-    A.n_hidden = nh;
-    A.act_x1 = L.x[1];
-    A.act_h2 = L.h2;
-    A.act_mask = L.mask;
-    A.dy_sig = L.dy[nh + 2];
-    A.dy_din = L.dy[nh + 3];
-    A.dy_dn0 = L.dy[nh + 4];
-    A.dy_rgb = L.dy[nh + 5];
-    A.x = x;
-    A.dirs = dirs;
-    A.d_x = d_x;
-    A.d_dirs = d_dirs;
-    A.dirs_per_sample = dirs_per_sample ? 1 : 0;
-    A.spr = spr < 1 ? 1 : spr;
-    A.skip_mask = desc->skip_mask;
-    A.pos_L = desc->pos_freqs;
-    A.pos_id = desc->pos_identity ? 1 : 0;
-    A.pos_nkb = P.pos_nkb;
-    A.dir_L = desc->dir_freqs;
-    A.dir_id = desc->dir_identity ? 1 : 0;
-    A.dir_nkb = P.dir_nkb;
-    A.use_dir = desc->use_dir ? 1 : 0;
+    BwdArgs A = fill_bwd_args(desc, P, L, reinterpret_cast<const float *>(packed_t), act, d_raw, n, dy, x, dirs, dirs_per_sample, spr,
+                              d_x, d_dirs);
     A.total_slabs = bwd_total_slabs(P, input_grad, 32);
     A.n_tiles = (n + 8 * 16 - 1) / (8 * 16);
     A.dy_rows = L.dy_rows;
-    const bool f16 = nsplit == SNERF_SPLIT_F16X3;
-    if (f16 && hipMemsetAsync(dy + (int64_t)L.dy_rows * n * 16, 0x80, STAT_INTS * sizeof(int), s) != hipSuccess)
+    if (fmt == FMT_F16 && hipMemsetAsync(dy + (int64_t)L.dy_rows * n * 16, 0x80, STAT_INTS * sizeof(int), s) != hipSuccess)
         return fail(SNERF_E_LAUNCH, "mlp_bwd_bf16: cannot reset the layer statistics");
-    if (nsplit == SNERF_SPLIT_F16X3) rc = input_grad ? launch_dgrad_bf16<2, true, FMT_F16>(A, s) : launch_dgrad_bf16<2, false, FMT_F16>(A, s);
-    else if (nsplit == 3) rc = input_grad ? launch_dgrad_bf16<3, true>(A, s) : launch_dgrad_bf16<3, false>(A, s);
+    if (fmt == FMT_F16) rc = input_grad ? launch_dgrad_bf16<2, true, FMT_F16>(A, s) : launch_dgrad_bf16<2, false, FMT_F16>(A, s);
+    else if (ns == 3) rc = input_grad ? launch_dgrad_bf16<3, true>(A, s) : launch_dgrad_bf16<3, false>(A, s);
     else rc = input_grad ? launch_dgrad_bf16<2, true>(A, s) : launch_dgrad_bf16<2, false>(A, s);
     if (rc) return rc;
     // wide jobs on the 16-bit matrix cores in the same format (f16x3: with per-layer scales - a per-sample scale cannot be
@@ -991,26 +870,23 @@ int launch_bwd_bf16(const snerf_mlp_desc *desc, const void *packed_t, int nsplit
 extern "C" int64_t snerf_mlp_packed_t_bf16_bytes(const snerf_mlp_desc *desc, int nsplit, int input_grad) {
     using namespace snerf;
     Plan P;
-    if (nsplit != 2 && nsplit != 3 && nsplit != SNERF_SPLIT_F16X3)
-        return fail(SNERF_E_BADARG, "mlp_packed_t_bf16_bytes: nsplit must be 2, 3 or %d (f16x3)", SNERF_SPLIT_F16X3);
-    int rc = plans_t(desc, P, "mlp_packed_t_bf16_bytes");
-    if (rc) return rc;
-    return (int64_t)(bwd_total_slabs(P, input_grad != 0, 32) + SLAB_PAD) * slab16_bytes(nsplit == SNERF_SPLIT_F16X3 ? 2 : nsplit);
+    int ns;
+    int rc = split_format("mlp_packed_t_bf16_bytes", nsplit, &ns, nullptr);
+    if (rc || (rc = plans_t(desc, P, "mlp_packed_t_bf16_bytes"))) return rc;
+    return (int64_t)(bwd_total_slabs(P, input_grad != 0, 32) + SLAB_PAD) * slab16_bytes(ns);
 }
 
 extern "C" int snerf_mlp_pack_t_bf16(const snerf_mlp_desc *desc, const float *params_flat, void *packed_t, int nsplit,
                                      int input_grad, snerf_stream_t stream) {
     using namespace snerf;
     Plan P;
-    if (nsplit != 2 && nsplit != 3 && nsplit != SNERF_SPLIT_F16X3)
-        return fail(SNERF_E_BADARG, "mlp_pack_t_bf16: nsplit must be 2, 3 or %d (f16x3)", SNERF_SPLIT_F16X3);
-    int rc = plans_t(desc, P, "mlp_pack_t_bf16");
-    if (rc) return rc;
+    int ns, fmt;
+    int rc = split_format("mlp_pack_t_bf16", nsplit, &ns, &fmt);
+    if (rc || (rc = plans_t(desc, P, "mlp_pack_t_bf16"))) return rc;
     if (!params_flat || !packed_t) return fail(SNERF_E_BADARG, "mlp_pack_t_bf16: null pointer");
     if (!aligned(packed_t, 16)) return fail(SNERF_E_ALIGN, "mlp_pack_t_bf16: packed_t must be 16-byte aligned");
     BwdPlan B;
     make_bwd_plan(P, B, input_grad != 0, 32);
-    const int fmt = nsplit == SNERF_SPLIT_F16X3 ? FMT_F16 : FMT_BF16, ns = fmt == FMT_F16 ? 2 : nsplit;
     if (fmt == FMT_F16)
         if ((rc = launch_wexp(P, ns, params_flat, packed_t, B.total_slabs, (hipStream_t)stream, "mlp_pack_t_bf16"))) return rc;
     hipLaunchKernelGGL(mlp_pack_t_bf16_kernel, dim3(B.total_slabs + SLAB_PAD), dim3(256), 0, (hipStream_t)stream, P, B, ns, fmt,
