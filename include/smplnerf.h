@@ -493,6 +493,47 @@ SNERF_API int snerf_smpl_lbs_bwd_f32(const snerf_smpl_model *model, const float 
                               int64_t B, void *workspace, int64_t workspace_bytes, float *d_betas, float *d_body_pose,
                               float *d_global_orient, snerf_stream_t stream);
 
+/* ---- The vertex_sphere model: ray-mesh hits and the sphere warp (datasets/vertex_sphere_dataset.py:84-160) -------------------
+ * All hits of R rays on one triangle mesh.  origins, dirs [R,3]; vertices [V,3]; faces [F,3] int32 indices into vertices;
+ * max_hits = K in 1 .. 16 -> t_hits [R,K], n_hits [R] int32.
+ * Intersection rule: two-sided Moeller-Trumbore in fp32, for triangle (a, b, c) of faces.
+ *   e1 = b - a, e2 = c - a, p = d x e2, det = e1 . p.
+ *   u = (o - a) . p / det, q = (o - a) x e1, v = d . q / det, t = e2 . q / det.
+ *   A hit is det != 0, u >= 0, v >= 0, u + v <= 1, t > 0.
+ *   There is no back-face culling: trimesh's intersector is two-sided.
+ *   t is in units of |d|.  The reference normalises its directions (:79), so t is the distance it computes with
+ *   torch.norm(hit - origin).
+ *   Products and sums are kept apart, as the build already does (-ffp-contract=off); a dot product is (x0 y0 + x1 y1) + x2 y2.
+ * Outputs: t_hits[r, :] holds the K smallest hit parameters in ascending order, padded with +inf.  n_hits[r] is the total number
+ *   of hits.  It may exceed K, and the caller can see that the list was cut.  Every element of both outputs is written.  Two
+ *   calls give the same bits.
+ * Not promised: a ray through a shared edge or vertex may count once or twice, and nothing is pinned relative to trimesh's own
+ *   tolerances.
+ * workspace: snerf_ray_mesh_workspace_bytes(F) bytes (36 F: a, e1, e2 per face, written by a pre-pass of every call); nothing of
+ *   size R F exists in memory.
+ * Argument checks, on the host before any device work: R = 0 is a no-op returning 0, also with null pointers; a bad scalar is an
+ *   error whatever R is.  A required null pointer, max_hits outside 1 .. 16, V < 1, F < 1, 3 V or 9 F or ceil(R/64) not below
+ *   2^31, and a workspace that is missing or too small are SNERF_E_BADARG with a message naming the argument.  Face indices in
+ *   [0, V) are a precondition of this entry (the Python operator rejects a bad table before any launch). */
+SNERF_API int64_t snerf_ray_mesh_workspace_bytes(int F);   /* -1 on a bad F */
+SNERF_API int snerf_ray_mesh_hits_f32(const float *origins, const float *dirs, const float *vertices, const int32_t *faces, int64_t R,
+                              int V, int F, int max_hits, float *t_hits, int32_t *n_hits, void *workspace,
+                              int64_t workspace_bytes, snerf_stream_t stream);
+/* The sphere warp (:128-159).  samples [n,3]; goal, canon [V,3]: ONE body in the goal and in the canonical pose (the data set has
+ * one pose per image).  d_v = sqrtf(|p - g_v|^2), the square summed as (dx^2 + dy^2) + dz^2, and the three-way weight
+ * w(d) = 1 where d < radius, 0 where d > radius, d itself where they are equal (the reference's two masked assignments leave an
+ * equal distance in place).
+ *   by_mean = 0 (:147-158)  i = argmin_v d_v, the lowest index on a tie as torch.argmin; warp = w(d_i) (canon_i - goal_i);
+ *                           nearest = i; count = (d_i < radius)
+ *   by_mean = 1 (:134-145)  warp = sum_v w(d_v) (canon_v - goal_v) / (sum_v w(d_v) + 1e-10), summed in a fixed order;
+ *                           count = the number of vertices with d_v < radius; nearest is still the argmin
+ * -> warp [n,3]; nearest [n], count [n] int32, each nullable.  Every element of a non-NULL output is written; no atomics; two
+ * calls give the same bits.  There is no backward: the warp is data of the batch (data[4]), not differentiated through.
+ * n >= 0 (0: SNERF_OK whatever the pointers are), V >= 1, radius finite and positive, 3 V and ceil(n/64) below 2^31; samples,
+ * goal, canon, warp non-null - else SNERF_E_BADARG before anything touches a device; a bad scalar is an error whatever n is. */
+SNERF_API int snerf_vertex_sphere_warp_f32(const float *samples, const float *goal, const float *canon, int64_t n, int V, float radius,
+                              int by_mean, float *warp, int32_t *nearest, int32_t *count, snerf_stream_t stream);
+
 /* ---- 8(f)-1: on-device ray generation + stratified coarse sampling --------------------------------------
  * Replaces get_rays (utils.py:50-54) + CoarseSampling (datasets/transforms.py:80-89) + ToTensor (:13-21) for a
  * batch of rays.  poses: fp64 [n_frames, 4, 4] camera-to-world; ray_index int64 [B] = frame*H*W + row*W + col;

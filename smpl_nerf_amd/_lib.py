@@ -143,6 +143,10 @@ SIGNATURES = {
     "snerf_smpl_lbs_fwd_f32": (c_int, [POINTER(SmplModel), _P, c_int, _P, _P, c_int64, _P, _P, _P, _P]),
     "snerf_smpl_lbs_bwd_workspace_bytes": (c_int64, [POINTER(SmplModel), c_int64]),
     "snerf_smpl_lbs_bwd_f32": (c_int, [POINTER(SmplModel), _P, c_int, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
+    # the vertex_sphere model: ray-mesh hits (csrc/ray_mesh.hip) and the sphere warp (csrc/vertex_sphere.hip)
+    "snerf_ray_mesh_workspace_bytes": (c_int64, [c_int]),
+    "snerf_ray_mesh_hits_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, c_int64, _P]),
+    "snerf_vertex_sphere_warp_f32": (c_int, [_P, _P, _P, c_int64, c_int, c_float, c_int, _P, _P, _P, _P]),
     "snerf_raygen_f64": (c_int, [_P, c_int64, c_int, c_int, c_double, _P, _P, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "snerf_mlp_fwd_encoded_f32": (c_int, [POINTER(MlpDesc), _P, _P, c_int64, c_int64, _P, _P]),
     "snerf_render_rays_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),

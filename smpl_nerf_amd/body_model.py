@@ -26,19 +26,28 @@ class SmplBodyModel(torch.nn.Module):
 
     The model arrays are buffers in the kernels' layout (so .to() and state_dict() work): v_template [V,3], blend
     [num_betas + 9(J-1), 3V] (shapedirs then posedirs, one row per coefficient), J_template [J,3] and J_dirs [J,3,num_betas]
-    (the joint regressor applied to template and shape directions once, in float64), weights [V,J], parents [J] int32."""
+    (the joint regressor applied to template and shape directions once, in float64), weights [V,J], parents [J] int32.
+    `.faces` is the triangle table [F,3] int32 of the surface (what ops.ray_mesh_hits takes) or None: a non-persistent buffer, so
+    it follows .to() and state_dict() does not list it."""
 
-    def __init__(self, v_template, blend, J_template, J_dirs, weights, parents):
+    def __init__(self, v_template, blend, J_template, J_dirs, weights, parents, faces=None):
         super().__init__()
         for name, a in (("v_template", v_template), ("blend", blend), ("J_template", J_template), ("J_dirs", J_dirs), ("weights", weights)):
             self.register_buffer(name, torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)))
         self.register_buffer("parents", torch.as_tensor(np.ascontiguousarray(parents, dtype=np.int32)))
+        if faces is not None:
+            faces = np.ascontiguousarray(np.asarray(faces).astype(np.int64))
+            if faces.ndim != 2 or faces.shape[1] != 3 or len(faces) < 1 or faces.min() < 0 or faces.max() >= self.v_template.shape[0]:
+                raise ValueError(f"SmplBodyModel: faces must be [F >= 1, 3] indices into the {self.v_template.shape[0]} vertices")
+            faces = torch.as_tensor(faces.astype(np.int32))
+        self.register_buffer("faces", faces, persistent=False)
         self._parents_host = None
 
     @classmethod
-    def from_arrays(cls, v_template, shapedirs, posedirs, J_regressor, weights, parents, num_betas=10):
+    def from_arrays(cls, v_template, shapedirs, posedirs, J_regressor, weights, parents, num_betas=10, faces=None):
         """From the arrays of an SMPL file: v_template [V,3], shapedirs [V,3,>=num_betas], posedirs [V,3,9(J-1)], J_regressor [J,V]
-        (dense or scipy-sparse), weights [V,J], parents [J] (the root's entry is replaced by -1: SMPL files store 2^32 - 1)."""
+        (dense or scipy-sparse), weights [V,J], parents [J] (the root's entry is replaced by -1: SMPL files store 2^32 - 1); faces
+        [F,3] (the files' `f`), optional."""
         v_template, shapedirs, posedirs, weights = (np.asarray(a, np.float64) for a in (v_template, shapedirs, posedirs, weights))
         reg = _dense(J_regressor).astype(np.float64)
         V, J = weights.shape
@@ -54,12 +63,13 @@ class SmplBodyModel(torch.nn.Module):
             raise ValueError("SmplBodyModel: parents must have J entries with parents[j] < j")
         shapedirs = shapedirs[:, :, :num_betas]
         blend = np.concatenate([shapedirs.reshape(3 * V, -1).T, posedirs.reshape(3 * V, -1).T], 0)
-        return cls(v_template, blend, reg @ v_template, np.einsum("jv,vcn->jcn", reg, shapedirs), weights, parents)
+        return cls(v_template, blend, reg @ v_template, np.einsum("jv,vcn->jcn", reg, shapedirs), weights, parents, faces)
 
     @classmethod
     def from_file(cls, path, num_betas=10):
         """An SMPL model file: `.npz` (arrays v_template, shapedirs, posedirs, J_regressor, weights, and kintree_table or parents),
-        or a `.pkl` that unpickles without chumpy (plain numpy arrays, a scipy-sparse J_regressor, kintree_table)."""
+        or a `.pkl` that unpickles without chumpy (plain numpy arrays, a scipy-sparse J_regressor, kintree_table).  The triangle table
+        `f` (or `faces`) is read when present."""
         path = str(path)
         if path.endswith(".npz"):
             d = dict(np.load(path, allow_pickle=False))
@@ -78,7 +88,8 @@ class SmplBodyModel(torch.nn.Module):
         if missing or ("parents" not in d and "kintree_table" not in d):
             raise ValueError(f"{path}: no {missing or ['kintree_table / parents']} in the file")
         parents = d["parents"] if "parents" in d else np.asarray(d["kintree_table"])[0]
-        return cls.from_arrays(d["v_template"], d["shapedirs"], d["posedirs"], d["J_regressor"], d["weights"], parents, num_betas)
+        return cls.from_arrays(d["v_template"], d["shapedirs"], d["posedirs"], d["J_regressor"], d["weights"], parents, num_betas,
+                               faces=d["f"] if "f" in d else d.get("faces"))
 
     num_joints = property(lambda self: self.weights.shape[1])
     num_betas = property(lambda self: self.J_dirs.shape[2])

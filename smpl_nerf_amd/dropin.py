@@ -45,6 +45,7 @@ REPLACEMENTS = {
     "models.append_smpl_params_pipeline": {"AppendSmplParamsPipeline": pipelines.AppendSmplParamsPipeline},
     "models.append_to_nerf_pipeline": {"AppendToNerfPipeline": pipelines.AppendToNerfPipeline},
     "models.dynamic_pipeline": {"DynamicPipeline": pipelines.DynamicPipeline},
+    "models.vertex_sphere_pipeline": {"VertexSpherePipeline": pipelines.VertexSpherePipeline},
 }
 _NAMES = {name: obj for table in REPLACEMENTS.values() for name, obj in table.items()}
 _originals = {}      # name -> the reference's own object (once seen), to recognise `from x import y` copies

@@ -9,6 +9,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     vertex_attention_warp   models/dynamic_pipeline.py:51-70 (the attention warp of DynamicPipeline as one operator)
     GaussianMixture / gaussian_mixture_pdf   utils.py:72-111 (the canonical-density term of SmplNerfSolver's loss)
     smpl_lbs            the body model the reference takes from smplx (train.py:214): SMPL linear blend skinning
+    ray_mesh_hits / vertex_sphere_warp   datasets/vertex_sphere_dataset.py:84-116 (trimesh's intersector) and :128-159 (the true warp)
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -679,3 +680,71 @@ def smpl_lbs(model_buffers, betas, body_pose, global_orient=None):
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (b, p, g)):
         return _SmplLbsFn.apply(model_buffers, b, p, g)
     return _smpl_fwd(model_buffers, b, p, g)[:2]
+
+
+# ------------------------------------------------------------------------------------------------
+# The vertex_sphere model (datasets/vertex_sphere_dataset.py:84-160): ray-mesh hits and the sphere warp
+# ------------------------------------------------------------------------------------------------
+def ray_mesh_hits(origins, directions, vertices, faces, max_hits: int = 1, faces_checked: bool = False):
+    """All hits of R rays on one triangle mesh (csrc/ray_mesh.hip; include/smplnerf.h states the rule: two-sided Moeller-Trumbore in
+    fp32): what the reference asks trimesh's RayMeshIntersector for one ray at a time (:85-89).  origins, directions [R,3] fp32,
+    vertices [V,3] fp32, faces [F,3] int32 -> (t_hits [R,K] fp32: the K = max_hits (1 .. 16) smallest hit parameters in ascending
+    order, padded with +inf, in units of |direction|; n_hits [R] int32: the number of hits, which may exceed K).  The face table
+    is range-checked against V before anything is launched (one device reduction and a host read); faces_checked=True skips
+    that for a table that has been through it.  The workspace (36 F bytes) is allocated here.  Nothing of size R F is built."""
+    # the table's own checks come first and need no device: a bad table is refused wherever it lives
+    if faces.dtype != torch.int32:
+        raise RuntimeError(f"ray_mesh_hits: `faces` must be int32 (got {faces.dtype})")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise RuntimeError(f"ray_mesh_hits: vertices {tuple(vertices.shape)} must be [V >= 1, 3] and faces {tuple(faces.shape)} [F >= 1, 3]")
+    R, V, F, dev = origins.shape[0], vertices.shape[0], faces.shape[0], origins.device
+    if not faces_checked:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= V:
+            raise RuntimeError(f"ray_mesh_hits: faces index vertices {lo} .. {hi}, outside [0, {V})")
+    for nm, t in (("origins", origins), ("directions", directions), ("vertices", vertices)):
+        _need_cuda(nm, t)
+    if not faces.is_cuda:
+        raise RuntimeError(f"smpl_nerf_amd: `faces` must live on the GPU (got {faces.device}); there is no CPU path")
+    if origins.dim() != 2 or origins.shape[1] != 3 or directions.shape != origins.shape:
+        raise RuntimeError(f"ray_mesh_hits: origins {tuple(origins.shape)} and directions {tuple(directions.shape)} must both be [R, 3]")
+    K = int(max_hits)
+    if not 1 <= K <= 16:
+        raise RuntimeError(f"ray_mesh_hits: max_hits must be 1 .. 16, got {max_hits}")
+    o, d, vt, fc = (t.detach().contiguous() for t in (origins, directions, vertices, faces))
+    t_hits = torch.empty((R, K), device=dev, dtype=torch.float32)
+    n_hits = torch.empty((R,), device=dev, dtype=torch.int32)
+    lib = _lib.load()
+    nbytes = lib.snerf_ray_mesh_workspace_bytes(F)
+    if nbytes < 0:
+        check(-1, "snerf_ray_mesh_workspace_bytes")
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev), _lib.timed(f"ray_mesh_hits[F={F},K={K}]"):
+        check(lib.snerf_ray_mesh_hits_f32(ptr(o), ptr(d), ptr(vt), ptr(fc), R, V, F, K, ptr(t_hits), ptr(n_hits), ptr(ws), nbytes,
+                                          current_stream()), "snerf_ray_mesh_hits_f32")
+    return t_hits, n_hits
+
+
+def vertex_sphere_warp(samples, goal, canon, radius, by_mean: bool = False, want_indices: bool = False):
+    """The deterministic warp of the vertex_sphere model (csrc/vertex_sphere.hip; :128-159) in one launch.  samples [..., 3], goal /
+    canon [V,3] (one body in the goal and in the canonical pose) -> warp, shaped like samples: canon_i - goal_i of the nearest goal
+    vertex i where it is closer than `radius`, else zero (by_mean=False), or the mean of canon_v - goal_v over the goal vertices
+    inside the radius (by_mean=True; the reference's 1e-10 in the denominator).  A distance equal to the radius weighs as itself
+    (quirk Q12).  want_indices=True: (warp, nearest [...] int32, count [...] int32) with the argmin vertex and the number of
+    vertices inside the radius (by_mean=False: whether the nearest is).  The outputs are data: no grad_fn, whatever the inputs
+    require.  No [n, V] tensor is built."""
+    for nm, t in (("samples", samples), ("goal", goal), ("canon", canon)):
+        _need_cuda(nm, t)
+    if samples.dim() < 1 or samples.shape[-1] != 3:
+        raise RuntimeError(f"vertex_sphere_warp: samples must be [..., 3], got {tuple(samples.shape)}")
+    if goal.dim() != 2 or goal.shape[1] != 3 or goal.shape[0] < 1 or canon.shape != goal.shape:
+        raise RuntimeError(f"vertex_sphere_warp: goal {tuple(goal.shape)} and canon {tuple(canon.shape)} must both be [V >= 1, 3]")
+    x, g, c = (t.detach().contiguous() for t in (samples, goal, canon))
+    n, V, dev = x.numel() // 3, g.shape[0], x.device
+    warp = torch.empty(samples.shape, device=dev, dtype=torch.float32)
+    nearest, count = ((torch.empty(samples.shape[:-1], device=dev, dtype=torch.int32) for _ in range(2)) if want_indices else (None, None))
+    lib = _lib.load()
+    with torch.cuda.device(dev), _lib.timed(f"vertex_sphere_warp[V={V}]"):
+        check(lib.snerf_vertex_sphere_warp_f32(ptr(x), ptr(g), ptr(c), n, V, float(radius), 1 if by_mean else 0, ptr(warp), ptr(nearest),
+                                               ptr(count), current_stream()), "snerf_vertex_sphere_warp_f32")
+    return (warp, nearest, count) if want_indices else warp

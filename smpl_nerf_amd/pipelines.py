@@ -71,6 +71,11 @@ class PipelineArgs:
         self.strict_cumsum = 0
         self.warp_radius = 0.01          # config_parser.py:47-49: DynamicPipeline's attention radius and temperature
         self.warp_temperature = 10000
+        self.vertex_sphere_radius = 0.01          # config_parser.py:35-45: the vertex_sphere model (vertex_sphere.VertexSphereRays)
+        self.warp_by_vertex_mean = 0
+        self.coarse_samples_from_prior = 0
+        self.coarse_samples_from_intersect = 0
+        self.std_dev_coarse_sample_prior = 0.03
         self.u = None  # optional explicit linspace(0, 1, number_fine_samples) buffer (ops.uniform_u)
         self.__dict__.update(kw)
 
@@ -417,6 +422,35 @@ class DynamicPipeline(NerfPipeline):
         rgb, _, densities = ops.composite(raw.view(B, Nc, 4), z_vals, sdirs.view(B, Nc, 3), bool(args.white_background),
                                           self._noise((B, Nc), dev), want_weights=False)           # :81
         return rgb, rgb, warp.view(B, Nc, 3), ray_samples, warped.view(B, Nc, 3), densities        # :83
+
+
+class VertexSpherePipeline(NerfPipeline):
+    """models/vertex_sphere_pipeline.py:7-50 drop-in: the deterministic-warp ("true warp") model.  The warp is not learned and
+    not computed here: it arrives with the batch, data = [ray_samples, ray_translation, ray_direction, z_vals, warp, rgb_truth]
+    (vertex_sphere.VertexSphereRays computes it from the posed body with ops.vertex_sphere_warp), and a plain NeRF is trained in
+    canonical space.  warped = ray_samples + warp (:28), per-sample view directions warped - o (:31), the coarse net on them and
+    the compositing that scales distances by |warped - o| (:42) - DynamicPipeline's tail.  Returns (rgb, rgb, warp, ray_samples,
+    warped [B,S,3], densities); with args.run_fine the reference's NotImplementedError (:50), raised before any launch."""
+
+    def _single_call_ok(self, data) -> bool:
+        return False      # (no single-call entry takes a warp from the batch)
+
+    def render_rays(self, data):
+        with torch.no_grad():
+            return self._forward_calls(data)
+
+    def _forward_calls(self, data):
+        ray_samples, ray_translation, ray_direction, z_vals, warp, _ = data
+        args = self.args
+        if args.run_fine:
+            raise NotImplementedError('calculating the deterministic/true warp for the fine samples in not implemented yet')   # :50
+        B, Nc = z_vals.shape
+        warped = ray_samples + warp                                                                # :28
+        sdirs = warped - ray_translation[:, None, :]                                               # :31
+        raw = self.model_coarse.forward_fused(warped, sdirs, Nc, self.position_encoder, self.direction_encoder)   # :29-41
+        rgb, _, densities = ops.composite(raw.view(B, Nc, 4), z_vals, sdirs, bool(args.white_background),
+                                          self._noise((B, Nc), ray_samples.device), want_weights=False)           # :42
+        return rgb, rgb, warp, ray_samples, warped, densities                                      # :48
 
 
 class AppendSmplParamsPipeline(NerfPipeline):

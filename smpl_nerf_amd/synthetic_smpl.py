@@ -72,3 +72,70 @@ def random_smpl_arrays(seed: int, n_vertices: int = 6890, n_joints: int = 24, nu
     out["weights"] = wts.astype(f)
     out["parents"] = np.array([SMPL_PARENTS[j] if j < len(SMPL_PARENTS) else j - 1 for j in range(J)], np.int32)
     return out
+
+
+def icosphere(level: int):
+    """The unit icosphere after `level` subdivisions: (vertices [V,3] float64 on the unit sphere, faces [F,3] int32, outward
+    winding) with V = 12 / 42 / 162 / 642 / 2562 and F = 20 / 80 / 320 / 1280 / 5120 for level 0 .. 4.  A closed surface: every edge
+    is shared by exactly two faces."""
+    g = (1.0 + 5.0 ** 0.5) / 2.0
+    verts = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1),
+             (-g, 0, -1), (-g, 0, 1)]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+             (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    verts = [np.asarray(v, np.float64) / np.linalg.norm(v) for v in verts]
+    for _ in range(int(level)):
+        mid, out = {}, []
+
+        def midpoint(a, b):
+            key = (a, b) if a < b else (b, a)
+            if key not in mid:
+                m = verts[a] + verts[b]
+                verts.append(m / np.linalg.norm(m))
+                mid[key] = len(verts) - 1
+            return mid[key]
+
+        for a, b, c in faces:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            out += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = out
+    return np.stack(verts), np.asarray(faces, np.int32)
+
+
+def bumpy_ellipsoid(level: int, seed: int, radii=(0.25, 0.8, 0.2), bump: float = 0.15):
+    """A body-sized closed surface: the icosphere of `level`, its radius modulated by a few low-frequency waves (so that a ray can
+    cross it more than twice) and scaled to an ellipsoid.  (vertices [V,3] float32, faces [F,3] int32)."""
+    rng = np.random.default_rng(seed)
+    v, faces = icosphere(level)
+    freq, phase = rng.integers(2, 5, (3, 3)), rng.uniform(0, 2 * np.pi, 3)
+    r = 1.0 + bump * sum(np.sin((v * freq[k]).sum(-1) * 1.7 + phase[k]) for k in range(3))
+    return (v * r[:, None] * np.asarray(radii)).astype(np.float32), faces
+
+
+SKIN_LENGTH = 0.25      # surface_smpl_arrays: the length over which a vertex's skinning weights change
+
+
+def surface_smpl_arrays(seed: int, level: int = 2, n_joints: int = 24, num_betas: int = 10) -> dict:
+    """A synthetic body that is a surface, with the arrays of an SMPL file plus `faces` (SmplBodyModel.from_arrays takes the dict
+    as keyword arguments): the template is bumpy_ellipsoid(level, seed) - 12 / 42 / 162 / 642 / 2562 vertices - every joint sits
+    half-way between the centroid and a patch of the surface, and the skinning weights are a softmax of minus the distance to
+    the joints over SKIN_LENGTH, so they vary smoothly over the surface and a posed body is still a surface.  Small blend shapes as in
+    random_smpl_arrays."""
+    rng = np.random.default_rng(seed)
+    f = np.float32
+    v, faces = bumpy_ellipsoid(level, seed)
+    V, J = len(v), int(n_joints)
+    v64 = v.astype(np.float64)
+    centre = v64[rng.choice(V, size=J, replace=J > V)]
+    patch = np.exp(-((v64[None] - centre[:, None]) ** 2).sum(-1) / 0.1 ** 2)
+    reg = 0.5 * patch / patch.sum(1, keepdims=True) + 0.5 / V
+    joints = reg @ v64
+    logits = -np.linalg.norm(v64[:, None] - joints[None], axis=-1) / SKIN_LENGTH
+    wts = np.exp(logits - logits.max(1, keepdims=True))
+    return {"v_template": v,
+            "shapedirs": rng.normal(0, 0.01, (V, 3, num_betas)).astype(f),
+            "posedirs": rng.normal(0, 0.003, (V, 3, 9 * (J - 1))).astype(f),
+            "J_regressor": reg.astype(f),
+            "weights": (wts / wts.sum(1, keepdims=True)).astype(f),
+            "parents": np.array([SMPL_PARENTS[j] if j < len(SMPL_PARENTS) else j - 1 for j in range(J)], np.int32),
+            "faces": faces}
