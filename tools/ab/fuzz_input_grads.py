@@ -1,7 +1,8 @@
 """Randomised sweep of the input-gradient contractions (snerf_dy_contract_f32 behind nets._extra_input_grads): d loss / d goal_pose of
 the pose-conditioned pipelines (per-ray additional inputs, raw or encoded, 2 / 69 / 1380 columns) and d loss / d encoded rows
 of RenderRayNet.forward, against CPU torch autograd on the restatement of the reference.  Random depth / width / skips / ray
-and sample counts.  Not part of the suite.
+and sample counts.  Not part of the suite: the suite's own check of the kernel, path by path against float64, is
+tests/test_gpu_contract.py.
 
     python tools/ab/fuzz_input_grads.py [cases] [seed]
 """
