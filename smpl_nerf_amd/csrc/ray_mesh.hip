@@ -6,7 +6,7 @@
 //
 // Mapping: a pre-pass writes (a, e1, e2) per face into the workspace (36 F bytes, once per call).  Main kernel: workgroup = 64-ray
 // chunk, lane = ray; its 8 waves split the faces and read the nine floats of a face at wave-uniform addresses (through the scalar
-// cache: one load per wave, not per lane), four faces per wait, as vw_walk of vertex_warp.hip does with vertices.  Each lane keeps
+// cache: one load per wave, not per lane), four faces per wait: the walk of pair_walk.h.  Each lane keeps
 // its K smallest t as a sorted register list plus a count; the per-wave lists meet in LDS and wave 0 merges them in wave order.
 // Nothing of size R F exists in memory; no atomics; the K smallest of a set do not depend on the order: two calls give the same bits.
 //
@@ -16,7 +16,7 @@
 // by 1e-5 so that it never decides: the decision is taken on the divided values.
 #include <math.h>
 
-#include "snerf_common.h"
+#include "pair_walk.h"
 
 namespace snerf {
 
@@ -62,14 +62,13 @@ template <int KC>
 __global__ __launch_bounds__(RM_WAVES * 64) void ray_mesh_hits_kernel(RmArgs A) {
     __shared__ float part[RM_WAVES][KC][WAVE];
     __shared__ int cnt[RM_WAVES][WAVE];
-    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = lane_id(), wave = wave_index();
     const int64_t r = (int64_t)blockIdx.x * WAVE + lane;
     const bool valid = r < A.R;
-    const int64_t rr = valid ? r : A.R - 1;
+    const int64_t rr = tail_index(r, A.R, valid);
     const float ox = A.origins[rr * 3 + 0], oy = A.origins[rr * 3 + 1], oz = A.origins[rr * 3 + 2];
     const float dx = A.dirs[rr * 3 + 0], dy = A.dirs[rr * 3 + 1], dz = A.dirs[rr * 3 + 2];
-    const int per = (A.F + RM_WAVES - 1) / RM_WAVES;
-    const int f0 = wave * per, f1 = f0 + per < A.F ? f0 + per : A.F;
+    const Slice sl = wave_slice(A.F, RM_WAVES, wave);
     float list[KC];
 #pragma unroll
     for (int i = 0; i < KC; ++i) list[i] = INFINITY;
@@ -98,20 +97,14 @@ __global__ __launch_bounds__(RM_WAVES * 64) void ray_mesh_hits_kernel(RmArgs A) 
         }
     };
 
-    int f = f0;
-    for (; f + 4 <= f1; f += 4) {
-        float T[36];
+    // (the walk indexes tri in 32 bits: the host refuses 9 F at 2^31 and above)
+    walk4<9>(
+        A.tri, sl.lo, sl.hi,
+        [&](int, const float *T) {
 #pragma unroll
-        for (int i = 0; i < 36; ++i) T[i] = A.tri[(int64_t)f * 9 + i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pair(T + 9 * j);
-    }
-    for (; f < f1; ++f) {
-        float T[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) T[i] = A.tri[(int64_t)f * 9 + i];
-        pair(T);
-    }
+            for (int j = 0; j < 4; ++j) pair(T + 9 * j);
+        },
+        [&](int, const float *T) { pair(T); });
 
 #pragma unroll
     for (int i = 0; i < KC; ++i) part[wave][i][lane] = list[i];
@@ -138,10 +131,7 @@ static void rm_launch(const RmArgs &A, unsigned blocks, hipStream_t s) {
 
 extern "C" int64_t snerf_ray_mesh_workspace_bytes(int F) {
     using namespace snerf;
-    if (F < 1 || (int64_t)F * 9 > 0x7fffffffLL) {
-        fail(SNERF_E_BADARG, "ray_mesh_workspace_bytes: F must be at least 1 and 9 F below 2^31");
-        return -1;
-    }
+    if (check_walk_count("ray_mesh_workspace_bytes", "F", F, 9)) return -1;
     return (int64_t)F * 9 * (int64_t)sizeof(float);
 }
 
@@ -151,15 +141,15 @@ extern "C" int snerf_ray_mesh_hits_f32(const float *origins, const float *dirs, 
     using namespace snerf;
     if (R < 0) return fail(SNERF_E_BADARG, "ray_mesh_hits: R must not be negative");
     if (max_hits < 1 || max_hits > RM_MAX_HITS) return fail(SNERF_E_BADARG, "ray_mesh_hits: max_hits must be 1 .. %d", RM_MAX_HITS);
-    if (V < 1 || (int64_t)V * 3 > 0x7fffffffLL) return fail(SNERF_E_BADARG, "ray_mesh_hits: V must be at least 1 and 3 V below 2^31");
-    if (F < 1 || (int64_t)F * 9 > 0x7fffffffLL) return fail(SNERF_E_BADARG, "ray_mesh_hits: F must be at least 1 and 9 F below 2^31");
+    if (int rc = check_walk_count("ray_mesh_hits", "V", V, 3)) return rc;
+    if (int rc = check_walk_count("ray_mesh_hits", "F", F, 9)) return rc;
     if (R == 0) return SNERF_OK;
     if (!origins || !dirs || !vertices || !faces || !t_hits || !n_hits)
         return fail(SNERF_E_BADARG, "ray_mesh_hits: null pointer (origins, dirs, vertices, faces, t_hits, n_hits)");
     if (!workspace || workspace_bytes < (int64_t)F * 9 * (int64_t)sizeof(float))
         return fail(SNERF_E_BADARG, "ray_mesh_hits: workspace missing or smaller than snerf_ray_mesh_workspace_bytes()");
-    const int64_t blocks = (R + WAVE - 1) / WAVE;
-    if (blocks > 0x7fffffffLL) return fail(SNERF_E_BADARG, "ray_mesh_hits: R too large");
+    int64_t blocks;
+    if (int rc = chunk_blocks("ray_mesh_hits", "R", R, blocks)) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *tri = (float *)workspace;
     hipLaunchKernelGGL(ray_mesh_faces_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, vertices, faces, F, tri);

@@ -7,15 +7,15 @@
 //   by_mean = 1 (:134-145)   warp = sum_v w(d_v) (c_v - g_v) / (sum_v w(d_v) + 1e-10)    count = #{v: d_v < r}     nearest = argmin
 // The warp is data of the batch (data[4]), not a function the loss is differentiated through: there is no backward.
 //
-// Mapping (vw_walk of vertex_warp.hip): workgroup = 64-sample chunk, lane = sample; its 16 waves split the vertices and read them at
-// wave-uniform addresses through the scalar cache, four per wait.  A pair costs the squared distance and one test (VALU-bound, about
-// 10 instructions); the square root is taken only where the squared distance is below the smallest seen so far (the argmin is
-// decided on the roots: two squares can share a root, and then the lower index keeps it) or below a threshold a little above r^2
-// (the weight is decided on the root).  The per-wave partials meet in LDS and wave 0 combines them in wave order: the sums run in
-// a fixed order, no atomics, two calls give the same bits.
+// Mapping (pair_walk.h; the four-per-wait loop is written out here, see the kernel): workgroup = 64-sample chunk, lane = sample; its
+// 16 waves split the vertices and read them at wave-uniform addresses through the scalar cache, four per wait.  A pair costs the
+// squared distance and one test (VALU-bound, about 10 instructions); the square root is taken only where the squared distance is
+// below the smallest seen so far (the argmin is decided on the roots: two squares can share a root, and then the lower index keeps
+// it) or below a threshold a little above r^2 (the weight is decided on the root).  The per-wave partials meet in LDS and wave 0
+// combines them in wave order: the sums run in a fixed order, no atomics, two calls give the same bits.
 #include <math.h>
 
-#include "snerf_common.h"
+#include "pair_walk.h"
 
 namespace snerf {
 
@@ -33,16 +33,15 @@ struct VsArgs {
 template <bool MEAN>
 __global__ __launch_bounds__(VS_WAVES * 64) void vertex_sphere_warp_kernel(VsArgs A) {
     __shared__ float part[VS_WAVES][MEAN ? 7 : 2][WAVE];   // best d, best index; count, sum of weights, numerator xyz
-    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = lane_id(), wave = wave_index();
     const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
     const bool valid = i < A.n;
-    const int64_t ii = valid ? i : A.n - 1;
+    const int64_t ii = tail_index(i, A.n, valid);
     const float px = A.samples[ii * 3 + 0], py = A.samples[ii * 3 + 1], pz = A.samples[ii * 3 + 2];
     const float *g = A.goal, *c = A.canon;
-    const int per = (A.V + VS_WAVES - 1) / VS_WAVES;
-    const int v0 = wave * per, v1 = v0 + per < A.V ? v0 + per : A.V;
+    const Slice sl = wave_slice(A.V, VS_WAVES, wave);
     float best_d2 = INFINITY, best_d = INFINITY, cnt = 0.f, sw = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
-    int best_i = v0 < A.V ? v0 : 0;
+    int best_i = sl.lo < A.V ? sl.lo : 0;   // (an empty slice: a vertex that exists; its best_d = inf never wins)
 
     auto vertex = [&](int v, float gx, float gy, float gz, float d2) {
         if (d2 < best_d2) {   // a smaller square: its root is smaller or the same, and only a smaller one takes the place
@@ -64,37 +63,28 @@ __global__ __launch_bounds__(VS_WAVES * 64) void vertex_sphere_warp_kernel(VsArg
         }
     };
 
-    int v = v0;
-    for (; v + 4 <= v1; v += 4) {
+    // Its own four-per-wait loop, not walk4: with the test of four in a lambda the mean-mode kernel measured 1.0 % slower on an MI355X.
+    int v = sl.lo;
+    for (; v + 4 <= sl.hi; v += 4) {
         float t[12], d2[4];
 #pragma unroll
         for (int k = 0; k < 12; ++k) t[k] = g[v * 3 + k];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float dx = px - t[3 * j], dy = py - t[3 * j + 1], dz = pz - t[3 * j + 2];
-            d2[j] = dx * dx + dy * dy + dz * dz;
-        }
-        const float m = fminf(fminf(d2[0], d2[1]), fminf(d2[2], d2[3]));
+        for (int j = 0; j < 4; ++j) d2[j] = dist2(px - t[3 * j], py - t[3 * j + 1], pz - t[3 * j + 2]);
+        const float m = fminf(fminf(d2[0], d2[1]), fminf(d2[2], d2[3]));   // one test of four: the running minimum or the weight's threshold
         if (m < best_d2 || (MEAN && m < A.r2_test)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) vertex(v + j, t[3 * j], t[3 * j + 1], t[3 * j + 2], d2[j]);
         }
     }
-    for (; v < v1; ++v) {
+    for (; v < sl.hi; ++v) {
         const float gx = g[v * 3 + 0], gy = g[v * 3 + 1], gz = g[v * 3 + 2];
-        const float dx = px - gx, dy = py - gy, dz = pz - gz;
-        vertex(v, gx, gy, gz, dx * dx + dy * dy + dz * dz);
+        vertex(v, gx, gy, gz, dist2(px - gx, py - gy, pz - gz));
     }
 
-    part[wave][0][lane] = best_d;
-    part[wave][1][lane] = __builtin_bit_cast(float, best_i);
-    if (MEAN) {
-        part[wave][2][lane] = cnt;
-        part[wave][3][lane] = sw;
-        part[wave][4][lane] = n0;
-        part[wave][5][lane] = n1;
-        part[wave][6][lane] = n2;
-    }
+    const float best_bits = __builtin_bit_cast(float, best_i);
+    if constexpr (MEAN) put_partials(part[wave], lane, best_d, best_bits, cnt, sw, n0, n1, n2);
+    else put_partials(part[wave], lane, best_d, best_bits);
     __syncthreads();
     if (wave != 0 || !valid) return;
     for (int w = 1; w < VS_WAVES; ++w) {   // in wave order = in vertex order: the lowest index keeps a tie
@@ -134,15 +124,13 @@ extern "C" int snerf_vertex_sphere_warp_f32(const float *samples, const float *g
                                             int by_mean, float *warp, int32_t *nearest, int32_t *count, snerf_stream_t stream) {
     using namespace snerf;
     if (n < 0) return fail(SNERF_E_BADARG, "vertex_sphere_warp: n must not be negative");
-    if (V < 1 || (int64_t)V * 3 > 0x7fffffffLL) return fail(SNERF_E_BADARG, "vertex_sphere_warp: V must be at least 1 and 3 V below 2^31");
+    if (int rc = check_walk_count("vertex_sphere_warp", "V", V, 3)) return rc;
     if (!(radius > 0.f) || !(radius <= 3.4028234663852886e38f)) return fail(SNERF_E_BADARG, "vertex_sphere_warp: radius must be finite and positive");
     if (n == 0) return SNERF_OK;
     if (!samples || !goal || !canon || !warp) return fail(SNERF_E_BADARG, "vertex_sphere_warp: null pointer (samples, goal, canon, warp)");
-    const int64_t blocks = (n + WAVE - 1) / WAVE;
-    if (blocks > 0x7fffffffLL) return fail(SNERF_E_BADARG, "vertex_sphere_warp: n too large");
-    // the weight test's threshold: above r^2 by more than the roundings of d^2 and of the square root can move a pair
-    const float r2_test = (float)((double)radius * (double)radius * (1.0 + 1e-6));
-    VsArgs A{samples, goal, canon, warp, nearest, count, n, V, radius, r2_test};
+    int64_t blocks;
+    if (int rc = chunk_blocks("vertex_sphere_warp", "n", n, blocks)) return rc;
+    VsArgs A{samples, goal, canon, warp, nearest, count, n, V, radius, pair_r2_test(radius)};
     hipStream_t s = (hipStream_t)stream;
     if (by_mean) hipLaunchKernelGGL(vertex_sphere_warp_kernel<true>, dim3((unsigned)blocks), dim3(VS_WAVES * 64), 0, s, A);
     else hipLaunchKernelGGL(vertex_sphere_warp_kernel<false>, dim3((unsigned)blocks), dim3(VS_WAVES * 64), 0, s, A);

@@ -7,8 +7,7 @@
 // rare: the radius is 1 cm on a 2 m body) ever meet sqrt or exp.  All other pairs cost the distance test: three subtractions,
 // three products, two sums, one compare (VALU-bound, 9 instructions per pair).
 //
-// Mapping, all three kernels: lane = sample, a wave walks vertices at wave-uniform addresses (the compiler reads them through
-// the scalar cache: one load per wave, not per lane).
+// Mapping, all three kernels: lane = sample, a wave walks vertices with the walk of pair_walk.h.
 //   forward          workgroup = (ray, 64-sample chunk); its 16 waves split the vertices, each keeps an online (m, sum, numerator)
 //                    per lane; the partials meet in LDS and wave 0 combines them in wave order.  A 64-ray batch is 64 x 16 waves.
 //   backward, verts  a wave owns 64 consecutive vertices of a ray and loops over the sample chunks; a vertex with a hit is summed
@@ -16,7 +15,7 @@
 //                    the tile is written once, zeros included.  No atomics, no read-modify-write of global memory.
 //   backward, samples  as the forward: workgroup = (ray, chunk), partial sums over vertex slices combined in LDS in wave order.
 // Two calls give the same bits.  The backward reads m, Z and warp from the forward, so it is one pass per output.
-#include "snerf_common.h"
+#include "pair_walk.h"
 
 namespace snerf {
 
@@ -37,39 +36,32 @@ struct VwBwdArgs {
     float radius, temperature, r2_test;
 };
 
-__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-
-// |p - g|^2 in the order ((dx dx + dy dy) + dz dz); the build keeps products and sums apart (-ffp-contract=off)
-__device__ __forceinline__ float dist2(float dx, float dy, float dz) { return dx * dx + dy * dy + dz * dz; }
-
-// f(v, gx, gy, gz, dx, dy, dz, d2) for the vertices [v0, v1) of g that can matter to the sample (px, py, pz), four at a time: their
-// twelve floats are requested together (a wave waits for the scalar cache once per four vertices), the four squared distances share
-// ONE test against r2, and f - which decides per vertex - runs for all four when any is below it.  WAVE_UNIFORM: when any lane's is.
+// f(v, gx, gy, gz, dx, dy, dz, d2) for the vertices [v0, v1) of g that can matter to the sample (px, py, pz): walk4 hands them over
+// four at a time, the four squared distances share ONE test against r2, and f - which decides per vertex - runs for all four when
+// any is below it (WAVE_UNIFORM: when any lane's is) and for each of the last 0 .. 3 vertices.
 template <bool WAVE_UNIFORM, class F>
 __device__ __forceinline__ void vw_walk(const float *g, int v0, int v1, float px, float py, float pz, float r2, F &&f) {
-    int v = v0;
-    for (; v + 4 <= v1; v += 4) {
-        float t[12], dx[4], dy[4], dz[4], d2[4];
+    walk4<3>(
+        g, v0, v1,
+        [&](int v, const float *t) {
+            float dx[4], dy[4], dz[4], d2[4];
 #pragma unroll
-        for (int i = 0; i < 12; ++i) t[i] = g[v * 3 + i];
+            for (int j = 0; j < 4; ++j) {
+                dx[j] = px - t[3 * j];
+                dy[j] = py - t[3 * j + 1];
+                dz[j] = pz - t[3 * j + 2];
+                d2[j] = dist2(dx[j], dy[j], dz[j]);
+            }
+            const bool any = fminf(fminf(d2[0], d2[1]), fminf(d2[2], d2[3])) < r2;
+            if (WAVE_UNIFORM ? __builtin_amdgcn_ballot_w64(any) != 0 : any) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            dx[j] = px - t[3 * j];
-            dy[j] = py - t[3 * j + 1];
-            dz[j] = pz - t[3 * j + 2];
-            d2[j] = dist2(dx[j], dy[j], dz[j]);
-        }
-        const bool any = fminf(fminf(d2[0], d2[1]), fminf(d2[2], d2[3])) < r2;
-        if (WAVE_UNIFORM ? __builtin_amdgcn_ballot_w64(any) != 0 : any) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) f(v + j, t[3 * j], t[3 * j + 1], t[3 * j + 2], dx[j], dy[j], dz[j], d2[j]);
-        }
-    }
-    for (; v < v1; ++v) {
-        const float gx = g[v * 3 + 0], gy = g[v * 3 + 1], gz = g[v * 3 + 2];
-        const float dx = px - gx, dy = py - gy, dz = pz - gz;
-        f(v, gx, gy, gz, dx, dy, dz, dist2(dx, dy, dz));
-    }
+                for (int j = 0; j < 4; ++j) f(v + j, t[3 * j], t[3 * j + 1], t[3 * j + 2], dx[j], dy[j], dz[j], d2[j]);
+            }
+        },
+        [&](int v, const float *t) {
+            const float dx = px - t[0], dy = py - t[1], dz = pz - t[2];
+            f(v, t[0], t[1], t[2], dx, dy, dz, dist2(dx, dy, dz));
+        });
 }
 
 __global__ __launch_bounds__(VW_WAVES * 64) void vertex_warp_fwd_kernel(VwArgs A) {
@@ -79,13 +71,12 @@ __global__ __launch_bounds__(VW_WAVES * 64) void vertex_warp_fwd_kernel(VwArgs A
     const int chunk = (int)(blockIdx.x - ray * A.chunks);
     const int s = chunk * WAVE + lane;
     const bool valid = s < A.S;
-    const int64_t sample = ray * A.S + (valid ? s : A.S - 1);
+    const int64_t sample = ray * A.S + tail_index(s, A.S, valid);
     const float px = A.samples[sample * 3 + 0], py = A.samples[sample * 3 + 1], pz = A.samples[sample * 3 + 2];
     const float *g = A.goal + ray * A.V * 3, *c = A.canon + ray * A.V * 3;
-    const int per = (A.V + VW_WAVES - 1) / VW_WAVES;
-    const int v0 = wave * per, v1 = v0 + per < A.V ? v0 + per : A.V;
+    const Slice sl = wave_slice(A.V, VW_WAVES, wave);
     float m = 0.f, sum = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f, hits = 0.f;
-    vw_walk<false>(g, v0, v1, px, py, pz, A.r2_test, [&](int v, float gx, float gy, float gz, float, float, float, float d2) {
+    vw_walk<false>(g, sl.lo, sl.hi, px, py, pz, A.r2_test, [&](int v, float gx, float gy, float gz, float, float, float, float d2) {
         if (d2 < A.r2_test) {   // (r2_test is a little above r^2: the exact decision is the one below)
             const float xr = A.radius - sqrtf(d2);
             if (xr > 0.f) {
@@ -107,12 +98,7 @@ __global__ __launch_bounds__(VW_WAVES * 64) void vertex_warp_fwd_kernel(VwArgs A
             }
         }
     });
-    part[wave][0][lane] = m;
-    part[wave][1][lane] = sum;
-    part[wave][2][lane] = hits;
-    part[wave][3][lane] = n0;
-    part[wave][4][lane] = n1;
-    part[wave][5][lane] = n2;
+    put_partials(part[wave], lane, m, sum, hits, n0, n1, n2);
     __syncthreads();
     if (wave != 0) return;
     float M = 0.f;
@@ -189,7 +175,7 @@ __global__ __launch_bounds__(VW_BWD_WAVES * 64) void vertex_warp_bwd_vertices_ke
     for (int chunk = 0; chunk < A.chunks; ++chunk) {
         const int s = chunk * WAVE + lane;
         const bool valid = s < A.S;
-        const VwSample q = vw_load_sample(A, ray * A.S + (valid ? s : A.S - 1));
+        const VwSample q = vw_load_sample(A, ray * A.S + tail_index(s, A.S, valid));
         vw_walk<true>(g, 0, nv, q.px, q.py, q.pz, A.r2_test, [&](int vi, float gx, float gy, float gz, float dx, float dy, float dz, float d2) {
             const bool near = valid && d2 < A.r2_test;
             if (__builtin_amdgcn_ballot_w64(near) == 0) return;   // wave-uniform
@@ -235,13 +221,12 @@ __global__ __launch_bounds__(VW_WAVES * 64) void vertex_warp_bwd_samples_kernel(
     const int chunk = (int)(blockIdx.x - ray * A.chunks);
     const int s = chunk * WAVE + lane;
     const bool valid = s < A.S;
-    const int64_t sample = ray * A.S + (valid ? s : A.S - 1);
+    const int64_t sample = ray * A.S + tail_index(s, A.S, valid);
     const VwSample q = vw_load_sample(A, sample);
     const float *g = A.goal + ray * A.V * 3, *c = A.canon + ray * A.V * 3;
-    const int per = (A.V + VW_WAVES - 1) / VW_WAVES;
-    const int v0 = wave * per, v1 = v0 + per < A.V ? v0 + per : A.V;
+    const Slice sl = wave_slice(A.V, VW_WAVES, wave);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    vw_walk<false>(g, v0, v1, q.px, q.py, q.pz, A.r2_test, [&](int v, float gx, float gy, float gz, float dx, float dy, float dz, float d2) {
+    vw_walk<false>(g, sl.lo, sl.hi, q.px, q.py, q.pz, A.r2_test, [&](int v, float gx, float gy, float gz, float dx, float dy, float dz, float d2) {
         if (d2 < A.r2_test) {
             const float d = sqrtf(d2), xr = A.radius - d;
             if (xr > 0.f && d > 0.f) {
@@ -255,9 +240,7 @@ __global__ __launch_bounds__(VW_WAVES * 64) void vertex_warp_bwd_samples_kernel(
             }
         }
     });
-    part[wave][0][lane] = s0;
-    part[wave][1][lane] = s1;
-    part[wave][2][lane] = s2;
+    put_partials(part[wave], lane, s0, s1, s2);
     __syncthreads();
     if (wave != 0 || !valid) return;
     float r0 = 0.f, r1 = 0.f, r2 = 0.f;
@@ -278,11 +261,9 @@ static int vw_check(const char *what, int64_t B, int S, int V, float radius, flo
     if (!(radius > 0.f)) return fail(SNERF_E_BADARG, "%s: radius must be positive", what);
     if (!(temperature >= 0.f)) return fail(SNERF_E_BADARG, "%s: temperature must not be negative", what);
     chunks = ((int64_t)S + WAVE - 1) / WAVE;
-    if ((int64_t)V * 3 > 0x7fffffffLL) return fail(SNERF_E_BADARG, "%s: V too large", what);
+    if (int rc = check_walk_count(what, "V", V, 3)) return rc;
     return B == 0 ? 1 : 0;
 }
-// the distance test's threshold: above r^2 by more than the roundings of d^2 and of the square root can move a pair
-static float vw_r2_test(float radius) { return (float)((double)radius * (double)radius * (1.0 + 1e-6)); }
 
 }  // namespace snerf
 
@@ -294,7 +275,7 @@ extern "C" int snerf_vertex_warp_fwd_f32(const float *samples, const float *goal
     if (int rc = vw_check("vertex_warp_fwd", B, S, V, radius, temperature, chunks)) return rc < 0 ? rc : SNERF_OK;
     if (!samples || !goal || !canon || !ray_o || !warp || !warped || !sdirs) return fail(SNERF_E_BADARG, "vertex_warp_fwd: null pointer");
     if (B * chunks > 0x7fffffffLL) return fail(SNERF_E_BADARG, "vertex_warp_fwd: B too large");
-    VwArgs A{samples, goal, canon, ray_o, warp, warped, sdirs, stats, S, V, (int)chunks, radius, temperature, vw_r2_test(radius)};
+    VwArgs A{samples, goal, canon, ray_o, warp, warped, sdirs, stats, S, V, (int)chunks, radius, temperature, pair_r2_test(radius)};
     hipLaunchKernelGGL(vertex_warp_fwd_kernel, dim3((unsigned)(B * chunks)), dim3(VW_WAVES * 64), 0, (hipStream_t)stream, A);
     return check_launch("vertex_warp_fwd");
 }
@@ -311,7 +292,7 @@ extern "C" int snerf_vertex_warp_bwd_f32(const float *samples, const float *goal
     const int64_t groups = ((int64_t)V + VW_BWD_WAVES * WAVE - 1) / (VW_BWD_WAVES * WAVE);
     if (B * chunks > 0x7fffffffLL || B * groups > 0x7fffffffLL) return fail(SNERF_E_BADARG, "vertex_warp_bwd: B too large");
     VwBwdArgs A{samples, goal, canon, warp, stats, d_warp, d_warped, d_sdirs, d_samples, d_goal, d_canon, S, V, (int)chunks, (int)groups,
-                radius, temperature, vw_r2_test(radius)};
+                radius, temperature, pair_r2_test(radius)};
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(vertex_warp_bwd_vertices_kernel, dim3((unsigned)(B * groups)), dim3(VW_BWD_WAVES * 64), 0, s, A);
     if (d_samples) hipLaunchKernelGGL(vertex_warp_bwd_samples_kernel, dim3((unsigned)(B * chunks)), dim3(VW_WAVES * 64), 0, s, A);
