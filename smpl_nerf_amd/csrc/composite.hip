@@ -142,7 +142,7 @@ __global__ __launch_bounds__(CP_THREADS) void composite_bwd_kernel(
         ray_norm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
     }
     float delta = 0.f, nrm = 0.f;  // of the sample last evaluated by this lane
-    auto sample = [&](int i, float4 &r, float &a, float &om, float &dist, float &sig, float &ex) {
+    auto sample = [&](int i, float4 &r, float &a, double &om, float &dist, float &sig, float &ex) {
         r = raw[base + i];
         const float zi = z[base + i];
         nrm = ray_norm;
@@ -153,9 +153,11 @@ __global__ __launch_bounds__(CP_THREADS) void composite_bwd_kernel(
         delta = (i + 1 < N) ? __fsub_rn(z[base + i + 1], zi) : 1e10f;
         dist = __fmul_rn(delta, nrm);
         sig = noise ? __fadd_rn(r.w, noise[base + i]) : r.w;
-        ex = expf(__fmul_rn(-fmaxf(sig, 0.f), dist));
+        // exp in double, rounded once: expf's error has a mean of about a tenth of an ulp on the device, which 1 - a = ex carries
+        // into the transmittance once per live sample (1.3e-5 of T after 4096 samples, against 8e-7 from unbiased rounding)
+        ex = (float)exp((double)__fmul_rn(-fmaxf(sig, 0.f), dist));
         a = __fsub_rn(1.0f, ex);
-        om = __fadd_rn(__fsub_rn(1.0f, a), 1e-10f);
+        om = (double)__fsub_rn(1.0f, a) + 1e-10;   // (in double: fp32 drops the 1e-10 wherever alpha is not 1)
     };
     // forward sweep: transmittance carried into each chunk
     const int nchunk = (N + WAVE - 1) / WAVE;
@@ -163,27 +165,28 @@ __global__ __launch_bounds__(CP_THREADS) void composite_bwd_kernel(
     for (int c = 0; c < nchunk; ++c) {
         if (lane == 0) s_carry[wave][c] = carry;
         const int i = c * WAVE + lane;
-        float om = 1.0f;
+        double om = 1.0;
         if (i < N) {
             float4 r;
             float a, dist, sig, ex;
             sample(i, r, a, om, dist, sig, ex);
         }
-        const double incl = wave_scan_mul((double)om);
+        const double incl = wave_scan_mul(om);
         carry *= wave_last(incl);
     }
     const float gsum = white_bg ? (gr + gg + gb) : 0.f;
     // reverse sweep
     double suffix = 0.0;   // sum_{i > last sample of this chunk} G_i * w_i
-    float ray_dd = 0.f;    // sum_i d dist_i * delta_i (ray-direction gradient)
+    double ray_dd = 0.0;   // sum_i d dist_i * delta_i (ray-direction gradient): terms of both signs, 10 to 1000 times their sum
     float z_pend = 0.f;    // lane 0: -e_i of the first sample of the chunk processed last, waiting for e_{i-1}
     for (int c = nchunk - 1; c >= 0; --c) {
         const int i = c * WAVE + lane;
         const bool ok = i < N;
         float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-        float a = 0.f, om = 1.0f, dist = 0.f, sig = 0.f, ex = 1.0f;
+        float a = 0.f, dist = 0.f, sig = 0.f, ex = 1.0f;
+        double om = 1.0;
         if (ok) sample(i, r, a, om, dist, sig, ex);
-        const double incl = wave_scan_mul((double)om);
+        const double incl = wave_scan_mul(om);
         const double excl = wave_shift_up1(incl, 1.0);
         const float T = (float)(s_carry[wave][c] * excl);
         const float w = a * T;
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(CP_THREADS) void composite_bwd_kernel(
         suffix += __shfl(incl_rev, 0, 64);
         float e = 0.f;   // d loss / d delta_i = d dist_i * |dir_i|
         if (ok) {
-            float da = dw * T - (float)(after / (double)om);
+            float da = dw * T - (float)(after / om);
             if (d_a) da += d_a[base + i];
             const float dsig = sig > 0.f ? da * dist * ex : 0.f;  // ex = exp(-relu(sigma) dist)
             d_raw[base + i] = make_float4(w * gr * cr * (1.f - cr), w * gg * cg * (1.f - cg), w * gb * cb * (1.f - cb), dsig);
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(CP_THREADS) void composite_bwd_kernel(
                     q3[1] = s * dp[1];
                     q3[2] = s * dp[2];
                 } else {
-                    ray_dd += ddist * delta;
+                    ray_dd += (double)ddist * (double)delta;
                 }
             }
         }
@@ -234,8 +237,8 @@ __global__ __launch_bounds__(CP_THREADS) void composite_bwd_kernel(
         }
     }
     if (d_dirs && !dirs_per_sample) {
-        ray_dd = wave_sum(ray_dd);
-        if (lane < 3) d_dirs[ray * 3 + lane] = ray_norm > 0.f ? ray_dd / ray_norm * dirs[ray * 3 + lane] : 0.f;
+        const float dd = (float)wave_sum(ray_dd);
+        if (lane < 3) d_dirs[ray * 3 + lane] = ray_norm > 0.f ? dd / ray_norm * dirs[ray * 3 + lane] : 0.f;
     }
 }
 
