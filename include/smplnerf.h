@@ -534,6 +534,39 @@ SNERF_API int snerf_ray_mesh_hits_f32(const float *origins, const float *dirs, c
 SNERF_API int snerf_vertex_sphere_warp_f32(const float *samples, const float *goal, const float *canon, int64_t n, int V, float radius,
                               int by_mean, float *warp, int32_t *nearest, int32_t *count, snerf_stream_t stream);
 
+/* ---- Image scores: structural similarity with its backward, and the squared error of MSE / PSNR (util/scores.py:11-48, 88-173) ----
+ * x, y: N images of C channels, H x W pixels, fp32, BOTH read through the four element strides (sn, sc, sh, sw): element
+ *   (n, c, h, w) lies at n sn + c sc + h sh + w sw, so [N,C,H,W] and channels-last [N,H,W,C] storage run without a copy.
+ * win [k]: the 1-D window; the 2-D window is G = win (x) win, applied as a VALID correlation: P = (H-k+1)(W-k+1) windows q.
+ * Rule, per image n and channel c:
+ *   mu1 = G*x  mu2 = G*y  e11 = G*(x x)  e22 = G*(y y)  e12 = G*(x y)      s11 = e11 - mu1^2  s22 = e22 - mu2^2  s12 = e12 - mu1 mu2
+ *   A = mu1^2 + mu2^2 + c1   D = s11 + s22 + c2   L = (2 mu1 mu2 + c1) / A   CS = (2 s12 + c2) / D   S = L CS
+ *   ssim[n C + c] = mean_q S     cs[n C + c] = mean_q CS     sqerr[n C + c] = the sum of (x - y)^2 over ALL H W pixels
+ *   (c1 = (k1 data_range)^2 and c2 = (k2 data_range)^2 are the caller's; the Gaussian window is the caller's too.)
+ * Written: every element of ssim and of each of cs, sqerr that is not NULL.  x == y gives ssim = cs = 1 and sqerr = 0 exactly.
+ * workspace: snerf_ssim_workspace_bytes(N, C, H, W, k) bytes, 8-byte aligned: three float64 partial sums per 32 x 32 tile of
+ *   windows, added by a second launch.  Nothing of map size is kept.
+ * Refused with SNERF_E_BADARG on the host, before anything touches a device: k < 1 or k > 33; H < k or W < k (the message names k,
+ *   H and W); c1 or c2 negative or not finite; N or C negative; C, H, W or N C times the tile count at 2^31 or above; with N C > 0
+ *   a null x, y, win or ssim (dx, g_ssim for the backward), a workspace that is null or too small.  A bad scalar is an error
+ *   whatever N is; with N C == 0 and good scalars both entries return SNERF_OK whatever the pointers are.
+ * No atomics, every sum in a fixed order that does not depend on the strides: two calls on the same inputs give the same bits, and
+ *   so do two layouts of the same images. */
+SNERF_API int64_t snerf_ssim_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int k);   /* -1 on a bad argument */
+SNERF_API int snerf_ssim_fwd_f32(const float *x, const float *y, int64_t N, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc,
+                              int64_t sh, int64_t sw, const float *win, int k, float c1, float c2, float *ssim, float *cs,
+                              float *sqerr, void *workspace, int64_t workspace_bytes, snerf_stream_t stream);
+/* Its backward.  g_ssim [N C], g_cs [N C] (NULL: zeros) are the gradients arriving at ssim and cs -> dx, the gradient with respect to
+ * x, written with the input strides, every pixel of every image.  Per window w = (g_ssim L + g_cs) / P, u = g_ssim CS / P,
+ *   a = u (2 mu2 - 2 mu1 L) / A + w (2 mu1 CS - 2 mu2) / D     b = -w CS / D     c = 2 w / D     (zero outside the valid windows)
+ *   dx[p] = (G^T a)[p] + 2 x[p] (G^T b)[p] + y[p] (G^T c)[p]     G^T: the full correlation with the flipped window
+ * The window statistics are recomputed from x and y.  The rule is symmetric in (x, y): the gradient with respect to y is this entry
+ * called with x and y swapped.  The workspace is checked as the forward's (one buffer serves both); the backward writes none of it.
+ * The same refusals and the same determinism as the forward. */
+SNERF_API int snerf_ssim_bwd_f32(const float *x, const float *y, int64_t N, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc,
+                              int64_t sh, int64_t sw, const float *win, int k, float c1, float c2, const float *g_ssim,
+                              const float *g_cs, float *dx, void *workspace, int64_t workspace_bytes, snerf_stream_t stream);
+
 /* ---- 8(f)-1: on-device ray generation + stratified coarse sampling --------------------------------------
  * Replaces get_rays (utils.py:50-54) + CoarseSampling (datasets/transforms.py:80-89) + ToTensor (:13-21) for a
  * batch of rays.  poses: fp64 [n_frames, 4, 4] camera-to-world; ray_index int64 [B] = frame*H*W + row*W + col;

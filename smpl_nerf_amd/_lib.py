@@ -147,6 +147,12 @@ SIGNATURES = {
     "snerf_ray_mesh_workspace_bytes": (c_int64, [c_int]),
     "snerf_ray_mesh_hits_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, c_int64, _P]),
     "snerf_vertex_sphere_warp_f32": (c_int, [_P, _P, _P, c_int64, c_int, c_float, c_int, _P, _P, _P, _P]),
+    # image scores: SSIM with its backward and the squared error of MSE / PSNR (csrc/ssim.hip)
+    "snerf_ssim_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int]),
+    "snerf_ssim_fwd_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int, c_float,
+                                   c_float, _P, _P, _P, _P, c_int64, _P]),
+    "snerf_ssim_bwd_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int, c_float,
+                                   c_float, _P, _P, _P, _P, c_int64, _P]),
     "snerf_raygen_f64": (c_int, [_P, c_int64, c_int, c_int, c_double, _P, _P, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "snerf_mlp_fwd_encoded_f32": (c_int, [POINTER(MlpDesc), _P, _P, c_int64, c_int64, _P, _P]),
     "snerf_render_rays_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),

@@ -10,6 +10,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     GaussianMixture / gaussian_mixture_pdf   utils.py:72-111 (the canonical-density term of SmplNerfSolver's loss)
     smpl_lbs            the body model the reference takes from smplx (train.py:214): SMPL linear blend skinning
     ray_mesh_hits / vertex_sphere_warp   datasets/vertex_sphere_dataset.py:84-116 (trimesh's intersector) and :128-159 (the true warp)
+    ssim / image_scores util/scores.py:88-173 (ssim) and :11-48 (img2mse, img2psnr): the scores of print_scores, on the device
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -748,3 +749,162 @@ def vertex_sphere_warp(samples, goal, canon, radius, by_mean: bool = False, want
         check(lib.snerf_vertex_sphere_warp_f32(ptr(x), ptr(g), ptr(c), n, V, float(radius), 1 if by_mean else 0, ptr(warp), ptr(nearest),
                                                ptr(count), current_stream()), "snerf_vertex_sphere_warp_f32")
     return (warp, nearest, count) if want_indices else warp
+
+
+# ------------------------------------------------------------------------------------------------
+# Image scores (util/scores.py): SSIM with its backward, MSE and PSNR (csrc/ssim.hip)
+# ------------------------------------------------------------------------------------------------
+def _ssim_tile_constants():
+    """The `constexpr int NAME = value;` lines of csrc/ssim_tiles.h: the kernels' tile extents, for the tests' shapes."""
+    import os
+    import re
+    with open(os.path.join(_lib.HERE, "csrc", "ssim_tiles.h")) as f:
+        return {k: int(v) for k, v in re.findall(r"constexpr int (SSIM_[A-Z_]+) = (\d+);", f.read())}
+
+
+SSIM_TILES = _ssim_tile_constants()
+_SSIM_WINDOWS = {}
+
+
+def ssim_window(kernel_size: int, kernel_sigma: float):
+    """The 1-D Gaussian window win[k] (numpy fp32) whose outer product is the reference's gaussian_filter (scores.py:71-86):
+    exp(-(i - (k - 1) / 2)^2 / (2 sigma^2)) in float64, normalised to sum 1, rounded to fp32 once."""
+    import numpy as np
+    i = np.arange(int(kernel_size), dtype=np.float64) - (int(kernel_size) - 1) / 2.
+    g = np.exp(-(i ** 2) / (2. * float(kernel_sigma) ** 2))
+    return (g / g.sum()).astype(np.float32)
+
+
+def _ssim_window_on(kernel_size, kernel_sigma, dev):
+    key = (int(kernel_size), float(kernel_sigma), str(dev))
+    if key not in _SSIM_WINDOWS:
+        _SSIM_WINDOWS[key] = torch.from_numpy(ssim_window(kernel_size, kernel_sigma)).to(dev)
+    return _SSIM_WINDOWS[key]
+
+
+def _ssim_call(entry, x, y, win, c1, c2, *outputs):
+    """One of the two entries on x, y [N,C,H,W] of EQUAL strides (what _ssim_layout hands out), with its workspace."""
+    N, C, H, W = x.shape
+    k, dev = win.numel(), x.device
+    lib = _lib.load()
+    nbytes = lib.snerf_ssim_workspace_bytes(N, C, H, W, k)
+    if nbytes < 0:
+        check(-1, "snerf_ssim_workspace_bytes")
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev), _lib.timed(f"{entry}[{H}x{W},k={k}]"):
+        check(getattr(lib, f"snerf_{entry}_f32")(ptr(x), ptr(y), N, C, H, W, *x.stride(), ptr(win), k, c1, c2, *(ptr(t) for t in outputs),
+                                                 ptr(ws), nbytes, current_stream()), f"snerf_{entry}_f32")
+
+
+def _ssim_fwd(x, y, win, c1, c2, want_cs, want_sqerr):
+    N, C = x.shape[:2]
+    ssim, cs, sqerr = (torch.empty((N, C), device=x.device, dtype=torch.float32) if want else None for want in (True, want_cs, want_sqerr))
+    _ssim_call("ssim_fwd", x, y, win, c1, c2, ssim, cs, sqerr)
+    return ssim, cs, sqerr
+
+
+def _ssim_bwd(x, y, win, c1, c2, g_ssim, g_cs):
+    dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32)
+    _ssim_call("ssim_bwd", x, y, win, c1, c2, g_ssim, g_cs, dx)
+    return dx
+
+
+class _SsimFn(torch.autograd.Function):
+    """snerf_ssim_fwd_f32 / snerf_ssim_bwd_f32 under autograd: per-channel ssim and cs [N,C].  The inputs are kept, nothing of map
+    size is; the backward recomputes the window statistics, one launch per input that wants a gradient (the gradient to y is the
+    same entry with the images swapped)."""
+
+    @staticmethod
+    def forward(ctx, x, y, win, c1, c2):
+        ssim, cs, _ = _ssim_fwd(x, y, win, c1, c2, True, False)
+        ctx.save_for_backward(x, y, win)
+        ctx.consts = (c1, c2)
+        ctx.set_materialize_grads(False)
+        return ssim, cs
+
+    @staticmethod
+    def backward(ctx, g_ssim, g_cs):
+        if g_ssim is None and g_cs is None:
+            return None, None, None, None, None
+        x, y, win = ctx.saved_tensors
+        gs = torch.zeros(x.shape[:2], device=x.device, dtype=torch.float32) if g_ssim is None else g_ssim.contiguous().float()
+        gc = None if g_cs is None else g_cs.contiguous().float()
+        dx = _ssim_bwd(x, y, win, *ctx.consts, gs, gc) if ctx.needs_input_grad[0] else None
+        dy = _ssim_bwd(y, x, win, *ctx.consts, gs, gc) if ctx.needs_input_grad[1] else None
+        return dx, dy, None, None, None
+
+
+def _ssim_layout(x, y):
+    """x and y as the entries read them: ONE set of four strides for both, no two elements at one address (dx is written through
+    them).  Tensors that already are (channels-first, channels-last, equal slices of both) pass untouched."""
+    def plain(t):
+        return all(st > 0 or n == 1 for st, n in zip(t.stride(), t.shape))
+    if x.stride() == y.stride() and plain(x):
+        return x, y
+    if plain(x):
+        return x, torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=x.dtype).copy_(y)
+    return x.contiguous(), y.contiguous()
+
+
+def _ssim_per_channel(x, y, kernel_size, kernel_sigma, data_range, k1, k2, want_sqerr=False):
+    """The checks of ssim() and the launch: (ssim [N,C], cs [N,C], sqerr [N,C] or None)."""
+    _need_cuda("x", x)
+    _need_cuda("y", y)
+    if x.dim() != 4 or x.shape != y.shape:
+        raise RuntimeError(f"ssim: x and y must be 4-D [N,C,H,W] of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.device != y.device:
+        raise RuntimeError(f"ssim: x on {x.device}, y on {y.device}")
+    k = int(kernel_size)
+    if x.size(-1) < k or x.size(-2) < k:      # scores.py:148-150
+        raise ValueError(f"Kernel size can't be greater than actual input size. Input size: {x.size()}. Kernel size: {k}")
+    if not 1 <= k <= SSIM_TILES["SSIM_MAX_K"]:
+        raise RuntimeError(f"ssim: kernel_size must be 1 .. {SSIM_TILES['SSIM_MAX_K']}, got {kernel_size}")
+    c1, c2 = float((k1 * data_range) ** 2), float((k2 * data_range) ** 2)      # scores.py:152-153
+    win = _ssim_window_on(k, kernel_sigma, x.device)
+    x, y = _ssim_layout(x, y)
+    if not want_sqerr and torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        return _SsimFn.apply(x, y, win, c1, c2) + (None,)
+    return _ssim_fwd(x.detach(), y.detach(), win, c1, c2, True, want_sqerr)
+
+
+def ssim(x, y, kernel_size: int = 11, kernel_sigma: float = 1.5, data_range=1., reduction: str = 'mean', full: bool = False,
+         k1: float = 0.01, k2: float = 0.03):
+    """util/scores.py:88-131 on 4-D fp32 GPU tensors [N,C,H,W] of any strides (channels-last views and slices run without a copy):
+    per image the channel mean of the per-channel SSIM, then `reduction` ('none' | 'mean' | 'sum') over the batch; full=True returns
+    (ssim, cs).  Two launches forward; differentiable with respect to x and y, one backward launch per input that wants a
+    gradient.  ValueError where the reference raises it: a window larger than the image.  The window is the separable
+    ssim_window(kernel_size, kernel_sigma); any kernel_size up to SSIM_TILES['SSIM_MAX_K'], even ones included."""
+    ssim_nc, cs_nc, _ = _ssim_per_channel(x, y, kernel_size, kernel_sigma, data_range, k1, k2)
+    ssim_val, cs = ssim_nc.mean(1), cs_nc.mean(1)
+    if reduction != 'none':
+        reduction_operation = {'mean': torch.mean, 'sum': torch.sum}
+        ssim_val, cs = reduction_operation[reduction](ssim_val, dim=0), reduction_operation[reduction](cs, dim=0)
+    return (ssim_val, cs) if full else ssim_val
+
+
+def image_scores(renders, truths, channels_first: bool = False, **ssim_kwargs):
+    """The scores of the reference's print_scores that need no network (util/scores.py:457-464; LPIPS needs VGG weights) of frames
+    [N,H,W,3] (channels_first=True: [N,3,H,W]) in ONE forward call: dict of 0-d device tensors
+        mse   scores.py:28: the mean of (x - y)^2 over every pixel and channel - the kernel's per-channel sums, added in float64
+        psnr  scores.py:47-48: -10 ln(mse) / ln(10)
+        ssim  ssim(renders, truths, **ssim_kwargs)
+    mse and psnr are float64 tensors (an fp32 ulp of a 30 dB PSNR is 2e-6, more than the error of the sums), ssim is fp32.  The
+    images are taken to lie in [0, 1] for psnr, as the reference's img2psnr takes them.  Evaluation only: nothing here is
+    differentiated through."""
+    import math
+    reduction = ssim_kwargs.pop("reduction", "mean")
+    if ssim_kwargs.pop("full", False):
+        raise ValueError("image_scores: `full` is not an option here; ssim(..., full=True) returns cs")
+    if renders.dim() != 4:
+        raise RuntimeError(f"image_scores: frames must be 4-D, got {tuple(renders.shape)}")
+    x, y = (renders.detach(), truths.detach()) if channels_first else (renders.detach().permute(0, 3, 1, 2), truths.detach().permute(0, 3, 1, 2))
+    ssim_nc, _, sqerr = _ssim_per_channel(x, y, ssim_kwargs.pop("kernel_size", 11), ssim_kwargs.pop("kernel_sigma", 1.5),
+                                          ssim_kwargs.pop("data_range", 1.), ssim_kwargs.pop("k1", 0.01), ssim_kwargs.pop("k2", 0.03),
+                                          want_sqerr=True)
+    if ssim_kwargs:
+        raise TypeError(f"image_scores: unknown arguments {sorted(ssim_kwargs)}")
+    val = ssim_nc.mean(1)
+    if reduction != 'none':
+        val = {'mean': torch.mean, 'sum': torch.sum}[reduction](val, dim=0)
+    mse = sqerr.double().sum() / x.numel()
+    return {"mse": mse, "psnr": -10. * torch.log(mse) / math.log(10.), "ssim": val}

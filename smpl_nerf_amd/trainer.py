@@ -759,11 +759,8 @@ class DataParallelTrainer:
         return loss.detach()
 
     # ------------------------------------------------------------------ the Solver loop (solver/nerf_solver.py:54-163)
-    @torch.no_grad()
-    def validate(self, val_loader, h: int = 0, w: int = 0):
-        """Validation pass of NerfSolver.train (:107-150) under no_grad: mean loss over the loader, the re-rendered
-        frames (rgb_fine reshaped to [-1, h, w, 3] when whole frames were covered, :143-145) and their PSNR
-        (util/scores.py:47-48).  Returns (val_loss, psnr or None, frames or None)."""
+    def _validation_pass(self, val_loader):
+        """The loop of validate() (:107-150): (val_loss, rendered rgb_fine per batch, rgb_truth per batch), on the device."""
         for m in self.models:
             m.eval()
         total, count, renders, truths = 0.0, 0, [], []
@@ -773,14 +770,35 @@ class DataParallelTrainer:
             count += 1
             renders.append(out[1].detach())
             truths.append(data[-1].detach())
-        val_loss = total / (count or 1)                                   # :152 (guards the empty loader the same way)
+        return total / (count or 1), renders, truths                      # :152 (guards the empty loader the same way)
+
+    @torch.no_grad()
+    def validate(self, val_loader, h: int = 0, w: int = 0):
+        """Validation pass of NerfSolver.train (:107-150) under no_grad: mean loss over the loader, the re-rendered
+        frames (rgb_fine reshaped to [-1, h, w, 3] when whole frames were covered, :143-145) and their PSNR
+        (util/scores.py:47-48).  Returns (val_loss, psnr or None, frames or None)."""
+        val_loss, renders, truths = self._validation_pass(val_loader)
         frames = psnr = None
-        if count and h and w:
+        if renders and h and w:
             r, t = torch.cat(renders).cpu().numpy(), torch.cat(truths).cpu().numpy()
             if r.shape[0] % (h * w) == 0:
                 frames = r.reshape(-1, h, w, 3)
                 psnr = sio.img2psnr(frames, t.reshape(-1, h, w, 3))
         return val_loss, psnr, frames
+
+    @torch.no_grad()
+    def validate_scores(self, val_loader, h: int, w: int, **ssim_kwargs):
+        """validate()'s pass with the whole frames scored ON THE DEVICE: the scores of the reference's print_scores that need no
+        network (util/scores.py:457-464: MSE, PSNR, SSIM; inference.py:257-258) through ops.image_scores - one forward call of the
+        SSIM kernel over the frames [-1, h, w, 3] as they lie, no host copy.  Returns (val_loss, dict of 0-d device tensors mse,
+        psnr, ssim - or None when the loader did not cover whole frames)."""
+        val_loss, renders, truths = self._validation_pass(val_loader)
+        scores = None
+        if renders and h and w:
+            r, t = torch.cat(renders), torch.cat(truths)
+            if r.shape[0] % (h * w) == 0:
+                scores = ops.image_scores(r.reshape(-1, h, w, 3), t.reshape(-1, h, w, 3), **ssim_kwargs)
+        return val_loss, scores
 
     def save_checkpoint(self, save_dir: str, model_names, epoch: int, history=None):
         """utils.save_run's per-model state_dict files (utils.py:282-283), plus what the reference does not keep: the
