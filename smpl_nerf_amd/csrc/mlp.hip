@@ -267,28 +267,6 @@ __global__ __launch_bounds__(NWAVES * 64) void mlp_fwd_fold_kernel(FwdArgs A) {
     mlp_fwd_body<WIDTH, NWAVES, false, false, true>(A);
 }
 
-static int fill_args(const snerf_mlp_desc *desc, Plan &P, FwdArgs &A) {
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "mlp: desc is null");
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp: %s", why);
-    A.n_hidden = P.n_hidden;
-    A.skip_mask = desc->skip_mask;
-    A.pos_L = desc->pos_freqs;
-    A.pos_id = desc->pos_identity ? 1 : 0;
-    A.pos_nkb = P.pos_nkb;
-    A.pos_dim = P.pos_dim;
-    A.dir_L = desc->dir_freqs;
-    A.dir_id = desc->dir_identity ? 1 : 0;
-    A.dir_nkb = P.dir_nkb;
-    A.dir_dim = P.dir_dim;
-    A.add_dim = P.add_dim;
-    A.add_nkb = P.add_nkb;
-    A.add_first = (P.add_dim && desc->add_first) ? 1 : 0;
-    A.use_dir = desc->use_dir ? 1 : 0;
-    A.enc_stride = P.pos_dim + P.add_dim + (desc->use_dir ? P.dir_dim : 0);
-    return SNERF_OK;
-}
-
 int launch_pack(const Plan &P, const float *params_flat, float *packed, hipStream_t s, const char *what) {
     hipLaunchKernelGGL(mlp_pack_kernel, dim3((P.total_slabs + SLAB_PAD) * PACK_PARTS), dim3(256), 0, s, P, params_flat, packed);
     return check_launch(what);
@@ -417,33 +395,60 @@ static int launch_fwd(const Plan &P, const FwdArgs &A, hipStream_t s) {
     return launch_fwd_nw<FWD_WAVES, ENCODED, TRAIN>(P, A, s);
 }
 
-// the activation buffer of a training forward (mlp_plan.h TrainLayout)
-static void set_train_layout(FwdArgs &A, const TrainLayout &L) {
-    A.act_pe = L.pe;
-    A.act_add = L.add;
-    A.act_dpe = L.dpe;
-    A.act_x1 = L.x[1];
-    A.act_o = L.o;
-    A.act_h1 = L.h1;
-    A.act_h2 = L.h2;
-    A.act_mask = L.mask;
+// snerf_mlp_fwd_f32 / _fwd_ws_f32 (inference) and snerf_mlp_fwd_train_f32
+int launch_mlp_fwd(const MlpFwdCall &c) {
+    const char *what = c.train ? "mlp_fwd_train" : "mlp_fwd";
+    Plan P;
+    if (int rc = plan_for(what, c.desc, P)) return rc;
+    // the inference reads dirs_per_sample as a bit set, and refuses a bad one in an empty call as well
+    if (!c.train && (c.dirs_per_sample & ~(SNERF_FWD_DIRS_PER_SAMPLE | SNERF_FWD_NO_RAY_FOLD)))
+        return fail(SNERF_E_BADARG, "mlp_fwd: dirs_per_sample is a bit set of SNERF_FWD_DIRS_PER_SAMPLE | SNERF_FWD_NO_RAY_FOLD (got %d)",
+                    c.dirs_per_sample);
+    if (int rc = check_fwd_args(what, P, c)) return rc;
+    if (c.n == 0) return SNERF_OK;
+    FwdArgs A = fill_fwd_args(P, c);
+    if (!c.train) {
+        if (c.workspace_bytes < 0) return fail(SNERF_E_BADARG, "mlp_fwd: negative workspace_bytes");
+        A.dirs_per_sample = (c.dirs_per_sample & SNERF_FWD_DIRS_PER_SAMPLE) ? 1 : 0;
+        A.no_fold = (c.dirs_per_sample & SNERF_FWD_NO_RAY_FOLD) ? 1 : 0;
+        A.fold_ws = reinterpret_cast<float *>(c.workspace);
+        A.fold_ws_bytes = c.workspace ? c.workspace_bytes : 0;
+        return launch_fwd<false, false>(P, A, (hipStream_t)c.stream);
+    }
+    set_train_layout(A, P, c.act);
+    return launch_fwd<false, true>(P, A, (hipStream_t)c.stream);
+}
+
+// snerf_mlp_fwd_encoded_train_f32 / snerf_mlp_fwd_encoded_f32: c.x holds rows of row_floats already encoded inputs
+static int launch_fwd_encoded(const MlpFwdCall &c, int64_t row_floats) {
+    const char *what = c.train ? "mlp_fwd_encoded_train" : "mlp_fwd_encoded";
+    Plan P;
+    if (int rc = plan_for(what, c.desc, P)) return rc;
+    if (int rc = check_fwd_args(what, P, c, true)) return rc;
+    if (c.n == 0) return SNERF_OK;
+    if (row_floats < P.pos_dim + P.add_dim || row_floats < P.dir_dim || row_floats > 0x7fffffff)
+        return fail(SNERF_E_BADARG, "%s: row of %lld floats is too short for this network", what, (long long)row_floats);
+    FwdArgs A = fill_fwd_args(P, c);
+    A.enc_stride = (int)row_floats;
+    if (c.train) {
+        set_train_layout(A, P, c.act);
+        return launch_fwd<true, true>(P, A, (hipStream_t)c.stream);
+    }
+    return launch_fwd<true, false>(P, A, (hipStream_t)c.stream);
 }
 
 }  // namespace snerf
 
 extern "C" int64_t snerf_mlp_param_floats(const snerf_mlp_desc *desc) {
-    using namespace snerf;
-    Plan P;
-    const char *why;
-    if (!desc || make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp: bad descriptor");
+    snerf::Plan P;
+    if (int rc = snerf::plan_for("mlp_param_floats", desc, P)) return rc;
     return P.param_floats;
 }
 
 extern "C" int64_t snerf_mlp_packed_floats(const snerf_mlp_desc *desc) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc || make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp: bad descriptor");
+    if (int rc = plan_for("mlp_packed_floats", desc, P)) return rc;
     return (int64_t)(P.total_slabs + SLAB_PAD) * SLAB_FLOATS;
 }
 
@@ -451,9 +456,7 @@ extern "C" int snerf_mlp_pack_f32(const snerf_mlp_desc *desc, const float *param
                                   snerf_stream_t stream) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "mlp_pack: desc is null");
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp_pack: %s", why);
+    if (int rc = plan_for("mlp_pack", desc, P)) return rc;
     if (!params_flat || !packed) return fail(SNERF_E_BADARG, "mlp_pack: null pointer");
     if (!aligned(packed, 16)) return fail(SNERF_E_ALIGN, "mlp_pack: packed must be 16-byte aligned");
     return launch_pack(P, params_flat, packed, (hipStream_t)stream, "mlp_pack");
@@ -462,9 +465,7 @@ extern "C" int snerf_mlp_pack_f32(const snerf_mlp_desc *desc, const float *param
 extern "C" int64_t snerf_mlp_fold_workspace_bytes(const snerf_mlp_desc *desc, int64_t n, int samples_per_ray) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "mlp_fold_workspace_bytes: desc is null");
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp_fold_workspace_bytes: %s", why);
+    if (int rc = plan_for("mlp_fold_workspace_bytes", desc, P)) return rc;
     if (n < 0 || samples_per_ray < 1) return fail(SNERF_E_BADARG, "mlp_fold_workspace_bytes: bad n/samples_per_ray");
     return fold_table_bytes(P, n, samples_per_ray);
 }
@@ -472,48 +473,23 @@ extern "C" int64_t snerf_mlp_fold_workspace_bytes(const snerf_mlp_desc *desc, in
 extern "C" int snerf_mlp_fwd_ws_f32(const snerf_mlp_desc *desc, const float *packed, const float *x, const float *dirs,
                                     int dirs_per_sample, const float *add, int64_t n, int samples_per_ray, float *raw,
                                     void *workspace, int64_t workspace_bytes, snerf_stream_t stream) {
-    using namespace snerf;
-    Plan P;
-    FwdArgs A{};
-    int rc = fill_args(desc, P, A);
-    if (rc) return rc;
-    if (n < 0 || samples_per_ray < 1) return fail(SNERF_E_BADARG, "mlp_fwd: bad n/samples_per_ray");
-    if (dirs_per_sample & ~(SNERF_FWD_DIRS_PER_SAMPLE | SNERF_FWD_NO_RAY_FOLD))
-        return fail(SNERF_E_BADARG, "mlp_fwd: dirs_per_sample is a bit set of SNERF_FWD_DIRS_PER_SAMPLE | SNERF_FWD_NO_RAY_FOLD (got %d)",
-                    dirs_per_sample);
-    if (n == 0) return SNERF_OK;
-    if (!packed || !x || !raw) return fail(SNERF_E_BADARG, "mlp_fwd: null pointer");
-    if (A.use_dir && !dirs) return fail(SNERF_E_BADARG, "mlp_fwd: dirs is null");
-    if (A.add_dim && !add) return fail(SNERF_E_BADARG, "mlp_fwd: add is null");
-    if (!aligned(packed, 16) || !aligned(raw, 16)) return fail(SNERF_E_ALIGN, "mlp_fwd: packed/raw must be 16-byte aligned");
-    if (workspace_bytes < 0) return fail(SNERF_E_BADARG, "mlp_fwd: negative workspace_bytes");
-    A.packed = packed;
-    A.x = x;
-    A.dirs = dirs;
-    A.add = add;
-    A.raw = raw;
-    A.n = n;
-    A.spr = samples_per_ray;
-    A.dirs_per_sample = (dirs_per_sample & SNERF_FWD_DIRS_PER_SAMPLE) ? 1 : 0;
-    A.no_fold = (dirs_per_sample & SNERF_FWD_NO_RAY_FOLD) ? 1 : 0;
-    A.fold_ws = reinterpret_cast<float *>(workspace);
-    A.fold_ws_bytes = workspace ? workspace_bytes : 0;
-    return launch_fwd<false, false>(P, A, (hipStream_t)stream);
+    snerf::MlpFwdCall c{desc, packed, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, stream};
+    c.workspace = workspace;
+    c.workspace_bytes = workspace_bytes;
+    return snerf::launch_mlp_fwd(c);
 }
 
 extern "C" int snerf_mlp_fwd_f32(const snerf_mlp_desc *desc, const float *packed, const float *x, const float *dirs,
                                  int dirs_per_sample, const float *add, int64_t n, int samples_per_ray, float *raw,
                                  snerf_stream_t stream) {
-    return snerf_mlp_fwd_ws_f32(desc, packed, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, nullptr, 0, stream);
+    return snerf::launch_mlp_fwd({desc, packed, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, stream});
 }
 
 extern "C" int snerf_mlp_train_sizes(const snerf_mlp_desc *desc, int64_t n, int64_t *act_floats, int64_t *dy_floats,
                                      int64_t *packed_t_floats, int64_t *gpart_floats, int32_t *gpart_count) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "mlp_train_sizes: desc is null");
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp_train_sizes: %s", why);
+    if (int rc = plan_for("mlp_train_sizes", desc, P)) return rc;
     if (n < 0) return fail(SNERF_E_BADARG, "mlp_train_sizes: negative n");
     TrainLayout L;
     make_train_layout(P, L);
@@ -532,9 +508,7 @@ extern "C" int snerf_mlp_dy_layout(const snerf_mlp_desc *desc, int32_t *n_layers
                                    int32_t *n_in) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "mlp_dy_layout: desc is null");
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp_dy_layout: %s", why);
+    if (int rc = plan_for("mlp_dy_layout", desc, P)) return rc;
     TrainLayout L;
     make_train_layout(P, L);
     if (n_layers) *n_layers = P.nlayers;
@@ -549,79 +523,22 @@ extern "C" int snerf_mlp_dy_layout(const snerf_mlp_desc *desc, int32_t *n_layers
 extern "C" int snerf_mlp_fwd_train_f32(const snerf_mlp_desc *desc, const float *packed, const float *x,
                                        const float *dirs, int dirs_per_sample, const float *add, int64_t n,
                                        int samples_per_ray, float *raw, float *act, snerf_stream_t stream) {
-    using namespace snerf;
-    Plan P;
-    FwdArgs A{};
-    int rc = fill_args(desc, P, A);
-    if (rc) return rc;
-    if (n < 0 || samples_per_ray < 1) return fail(SNERF_E_BADARG, "mlp_fwd_train: bad n/samples_per_ray");
-    if (n == 0) return SNERF_OK;
-    if (!packed || !x || !raw || !act) return fail(SNERF_E_BADARG, "mlp_fwd_train: null pointer");
-    if (A.use_dir && !dirs) return fail(SNERF_E_BADARG, "mlp_fwd_train: dirs is null");
-    if (A.add_dim && !add) return fail(SNERF_E_BADARG, "mlp_fwd_train: add is null");
-    if (!aligned(packed, 16) || !aligned(raw, 16) || !aligned(act, 16))
-        return fail(SNERF_E_ALIGN, "mlp_fwd_train: packed/raw/act must be 16-byte aligned");
-    TrainLayout L;
-    make_train_layout(P, L);
-    A.packed = packed;
-    A.x = x;
-    A.dirs = dirs;
-    A.add = add;
-    A.raw = raw;
-    A.n = n;
-    A.spr = samples_per_ray;
-    A.dirs_per_sample = dirs_per_sample ? 1 : 0;
-    A.act = act;
-    set_train_layout(A, L);
-    return launch_fwd<false, true>(P, A, (hipStream_t)stream);
+    snerf::MlpFwdCall c{desc, packed, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, stream};
+    c.act = act;
+    c.train = true;
+    return snerf::launch_mlp_fwd(c);
 }
 
 extern "C" int snerf_mlp_fwd_encoded_train_f32(const snerf_mlp_desc *desc, const float *packed, const float *x_enc,
                                                int64_t n, int64_t row_floats, float *raw, float *act,
                                                snerf_stream_t stream) {
-    using namespace snerf;
-    Plan P;
-    FwdArgs A{};
-    int rc = fill_args(desc, P, A);
-    if (rc) return rc;
-    if (n < 0) return fail(SNERF_E_BADARG, "mlp_fwd_encoded_train: bad n");
-    if (n == 0) return SNERF_OK;
-    if (!packed || !x_enc || !raw || !act) return fail(SNERF_E_BADARG, "mlp_fwd_encoded_train: null pointer");
-    if (!aligned(packed, 16) || !aligned(raw, 16) || !aligned(act, 16))
-        return fail(SNERF_E_ALIGN, "mlp_fwd_encoded_train: packed/raw/act must be 16-byte aligned");
-    if (row_floats < A.pos_dim + A.add_dim || row_floats < A.dir_dim || row_floats > 0x7fffffff)
-        return fail(SNERF_E_BADARG, "mlp_fwd_encoded_train: row of %lld floats is too short for this network", (long long)row_floats);
-    TrainLayout L;
-    make_train_layout(P, L);
-    A.enc_stride = (int)row_floats;
-    A.packed = packed;
-    A.x = x_enc;
-    A.raw = raw;
-    A.n = n;
-    A.spr = 1;
-    A.act = act;
-    set_train_layout(A, L);
-    return launch_fwd<true, true>(P, A, (hipStream_t)stream);
+    snerf::MlpFwdCall c{desc, packed, x_enc, nullptr, 0, nullptr, n, 1, raw, stream};
+    c.act = act;
+    c.train = true;
+    return snerf::launch_fwd_encoded(c, row_floats);
 }
 
 extern "C" int snerf_mlp_fwd_encoded_f32(const snerf_mlp_desc *desc, const float *packed, const float *x_enc,
                                          int64_t n, int64_t row_floats, float *raw, snerf_stream_t stream) {
-    using namespace snerf;
-    Plan P;
-    FwdArgs A{};
-    int rc = fill_args(desc, P, A);
-    if (rc) return rc;
-    if (n < 0) return fail(SNERF_E_BADARG, "mlp_fwd_encoded: bad n");
-    if (n == 0) return SNERF_OK;
-    if (!packed || !x_enc || !raw) return fail(SNERF_E_BADARG, "mlp_fwd_encoded: null pointer");
-    if (row_floats < A.pos_dim + A.add_dim || row_floats < A.dir_dim || row_floats > 0x7fffffff)
-        return fail(SNERF_E_BADARG, "mlp_fwd_encoded: row of %lld floats is too short for this network", (long long)row_floats);
-    A.enc_stride = (int)row_floats;
-    if (!aligned(packed, 16) || !aligned(raw, 16)) return fail(SNERF_E_ALIGN, "mlp_fwd_encoded: packed/raw must be 16-byte aligned");
-    A.packed = packed;
-    A.x = x_enc;
-    A.raw = raw;
-    A.n = n;
-    A.spr = 1;
-    return launch_fwd<true, false>(P, A, (hipStream_t)stream);
+    return snerf::launch_fwd_encoded({desc, packed, x_enc, nullptr, 0, nullptr, n, 1, raw, stream}, row_floats);
 }

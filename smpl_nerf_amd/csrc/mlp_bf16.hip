@@ -418,14 +418,6 @@ int launch_pack_bf16(const Plan &P, int ns, const float *params_flat, void *pack
     return check_launch(what);
 }
 
-static int plan16(const snerf_mlp_desc *desc, Plan &P, const char *what) {
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "%s: desc is null", what);
-    if (make_plan(*desc, P, why, 32) != 0) return fail(SNERF_E_BADARG, "%s: %s", what, why);
-    if (desc->width != 256) return fail(SNERF_E_BADARG, "%s: the split-bf16 path supports width 256 only", what);
-    return SNERF_OK;
-}
-
 template <int NS, bool TRAIN, int FMT = FMT_BF16>
 static int launch_bf16(const FwdArgs &A, hipStream_t s) {
     constexpr int NW = 8;
@@ -438,76 +430,35 @@ static int launch_bf16(const FwdArgs &A, hipStream_t s) {
     return check_launch("mlp_fwd_bf16");
 }
 
-// argument checks + FwdArgs shared by the inference and the training forward; act == nullptr: inference
-static int fwd_bf16(const snerf_mlp_desc *desc, const void *packed, int nsplit, const float *x, const float *dirs,
-                    int dirs_per_sample, const float *add, int64_t n, int samples_per_ray, float *raw, float *act,
-                    bool train, snerf_stream_t stream, const char *what) {
+// snerf_mlp_fwd_bf16_f32 and snerf_mlp_fwd_train_bf16_f32
+int launch_mlp_fwd_bf16(int nsplit, const MlpFwdCall &c) {
+    const char *what = c.train ? "mlp_fwd_train_bf16" : "mlp_fwd_bf16";
+    const hipStream_t s = (hipStream_t)c.stream;
     Plan P;
     int ns, fmt;
     int rc = split_format(what, nsplit, &ns, &fmt);
-    if (rc || (rc = plan16(desc, P, what))) return rc;
-    if (n < 0 || samples_per_ray < 1) return fail(SNERF_E_BADARG, "%s: bad n/samples_per_ray", what);
-    if (n == 0) return SNERF_OK;
-    if (!packed || !x || !raw || (train && !act)) return fail(SNERF_E_BADARG, "%s: null pointer", what);
-    if (desc->use_dir && !dirs) return fail(SNERF_E_BADARG, "%s: dirs is null", what);
-    if (P.add_dim && !add) return fail(SNERF_E_BADARG, "%s: add is null", what);
-    if (!aligned(packed, 16) || !aligned(raw, 16) || (train && !aligned(act, 16)))
-        return fail(SNERF_E_ALIGN, "%s: packed/raw/act must be 16-byte aligned", what);
-    FwdArgs A{};
-    A.packed = reinterpret_cast<const float *>(packed);
-    A.x = x;
-    A.dirs = dirs;
-    A.add = add;
-    A.raw = raw;
-    A.n = n;
-    A.spr = samples_per_ray;
-    A.dirs_per_sample = dirs_per_sample ? 1 : 0;
-    A.n_hidden = P.n_hidden;
-    A.skip_mask = desc->skip_mask;
-    A.pos_L = desc->pos_freqs;
-    A.pos_id = desc->pos_identity ? 1 : 0;
-    A.pos_nkb = P.pos_nkb;
-    A.pos_dim = P.pos_dim;
-    A.dir_L = desc->dir_freqs;
-    A.dir_id = desc->dir_identity ? 1 : 0;
-    A.dir_nkb = P.dir_nkb;
-    A.dir_dim = P.dir_dim;
-    A.add_dim = P.add_dim;
-    A.add_nkb = P.add_nkb;
-    A.add_first = (P.add_dim && desc->add_first) ? 1 : 0;
-    A.use_dir = desc->use_dir ? 1 : 0;
+    if (rc || (rc = plan_for_256(what, c.desc, P, 32)) || (rc = check_fwd_args(what, P, c))) return rc;
+    if (c.n == 0) return SNERF_OK;
+    FwdArgs A = fill_fwd_args(P, c);
     A.total_slabs = P.total_slabs;
-    A.n_tiles = (n + 8 * 16 - 1) / (8 * 16);
-    if (train) {
+    A.n_tiles = (c.n + 8 * 16 - 1) / (8 * 16);
+    if (c.train) {
         // the activation buffer has the layout of the 16-wide plan the backward kernels are built on
         Plan Q;
-        const char *why;
-        if (make_plan(*desc, Q, why) != 0) return fail(SNERF_E_BADARG, "%s: %s", what, why);
-        TrainLayout L;
-        make_train_layout(Q, L);
-        A.act = act;
-        A.act_pe = L.pe;
-        A.act_add = L.add;
-        A.act_dpe = L.dpe;
-        A.act_x1 = L.x[1];
-        A.act_o = L.o;
-        A.act_h1 = L.h1;
-        A.act_h2 = L.h2;
-        A.act_mask = L.mask;
-        A.act_rows = L.act_rows;
-        if (fmt == FMT_F16 &&
-            hipMemsetAsync(act + (int64_t)L.act_rows * n * 16, 0x80, STAT_INTS * sizeof(int), (hipStream_t)stream) != hipSuccess)
+        if ((rc = plan_for(what, c.desc, Q))) return rc;
+        set_train_layout(A, Q, c.act);
+        if (fmt == FMT_F16 && hipMemsetAsync(c.act + (int64_t)A.act_rows * c.n * 16, 0x80, STAT_INTS * sizeof(int), s) != hipSuccess)
             return fail(SNERF_E_LAUNCH, "%s: cannot reset the layer statistics", what);
         A.pos_nkb16 = Q.pos_nkb;
         A.add_nkb16 = Q.add_nkb;
         A.dir_nkb16 = Q.dir_nkb;
-        if (fmt == FMT_F16) return launch_bf16<2, true, FMT_F16>(A, (hipStream_t)stream);
-        if (ns == 3) return launch_bf16<3, true>(A, (hipStream_t)stream);
-        return launch_bf16<2, true>(A, (hipStream_t)stream);
+        if (fmt == FMT_F16) return launch_bf16<2, true, FMT_F16>(A, s);
+        if (ns == 3) return launch_bf16<3, true>(A, s);
+        return launch_bf16<2, true>(A, s);
     }
-    if (fmt == FMT_F16) return launch_bf16<2, false, FMT_F16>(A, (hipStream_t)stream);
-    if (ns == 3) return launch_bf16<3, false>(A, (hipStream_t)stream);
-    return launch_bf16<2, false>(A, (hipStream_t)stream);
+    if (fmt == FMT_F16) return launch_bf16<2, false, FMT_F16>(A, s);
+    if (ns == 3) return launch_bf16<3, false>(A, s);
+    return launch_bf16<2, false>(A, s);
 }
 
 }  // namespace snerf
@@ -517,7 +468,7 @@ extern "C" int64_t snerf_mlp_packed_bf16_bytes(const snerf_mlp_desc *desc, int n
     Plan P;
     int ns;
     int rc = split_format("mlp_packed_bf16_bytes", nsplit, &ns, nullptr);
-    if (rc || (rc = plan16(desc, P, "mlp_packed_bf16_bytes"))) return rc;
+    if (rc || (rc = plan_for_256("mlp_packed_bf16_bytes", desc, P, 32))) return rc;
     return (int64_t)(P.total_slabs + SLAB_PAD) * slab16_bytes(ns);
 }
 
@@ -527,7 +478,7 @@ extern "C" int snerf_mlp_pack_bf16(const snerf_mlp_desc *desc, const float *para
     Plan P;
     int ns, fmt;
     int rc = split_format("mlp_pack_bf16", nsplit, &ns, &fmt);
-    if (rc || (rc = plan16(desc, P, "mlp_pack_bf16"))) return rc;
+    if (rc || (rc = plan_for_256("mlp_pack_bf16", desc, P, 32))) return rc;
     if (!params_flat || !packed) return fail(SNERF_E_BADARG, "mlp_pack_bf16: null pointer");
     if (!aligned(packed, 16)) return fail(SNERF_E_ALIGN, "mlp_pack_bf16: packed must be 16-byte aligned");
     return launch_pack_bf16(P, ns, params_flat, packed, (hipStream_t)stream, "mlp_pack_bf16", fmt);
@@ -536,13 +487,14 @@ extern "C" int snerf_mlp_pack_bf16(const snerf_mlp_desc *desc, const float *para
 extern "C" int snerf_mlp_fwd_bf16_f32(const snerf_mlp_desc *desc, const void *packed, int nsplit, const float *x,
                                       const float *dirs, int dirs_per_sample, const float *add, int64_t n,
                                       int samples_per_ray, float *raw, snerf_stream_t stream) {
-    return snerf::fwd_bf16(desc, packed, nsplit, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, nullptr, false,
-                           stream, "mlp_fwd_bf16");
+    return snerf::launch_mlp_fwd_bf16(nsplit, {desc, packed, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, stream});
 }
 
 extern "C" int snerf_mlp_fwd_train_bf16_f32(const snerf_mlp_desc *desc, const void *packed, int nsplit, const float *x,
                                             const float *dirs, int dirs_per_sample, const float *add, int64_t n,
                                             int samples_per_ray, float *raw, float *act, snerf_stream_t stream) {
-    return snerf::fwd_bf16(desc, packed, nsplit, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, act, true, stream,
-                           "mlp_fwd_train_bf16");
+    snerf::MlpFwdCall c{desc, packed, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, stream};
+    c.act = act;
+    c.train = true;
+    return snerf::launch_mlp_fwd_bf16(nsplit, c);
 }

@@ -1,7 +1,8 @@
 // Device-side building blocks shared by the forward (mlp.hip) and training (mlp_train.hip) kernels: the two slab pipes - SlabPipeDma
 // (L2 -> LDS by global_load_lds into a 4-slot ring: the headline inference kernel of width 256 and every kernel of the widths above
 // 256) and SlabPipe (L2 -> registers -> 3-slot LDS ring: training forward and dgrad up to width 256) -, the k-block MFMA step, the
-// layer walker and the in-register positional-encoding operands.  See mlp_plan.h for the operand algebra.
+// layer walker and the in-register positional-encoding operands.  See mlp_plan.h for the operand algebra.  Host side: the plan
+// preamble of every entry (plan_for), the call records and precision dispatch of the two directions, the forward checks and fill.
 #pragma once
 #include <type_traits>
 #include "snerf_common.h"
@@ -18,18 +19,69 @@ struct TrainLayout;
 // share of the CUs, n / (n + n_beside), so that both nets' workgroups are resident in one round
 int launch_wgrad(const Plan &P, const TrainLayout &L, const float *act, const float *dy, int64_t n, float *gpart,
                  float *flat_grad, hipStream_t s, int wide_nsplit = 0, bool accumulate = false, int64_t n_beside = 0);
+// ---- host: the preamble of every entry that takes a descriptor, of either net: null check, plan, "<what>: <why>" when the plan
+// refuses it.  (Here and not beside make_plan: mlp_plan.h stays free of the HIP headers, tests/native/plan_sanitize.cpp compiles it
+// alone.)
+inline int make_plan(const snerf_warp_desc &d, Plan &P, const char *&why, int kw) { return make_warp_plan(d, P, why, kw); }
+template <class Desc>
+int plan_for(const char *what, const Desc *desc, Plan &P, int kw = 16) {
+    const char *why;
+    if (!desc) return fail(SNERF_E_BADARG, "%s: desc is null", what);
+    if (make_plan(*desc, P, why, kw) != 0) return fail(SNERF_E_BADARG, "%s: %s", what, why);
+    return SNERF_OK;
+}
+// ... of the split-precision entries, whose kernels exist for width 256 alone
+template <class Desc>
+int plan_for_256(const char *what, const Desc *desc, Plan &P, int kw) {
+    if (int rc = plan_for(what, desc, P, kw)) return rc;
+    if (desc->width != 256) return fail(SNERF_E_BADARG, "%s: the split-bf16 path supports width 256 only", what);
+    return SNERF_OK;
+}
+
+// ---- one call of a RenderRayNet, forward or backward: what the C-ABI entries and the one-call render / training entries hand to
+// the implementations below.  The members up to `stream` are set by every caller, in this order; the others only where needed.
+struct MlpFwdCall {
+    const snerf_mlp_desc *desc;
+    const void *packed;    // the fp32 stream or a split-precision one
+    const float *x, *dirs;
+    int dirs_per_sample;   // a boolean; the fp32 inference alone reads the bit set of SNERF_FWD_*
+    const float *add;
+    int64_t n;
+    int spr;
+    float *raw;
+    snerf_stream_t stream;
+    float *act = nullptr;          // training forward (`train`): the activation buffer
+    bool train = false;
+    void *workspace = nullptr;     // fp32 inference: room for the per-ray fold table (snerf_mlp_fold_workspace_bytes)
+    int64_t workspace_bytes = 0;
+};
+struct MlpBwdCall {
+    const snerf_mlp_desc *desc;
+    const void *packed_t;
+    const float *act, *d_raw;
+    int64_t n;
+    float *dy, *gpart, *flat_grad;
+    snerf_stream_t stream;
+    const float *x = nullptr, *dirs = nullptr;   // input gradients (d_x != null): the forward inputs ...
+    int dirs_per_sample = 0, spr = 1;
+    float *d_x = nullptr, *d_dirs = nullptr;     // ... and their gradients
+    bool accumulate = false;           // flat_grad += instead of = (train_step.hip)
+    bool beside_another_net = false;   // the caller runs another net's backward on a second stream at the same time (train_step.hip)
+    int64_t n_beside = 0;              // ... on this many samples (launch_wgrad)
+};
+// defined in mlp.hip / mlp_bf16.hip: the bodies of snerf_mlp_fwd_f32, _fwd_ws_f32, _fwd_train_f32 and of their split-precision twins
+int launch_mlp_fwd(const MlpFwdCall &c);
+int launch_mlp_fwd_bf16(int nsplit, const MlpFwdCall &c);
 // defined in mlp_train.hip / mlp_train_bf16.hip: dgrad + wgrad + reduce of one net on n samples (the bodies of snerf_mlp_bwd_f32 /
-// snerf_mlp_bwd_inputs_f32 and their split-precision twins); accumulate: flat_grad += instead of = (train_step.hip)
-int launch_bwd(const snerf_mlp_desc *desc, const float *packed_t, const float *act, const float *d_raw, int64_t n, float *dy,
-               float *gpart, float *flat_grad, const float *x, const float *dirs, int dirs_per_sample, int spr, float *d_x,
-               float *d_dirs, snerf_stream_t stream, bool accumulate = false, bool beside_another_net = false, int64_t n_beside = 0);
-// (beside_another_net: the caller runs another net's backward on a second stream at the same time - train_step.hip)
+// snerf_mlp_bwd_inputs_f32 and their split-precision twins)
+int launch_bwd(const MlpBwdCall &c);
+int launch_bwd_bf16(int nsplit, const MlpBwdCall &c);
+// `precision` of the one-call entries: 0 = the fp32 kernels, otherwise the nsplit of the split-precision ones
+inline int mlp_forward(int precision, const MlpFwdCall &c) { return precision == 0 ? launch_mlp_fwd(c) : launch_mlp_fwd_bf16(precision, c); }
+inline int mlp_backward(int precision, const MlpBwdCall &c) { return precision == 0 ? launch_bwd(c) : launch_bwd_bf16(precision, c); }
 // defined in warp.hip: the body of snerf_warp_bwd_f32
 int launch_warp_bwd(const snerf_warp_desc *desc, const float *packed_t, const float *act, const float *d_warp, int64_t n, float *dy,
                     float *gpart, float *flat_grad, snerf_stream_t stream, bool accumulate = false);
-int launch_bwd_bf16(const snerf_mlp_desc *desc, const void *packed_t, int nsplit, const float *act, const float *d_raw, int64_t n,
-                    float *dy, float *gpart, float *flat_grad, const float *x, const float *dirs, int dirs_per_sample, int spr,
-                    float *d_x, float *d_dirs, snerf_stream_t stream, bool accumulate = false);
 // defined in mlp_lat.hip: the latency-class kernels of small calls, and which form a call takes (mode 0: the throughput kernel alone,
 // 1: the latency kernels alone, 2: the throughput kernel on the first n_main samples - whole rounds of the chip - and the latency
 // kernels on the rest)
@@ -84,6 +136,64 @@ struct FwdArgs {
     int total_slabs;   // slabs of the weight stream (persistent workgroups wrap around)
     int64_t n_tiles;   // sample tiles (NWAVES x 16 samples)
 };
+
+// ---- host: what every forward entry (mlp.hip, mlp_bf16.hip) checks and fills alike; `what` prefixes every error text ----
+// encoded: x holds whole encoded rows - no rays, hence no samples_per_ray, dirs or add.  (n == 0 is valid with any pointers:
+// SNERF_OK, and the caller returns before it touches them.)
+inline int check_fwd_args(const char *what, const Plan &P, const MlpFwdCall &c, bool encoded = false) {
+    if (c.n < 0 || c.spr < 1) return fail(SNERF_E_BADARG, "%s: bad n%s", what, encoded ? "" : "/samples_per_ray");
+    if (c.n == 0) return SNERF_OK;
+    if (!c.packed || !c.x || !c.raw || (c.train && !c.act)) return fail(SNERF_E_BADARG, "%s: null pointer", what);
+    if (!encoded && c.desc->use_dir && !c.dirs) return fail(SNERF_E_BADARG, "%s: dirs is null", what);
+    if (!encoded && P.add_dim && !c.add) return fail(SNERF_E_BADARG, "%s: add is null", what);
+    if (!aligned(c.packed, 16) || !aligned(c.raw, 16) || (c.train && !aligned(c.act, 16)))
+        return fail(SNERF_E_ALIGN, "%s: packed/raw%s must be 16-byte aligned", what, c.train ? "/act" : "");
+    return SNERF_OK;
+}
+// everything of FwdArgs that the call, the descriptor and the plan determine; left to the launches: total_slabs, n_tiles, the fold
+inline FwdArgs fill_fwd_args(const Plan &P, const MlpFwdCall &c) {
+    const snerf_mlp_desc *desc = c.desc;
+    FwdArgs A{};
+    A.packed = reinterpret_cast<const float *>(c.packed);
+    A.x = c.x;
+    A.dirs = c.dirs;
+    A.add = c.add;
+    A.raw = c.raw;
+    A.n = c.n;
+    A.spr = c.spr;
+    A.dirs_per_sample = c.dirs_per_sample ? 1 : 0;
+    A.n_hidden = P.n_hidden;
+    A.skip_mask = desc->skip_mask;
+    A.pos_L = desc->pos_freqs;
+    A.pos_id = desc->pos_identity ? 1 : 0;
+    A.pos_nkb = P.pos_nkb;
+    A.pos_dim = P.pos_dim;
+    A.dir_L = desc->dir_freqs;
+    A.dir_id = desc->dir_identity ? 1 : 0;
+    A.dir_nkb = P.dir_nkb;
+    A.dir_dim = P.dir_dim;
+    A.add_dim = P.add_dim;
+    A.add_nkb = P.add_nkb;
+    A.add_first = (P.add_dim && desc->add_first) ? 1 : 0;
+    A.use_dir = desc->use_dir ? 1 : 0;
+    A.enc_stride = P.pos_dim + P.add_dim + (desc->use_dir ? P.dir_dim : 0);
+    return A;
+}
+// the activation buffer of a training forward; P16: the 16-wide plan, whose TrainLayout (mlp_plan.h) the backward kernels read
+inline void set_train_layout(FwdArgs &A, const Plan &P16, float *act) {
+    TrainLayout L;
+    make_train_layout(P16, L);
+    A.act = act;
+    A.act_pe = L.pe;
+    A.act_add = L.add;
+    A.act_dpe = L.dpe;
+    A.act_x1 = L.x[1];
+    A.act_o = L.o;
+    A.act_h1 = L.h1;
+    A.act_h2 = L.h2;
+    A.act_mask = L.mask;
+    A.act_rows = L.act_rows;
+}
 
 // one tile (16 features of this lane's sample) <-> the tile-row-major activation buffer
 __device__ __forceinline__ void store_tile(float *buf, int row, int64_t n, int64_t sample, int g, f4 v) {

@@ -925,9 +925,7 @@ extern "C" int snerf_mlp_pack_t_f32(const snerf_mlp_desc *desc, const float *par
                                     int input_grad, snerf_stream_t stream) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "mlp_pack_t: desc is null");
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp_pack_t: %s", why);
+    if (int rc = plan_for("mlp_pack_t", desc, P)) return rc;
     if (!params_flat || !packed_t) return fail(SNERF_E_BADARG, "mlp_pack_t: null pointer");
     if (!aligned(packed_t, 16)) return fail(SNERF_E_ALIGN, "mlp_pack_t: packed_t must be 16-byte aligned");
     BwdPlan B;
@@ -936,21 +934,17 @@ extern "C" int snerf_mlp_pack_t_f32(const snerf_mlp_desc *desc, const float *par
 }
 
 namespace snerf {
-// accumulate: flat_grad += instead of = (one ray chunk of a larger batch, train_step.hip)
-int launch_bwd(const snerf_mlp_desc *desc, const float *packed_t, const float *act, const float *d_raw, int64_t n,
-               float *dy, float *gpart, float *flat_grad, const float *x, const float *dirs, int dirs_per_sample,
-               int spr, float *d_x, float *d_dirs, snerf_stream_t stream, bool accumulate, bool beside_another_net, int64_t n_beside) {
+int launch_bwd(const MlpBwdCall &c) {
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "mlp_bwd: desc is null");
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp_bwd: %s", why);
-    if (int rc = check_bwd_args("mlp_bwd", desc, P, packed_t, act, d_raw, n, dy, gpart, flat_grad, x, dirs, spr, d_x, d_dirs, 8, 8)) return rc;
-    if (n == 0) return SNERF_OK;
-    const bool input_grad = d_x != nullptr;
-    hipStream_t s = (hipStream_t)stream;
+    int rc = plan_for("mlp_bwd", c.desc, P);
+    if (rc || (rc = check_bwd_args("mlp_bwd", P, c, 8, 8))) return rc;
+    if (c.n == 0) return SNERF_OK;
+    const int64_t n = c.n;
+    const bool input_grad = c.d_x != nullptr;
+    hipStream_t s = (hipStream_t)c.stream;
     TrainLayout L;
     make_train_layout(P, L);
-    const BwdArgs A = fill_bwd_args(desc, P, L, packed_t, act, d_raw, n, dy, x, dirs, dirs_per_sample, spr, d_x, d_dirs);
+    const BwdArgs A = fill_bwd_args(P, L, c);
     // the waves of a sample tile as in the forward (snerf_common.h tile_waves: small calls and the widths above 256 run 4-wave workgroups)
     const int n_cu = device_cu_count("mlp_bwd");
     if (n_cu < 1) return n_cu;
@@ -958,10 +952,10 @@ int launch_bwd(const snerf_mlp_desc *desc, const float *packed_t, const float *a
     const bool wide_pe = input_grad && bwd_pe_tiles(P).pos == 8;
     // calls of a few 16-sample tiles per CU: the latency-class dgrad (mlp_lat.hip; bit-identical d Y); a call of a few rounds and a
     // fraction: whole rounds here, the fraction there
-    const LatChoice lc = lat_choose_bwd(P, n, input_grad, beside_another_net);
+    const LatChoice lc = lat_choose_bwd(P, n, input_grad, c.beside_another_net);
     if (lc.mode == 1) {
         if (int lrc = launch_bwd_lat(P, A, s, 0)) return lrc;
-        return launch_wgrad(P, L, act, dy, n, gpart, flat_grad, s, 0, accumulate, n_beside);
+        return launch_wgrad(P, L, c.act, c.dy, n, c.gpart, c.flat_grad, s, 0, c.accumulate, c.n_beside);
     }
     const int64_t n_dgrad = lc.mode == 2 ? lc.n_main : n;   // samples of the throughput kernel below
     auto launch = [&](auto bw_c) -> int {
@@ -982,18 +976,16 @@ int launch_bwd(const snerf_mlp_desc *desc, const float *packed_t, const float *a
         });
     };
     if (int lrc = small ? launch(std::integral_constant<int, 4>{}) : launch(std::integral_constant<int, 8>{})) return lrc;
-    int rc = check_launch("mlp_bwd(dgrad)");
-    if (rc) return rc;
+    if ((rc = check_launch("mlp_bwd(dgrad)"))) return rc;
     if (lc.mode == 2 && (rc = launch_bwd_lat(P, A, s, lc.n_main))) return rc;
-    return launch_wgrad(P, L, act, dy, n, gpart, flat_grad, s, 0, accumulate, n_beside);
+    return launch_wgrad(P, L, c.act, c.dy, n, c.gpart, c.flat_grad, s, 0, c.accumulate, c.n_beside);
 }
 }  // namespace snerf
 
 extern "C" int snerf_mlp_bwd_f32(const snerf_mlp_desc *desc, const float *packed_t, const float *act,
                                  const float *d_raw, int64_t n, float *dy, float *gpart, float *flat_grad,
                                  snerf_stream_t stream) {
-    return snerf::launch_bwd(desc, packed_t, act, d_raw, n, dy, gpart, flat_grad, nullptr, nullptr, 0, 1, nullptr,
-                             nullptr, stream);
+    return snerf::launch_bwd({desc, packed_t, act, d_raw, n, dy, gpart, flat_grad, stream});
 }
 
 extern "C" int snerf_mlp_bwd_inputs_f32(const snerf_mlp_desc *desc, const float *packed_t, const float *act,
@@ -1001,6 +993,6 @@ extern "C" int snerf_mlp_bwd_inputs_f32(const snerf_mlp_desc *desc, const float 
                                         int samples_per_ray, int64_t n, float *dy, float *gpart, float *flat_grad,
                                         float *d_x, float *d_dirs, snerf_stream_t stream) {
     if (!d_x) return snerf::fail(SNERF_E_BADARG, "mlp_bwd_inputs: d_x is null");
-    return snerf::launch_bwd(desc, packed_t, act, d_raw, n, dy, gpart, flat_grad, x, dirs, dirs_per_sample,
-                             samples_per_ray, d_x, d_dirs, stream);
+    return snerf::launch_bwd({desc, packed_t, act, d_raw, n, dy, gpart, flat_grad, stream, x, dirs, dirs_per_sample, samples_per_ray,
+                              d_x, d_dirs});
 }

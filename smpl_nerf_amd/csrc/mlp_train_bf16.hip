@@ -370,7 +370,7 @@ __global__ __launch_bounds__(WB_THREADS) void mlp_wgrad_bf16_kernel(Plan P, Trai
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // ---- the job: (wide layer, segment, group of 16 input k-blocks), like mlp_wgrad_kernel ----
-    // one group of output tiles per pair (J.ib == 0, the job owns all of the layer's output tiles): plans_t admits width 256 only,
+    // one group of output tiles per pair (J.ib == 0, the job owns all of the layer's output tiles): plan_for_256 admits width 256 only,
     // i.e. t_out <= 16
     const WgradWideJob J = wgrad_wide_job<true>(P, blockIdx.x);
     const int l = J.l, s = J.s, kb0 = J.kb0, jb = J.jb;
@@ -651,7 +651,7 @@ __global__ __launch_bounds__(WC_THREADS) void mlp_wgrad_f16_kernel(Plan P, Train
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // ---- the job: (wide layer, segment, group of 16 input k-blocks), like mlp_wgrad_kernel ----
-    // one group of output tiles per pair (J.ib == 0, the job owns all of the layer's output tiles): plans_t admits width 256 only,
+    // one group of output tiles per pair (J.ib == 0, the job owns all of the layer's output tiles): plan_for_256 admits width 256 only,
     // i.e. t_out <= 16
     const WgradWideJob J = wgrad_wide_job<true>(P, blockIdx.x);
     const int l = J.l, s = J.s, kb0 = J.kb0, jb = J.jb;
@@ -815,14 +815,6 @@ int launch_wgrad_wide_bf16(const Plan &P, const TrainLayout &L, const WgradArgs 
     return rc ? rc : check_launch("wgrad_bf16");
 }
 
-static int plans_t(const snerf_mlp_desc *desc, Plan &P, const char *what) {
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "%s: desc is null", what);
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "%s: %s", what, why);
-    if (desc->width != 256) return fail(SNERF_E_BADARG, "%s: the split-bf16 path supports width 256 only", what);
-    return SNERF_OK;
-}
-
 template <int NS, bool INPUT_GRAD, int FMT = FMT_BF16>
 static int launch_dgrad_bf16(const BwdArgs &A, hipStream_t s) {
     constexpr int NW = 8;
@@ -835,26 +827,22 @@ static int launch_dgrad_bf16(const BwdArgs &A, hipStream_t s) {
     return check_launch("mlp_bwd_bf16(dgrad)");
 }
 
-int launch_bwd_bf16(const snerf_mlp_desc *desc, const void *packed_t, int nsplit, const float *act,
-                    const float *d_raw, int64_t n, float *dy, float *gpart, float *flat_grad, const float *x,
-                    const float *dirs, int dirs_per_sample, int spr, float *d_x, float *d_dirs,
-                    snerf_stream_t stream, bool accumulate) {
+int launch_bwd_bf16(int nsplit, const MlpBwdCall &c) {
     Plan P;
     int ns, fmt;
     int rc = split_format("mlp_bwd_bf16", nsplit, &ns, &fmt);
-    if (rc || (rc = plans_t(desc, P, "mlp_bwd_bf16"))) return rc;
-    if ((rc = check_bwd_args("mlp_bwd_bf16", desc, P, packed_t, act, d_raw, n, dy, gpart, flat_grad, x, dirs, spr, d_x, d_dirs, 4, 2))) return rc;
-    if (n == 0) return SNERF_OK;
-    const bool input_grad = d_x != nullptr;
-    hipStream_t s = (hipStream_t)stream;
+    if (rc || (rc = plan_for_256("mlp_bwd_bf16", c.desc, P, 16)) || (rc = check_bwd_args("mlp_bwd_bf16", P, c, 4, 2))) return rc;
+    if (c.n == 0) return SNERF_OK;
+    const int64_t n = c.n;
+    const bool input_grad = c.d_x != nullptr;
+    hipStream_t s = (hipStream_t)c.stream;
     TrainLayout L;
     make_train_layout(P, L);
-    BwdArgs A = fill_bwd_args(desc, P, L, reinterpret_cast<const float *>(packed_t), act, d_raw, n, dy, x, dirs, dirs_per_sample, spr,
-                              d_x, d_dirs);
+    BwdArgs A = fill_bwd_args(P, L, c);
     A.total_slabs = bwd_total_slabs(P, input_grad, 32);
     A.n_tiles = (n + 8 * 16 - 1) / (8 * 16);
     A.dy_rows = L.dy_rows;
-    if (fmt == FMT_F16 && hipMemsetAsync(dy + (int64_t)L.dy_rows * n * 16, 0x80, STAT_INTS * sizeof(int), s) != hipSuccess)
+    if (fmt == FMT_F16 && hipMemsetAsync(c.dy + (int64_t)L.dy_rows * n * 16, 0x80, STAT_INTS * sizeof(int), s) != hipSuccess)
         return fail(SNERF_E_LAUNCH, "mlp_bwd_bf16: cannot reset the layer statistics");
     if (fmt == FMT_F16) rc = input_grad ? launch_dgrad_bf16<2, true, FMT_F16>(A, s) : launch_dgrad_bf16<2, false, FMT_F16>(A, s);
     else if (ns == 3) rc = input_grad ? launch_dgrad_bf16<3, true>(A, s) : launch_dgrad_bf16<3, false>(A, s);
@@ -862,7 +850,7 @@ int launch_bwd_bf16(const snerf_mlp_desc *desc, const void *packed_t, int nsplit
     if (rc) return rc;
     // wide jobs on the 16-bit matrix cores in the same format (f16x3: with per-layer scales - a per-sample scale cannot be
     // factored out of a contraction over samples), narrow jobs and the reduce in fp32
-    return launch_wgrad(P, L, act, dy, n, gpart, flat_grad, s, nsplit, accumulate);
+    return launch_wgrad(P, L, c.act, c.dy, n, c.gpart, c.flat_grad, s, nsplit, c.accumulate);
 }
 
 }  // namespace snerf
@@ -872,7 +860,7 @@ extern "C" int64_t snerf_mlp_packed_t_bf16_bytes(const snerf_mlp_desc *desc, int
     Plan P;
     int ns;
     int rc = split_format("mlp_packed_t_bf16_bytes", nsplit, &ns, nullptr);
-    if (rc || (rc = plans_t(desc, P, "mlp_packed_t_bf16_bytes"))) return rc;
+    if (rc || (rc = plan_for_256("mlp_packed_t_bf16_bytes", desc, P, 16))) return rc;
     return (int64_t)(bwd_total_slabs(P, input_grad != 0, 32) + SLAB_PAD) * slab16_bytes(ns);
 }
 
@@ -882,7 +870,7 @@ extern "C" int snerf_mlp_pack_t_bf16(const snerf_mlp_desc *desc, const float *pa
     Plan P;
     int ns, fmt;
     int rc = split_format("mlp_pack_t_bf16", nsplit, &ns, &fmt);
-    if (rc || (rc = plans_t(desc, P, "mlp_pack_t_bf16"))) return rc;
+    if (rc || (rc = plan_for_256("mlp_pack_t_bf16", desc, P, 16))) return rc;
     if (!params_flat || !packed_t) return fail(SNERF_E_BADARG, "mlp_pack_t_bf16: null pointer");
     if (!aligned(packed_t, 16)) return fail(SNERF_E_ALIGN, "mlp_pack_t_bf16: packed_t must be 16-byte aligned");
     BwdPlan B;
@@ -897,8 +885,7 @@ extern "C" int snerf_mlp_pack_t_bf16(const snerf_mlp_desc *desc, const float *pa
 extern "C" int snerf_mlp_bwd_bf16_f32(const snerf_mlp_desc *desc, const void *packed_t, int nsplit, const float *act,
                                       const float *d_raw, int64_t n, float *dy, float *gpart, float *flat_grad,
                                       snerf_stream_t stream) {
-    return snerf::launch_bwd_bf16(desc, packed_t, nsplit, act, d_raw, n, dy, gpart, flat_grad, nullptr, nullptr, 0, 1,
-                                  nullptr, nullptr, stream);
+    return snerf::launch_bwd_bf16(nsplit, {desc, packed_t, act, d_raw, n, dy, gpart, flat_grad, stream});
 }
 
 extern "C" int snerf_mlp_bwd_inputs_bf16_f32(const snerf_mlp_desc *desc, const void *packed_t, int nsplit, const float *act,
@@ -906,6 +893,6 @@ extern "C" int snerf_mlp_bwd_inputs_bf16_f32(const snerf_mlp_desc *desc, const v
                                              int samples_per_ray, int64_t n, float *dy, float *gpart, float *flat_grad,
                                              float *d_x, float *d_dirs, snerf_stream_t stream) {
     if (!d_x) return snerf::fail(SNERF_E_BADARG, "mlp_bwd_inputs_bf16: d_x is null");
-    return snerf::launch_bwd_bf16(desc, packed_t, nsplit, act, d_raw, n, dy, gpart, flat_grad, x, dirs, dirs_per_sample,
-                                  samples_per_ray, d_x, d_dirs, stream);
+    return snerf::launch_bwd_bf16(nsplit, {desc, packed_t, act, d_raw, n, dy, gpart, flat_grad, stream, x, dirs, dirs_per_sample,
+                                           samples_per_ray, d_x, d_dirs});
 }

@@ -71,17 +71,14 @@ int launch_wgrad_wide_bf16(const Plan &P, const TrainLayout &L, const WgradArgs 
 
 // ---- host: what launch_bwd (mlp_train.hip) and launch_bwd_bf16 (mlp_train_bf16.hip) check and fill alike ----
 // `what` prefixes every error text; max_pos_nkb / max_dir_nkb: the encoder k-blocks the caller's INPUT_GRAD kernels hold
-inline int check_bwd_args(const char *what, const snerf_mlp_desc *desc, const Plan &P, const void *packed_t, const float *act,
-                          const float *d_raw, int64_t n, const float *dy, const float *gpart, const float *flat_grad,
-                          const float *x, const float *dirs, int spr, const float *d_x, const float *d_dirs, int max_pos_nkb,
-                          int max_dir_nkb) {
-    if (n < 0) return fail(SNERF_E_BADARG, "%s: negative n", what);
-    if (n == 0) return SNERF_OK;   // (an empty call is valid with any pointers: the caller returns before it touches them)
-    if (!packed_t || !act || !d_raw || !dy || !gpart || !flat_grad) return fail(SNERF_E_BADARG, "%s: null pointer", what);
-    if (!aligned(packed_t, 16) || !aligned(act, 16) || !aligned(d_raw, 16) || !aligned(dy, 16) || !aligned(gpart, 16))
+inline int check_bwd_args(const char *what, const Plan &P, const MlpBwdCall &c, int max_pos_nkb, int max_dir_nkb) {
+    if (c.n < 0) return fail(SNERF_E_BADARG, "%s: negative n", what);
+    if (c.n == 0) return SNERF_OK;   // (an empty call is valid with any pointers: the caller returns before it touches them)
+    if (!c.packed_t || !c.act || !c.d_raw || !c.dy || !c.gpart || !c.flat_grad) return fail(SNERF_E_BADARG, "%s: null pointer", what);
+    if (!aligned(c.packed_t, 16) || !aligned(c.act, 16) || !aligned(c.d_raw, 16) || !aligned(c.dy, 16) || !aligned(c.gpart, 16))
         return fail(SNERF_E_ALIGN, "%s: buffers must be 16-byte aligned", what);
-    if (d_x != nullptr) {
-        if (!x || !d_dirs || (desc->use_dir && !dirs) || spr < 1)
+    if (c.d_x != nullptr) {
+        if (!c.x || !c.d_dirs || (c.desc->use_dir && !c.dirs) || c.spr < 1)
             return fail(SNERF_E_BADARG, "%s: input gradients need x, dirs, d_x, d_dirs", what);
         if (P.pos_nkb > max_pos_nkb || P.dir_nkb > max_dir_nkb)
             return fail(SNERF_E_BADARG, "%s: input gradients support at most %d position / %d direction encoder k-blocks", what,
@@ -90,16 +87,15 @@ inline int check_bwd_args(const char *what, const snerf_mlp_desc *desc, const Pl
     return SNERF_OK;
 }
 // everything of BwdArgs but the split-bf16 kernel's total_slabs / n_tiles / dy_rows
-inline BwdArgs fill_bwd_args(const snerf_mlp_desc *desc, const Plan &P, const TrainLayout &L, const float *packed_t,
-                             const float *act, const float *d_raw, int64_t n, float *dy, const float *x, const float *dirs,
-                             int dirs_per_sample, int spr, float *d_x, float *d_dirs) {
+inline BwdArgs fill_bwd_args(const Plan &P, const TrainLayout &L, const MlpBwdCall &c) {
+    const snerf_mlp_desc *desc = c.desc;
     const int nh = P.n_hidden;
     BwdArgs A{};
-    A.packed_t = packed_t;
-    A.act = act;
-    A.d_raw = d_raw;
-    A.dy = dy;
-    A.n = n;
+    A.packed_t = reinterpret_cast<const float *>(c.packed_t);
+    A.act = c.act;
+    A.d_raw = c.d_raw;
+    A.dy = c.dy;
+    A.n = c.n;
     A.n_hidden = nh;
     A.act_x1 = L.x[1];
     A.act_h2 = L.h2;
@@ -108,12 +104,12 @@ inline BwdArgs fill_bwd_args(const snerf_mlp_desc *desc, const Plan &P, const Tr
     A.dy_din = L.dy[nh + 3];
     A.dy_dn0 = L.dy[nh + 4];
     A.dy_rgb = L.dy[nh + 5];
-    A.x = x;
-    A.dirs = dirs;
-    A.d_x = d_x;
-    A.d_dirs = d_dirs;
-    A.dirs_per_sample = dirs_per_sample ? 1 : 0;
-    A.spr = spr < 1 ? 1 : spr;
+    A.x = c.x;
+    A.dirs = c.dirs;
+    A.d_x = c.d_x;
+    A.d_dirs = c.d_dirs;
+    A.dirs_per_sample = c.dirs_per_sample ? 1 : 0;
+    A.spr = c.spr < 1 ? 1 : c.spr;
     A.skip_mask = desc->skip_mask;
     A.pos_L = desc->pos_freqs;
     A.pos_id = desc->pos_identity ? 1 : 0;

@@ -2,7 +2,7 @@
 // Pure sequencing of the library's own entry points on the caller's stream; the workspace holds what the
 // reference keeps as temporaries (raw, weights, z_fine) - [B*N, 84] encodings and [B*N, 256] activations never
 // exist in HBM.
-#include "snerf_common.h"
+#include "warp_plan.h"
 
 namespace snerf {
 
@@ -22,35 +22,6 @@ static RenderWs render_ws(int64_t B, int Nc, int Nf) {
     w.raw_f = off, off += align16(B * N * 4 * 4);
     w.total = off;
     return w;
-}
-
-// add: per-ray additional inputs [n / spr, add_dim] or null; fold_ws / fold_bytes: room for the per-ray fold of the fp32
-// kernel (snerf_mlp_fold_workspace_bytes; 0 bytes = the per-sample form)
-static int mlp(const snerf_mlp_desc *desc, const void *packed, int precision, const float *x, const float *dirs,
-               int64_t n, int spr, float *raw, snerf_stream_t stream, const float *add = nullptr, void *fold_ws = nullptr,
-               int64_t fold_bytes = 0) {
-    if (precision == 0) {
-        if (add && fold_bytes > 0)
-            return snerf_mlp_fwd_ws_f32(desc, reinterpret_cast<const float *>(packed), x, dirs, 0, add, n, spr, raw, fold_ws, fold_bytes,
-                                        stream);
-        return snerf_mlp_fwd_f32(desc, reinterpret_cast<const float *>(packed), x, dirs, 0, add, n, spr, raw, stream);
-    }
-    return snerf_mlp_fwd_bf16_f32(desc, packed, precision, x, dirs, 0, add, n, spr, raw, stream);
-}
-
-static int mlp_per_sample_dirs(const snerf_mlp_desc *desc, const void *packed, int precision, const float *x,
-                               const float *sdirs, int64_t n, int spr, float *raw, snerf_stream_t stream) {
-    if (precision == 0)
-        return snerf_mlp_fwd_f32(desc, reinterpret_cast<const float *>(packed), x, sdirs, 1, nullptr, n, spr, raw, stream);
-    return snerf_mlp_fwd_bf16_f32(desc, packed, precision, x, sdirs, 1, nullptr, n, spr, raw, stream);
-}
-static int warp(const snerf_warp_desc *desc, const void *packed, int precision, const float *x, const float *pose_enc,
-                const float *o, int64_t n, int spr, float *w, float *warped, float *sdirs, void *fold_ws, int64_t fold_bytes,
-                snerf_stream_t stream) {
-    if (precision == 0)
-        return snerf_warp_fwd_ws_f32(desc, reinterpret_cast<const float *>(packed), x, pose_enc, o, n, spr, w, warped, sdirs,
-                                     fold_ws, fold_bytes, stream);
-    return snerf_warp_fwd_bf16_f32(desc, packed, x, pose_enc, o, n, spr, w, warped, sdirs, stream);
 }
 
 struct SmplWs {
@@ -171,8 +142,17 @@ static int snerf::render_rays_impl(const snerf_mlp_desc *desc_coarse, const void
     hipStream_t s = (hipStream_t)stream;
     int rc;
     // coarse net on the given samples, then compositing (:29-42)
-    if ((rc = mlp(desc_coarse, packed_coarse, precision, ray_samples, rays_d, B * Nc, Nc, raw_c, stream, additional, fold_ws, fold_c)))
-        return rc;
+    // (additional: per-ray inputs [B, add_dim] or null; fold_ws: room for the per-ray fold of the fp32 kernel, 0 bytes = the
+    // per-sample form)
+    auto mlp = [&](const snerf_mlp_desc *desc, const void *packed, const float *x, int n_per_ray, float *raw, int64_t fold_bytes) {
+        MlpFwdCall c{desc, packed, x, rays_d, 0, additional, B * n_per_ray, n_per_ray, raw, stream};
+        if (additional && fold_bytes > 0) {
+            c.workspace = fold_ws;
+            c.workspace_bytes = fold_bytes;
+        }
+        return mlp_forward(precision, c);
+    };
+    if ((rc = mlp(desc_coarse, packed_coarse, ray_samples, Nc, raw_c, fold_c))) return rc;
     if (Nf == 0) {  // run_fine = 0 (:43-44): (rgb, rgb, ray_samples, alpha)
         if ((rc = snerf_composite_fwd_f32(raw_c, z_vals, rays_d, 0, noise_coarse, B, Nc, white_background, rgb, weights_c,
                                           densities_fine, stream)))
@@ -190,7 +170,7 @@ static int snerf::render_rays_impl(const snerf_mlp_desc *desc_coarse, const void
                                 samples_fine, stream)))
         return rc;
     const int N = Nc + Nf;
-    if ((rc = mlp(desc_fine, packed_fine, precision, samples_fine, rays_d, B * N, N, raw_f, stream, additional, fold_ws, fold_f))) return rc;
+    if ((rc = mlp(desc_fine, packed_fine, samples_fine, N, raw_f, fold_f))) return rc;
     return snerf_composite_fwd_f32(raw_f, z_fine, rays_d, 0, noise_fine, B, N, white_background, rgb_fine, nullptr,
                                    densities_fine, stream);
 }
@@ -234,10 +214,16 @@ extern "C" int snerf_render_rays_smpl_f32(const snerf_mlp_desc *desc_coarse, con
     const int N = Nc + Nf;
     int rc;
     // coarse: warp the given samples, net on (x', x' - o), compositing scaled per sample (:38-63)
-    if ((rc = warp(desc_warp, packed_warp, precision, ray_samples, pose_enc, rays_o, B * Nc, Nc, warp_c, warped_c, sdirs_c, ws + sw.fold,
-                   sw.fold_bytes, stream)))
-        return rc;
-    if ((rc = mlp_per_sample_dirs(desc_coarse, packed_coarse, precision, warped_c, sdirs_c, B * Nc, Nc, raw_c, stream))) return rc;
+    // one stage: the warp of n_per_ray samples per ray, then the net on (x', x' - o) with per-sample directions
+    auto stage = [&](const snerf_mlp_desc *desc, const void *packed, const float *x, int n_per_ray, float *wrp, float *warped, float *sdirs,
+                     float *raw) {
+        WarpFwdCall wc{desc_warp, packed_warp, x, pose_enc, rays_o, B * n_per_ray, n_per_ray, wrp, warped, sdirs, stream};
+        wc.workspace = ws + sw.fold;
+        wc.workspace_bytes = sw.fold_bytes;
+        if (int src = warp_forward(precision, wc)) return src;
+        return mlp_forward(precision, {desc, packed, warped, sdirs, 1, nullptr, B * n_per_ray, n_per_ray, raw, stream});
+    };
+    if ((rc = stage(desc_coarse, packed_coarse, ray_samples, Nc, warp_c, warped_c, sdirs_c, raw_c))) return rc;
     if ((rc = snerf_composite_fwd_f32(raw_c, z_vals, sdirs_c, 1, noise_coarse, B, Nc, white_background, rgb, weights_c, alpha_c,
                                       stream)))
         return rc;
@@ -245,10 +231,7 @@ extern "C" int snerf_render_rays_smpl_f32(const snerf_mlp_desc *desc_coarse, con
     if ((rc = sample_pdf_merged(refsum, z_vals, weights_c, u, rays_o, rays_d, B, Nc, Nf, nullptr, z_samples, z_fine, samples_fine,
                                 stream)))
         return rc;
-    if ((rc = warp(desc_warp, packed_warp, precision, samples_fine, pose_enc, rays_o, B * N, N, warp_fine, warped_fine, sdirs_f,
-                   ws + sw.fold, sw.fold_bytes, stream)))
-        return rc;
-    if ((rc = mlp_per_sample_dirs(desc_fine, packed_fine, precision, warped_fine, sdirs_f, B * N, N, raw_f, stream))) return rc;
+    if ((rc = stage(desc_fine, packed_fine, samples_fine, N, warp_fine, warped_fine, sdirs_f, raw_f))) return rc;
     return snerf_composite_fwd_f32(raw_f, z_fine, rays_d, 0, noise_fine, B, N, white_background, rgb_fine, nullptr,
                                    densities_fine, stream);
 }

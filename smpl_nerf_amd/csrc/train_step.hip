@@ -194,9 +194,7 @@ extern "C" int snerf_mlp_stream_slots(const snerf_mlp_desc *desc, int32_t *slot_
                                       snerf_stream_t stream) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "mlp_stream_slots: desc is null");
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "mlp_stream_slots: %s", why);
+    if (int rc = plan_for("mlp_stream_slots", desc, P)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (slot_fwd) {
         if (hipMemsetAsync(slot_fwd, 0xff, (size_t)P.param_floats * sizeof(int32_t), s) != hipSuccess)
@@ -250,10 +248,11 @@ extern "C" int snerf_adam_step_f32(const snerf_adam_state *st, const snerf_adam_
     A.eps = (float)st->eps;
     A.wd = (float)st->weight_decay;
     Plan P;
-    const char *why;
+    char who_net[32];
     for (int k = 0; k < n_nets; ++k) {
         const snerf_adam_net &N = nets_host[k];
-        if (!N.desc || make_plan(*N.desc, P, why) != 0) return fail(SNERF_E_BADARG, "adam_step: net %d has a bad descriptor", k);
+        snprintf(who_net, sizeof who_net, "adam_step: net %d", k);
+        if (int rc = plan_for(who_net, N.desc, P)) return rc;
         if (N.param_offset < 0 || N.param_offset + P.param_floats > st->n_params)
             return fail(SNERF_E_BADARG, "adam_step: net %d does not lie inside the flat parameter buffer", k);
         if (N.precision != 0 && !split_code(N.precision)) return fail(SNERF_E_BADARG, "adam_step: net %d: bad precision code", k);
@@ -418,8 +417,7 @@ static int train_ws(const snerf_mlp_desc *dc, const snerf_mlp_desc *df, int64_t 
 static int contract_additional(const snerf_mlp_desc *desc, const float *params, const float *dy, int64_t n, int spr, float *out,
                                bool overwrite, float *scratch, snerf_stream_t stream) {
     Plan P;
-    const char *why;
-    if (make_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "nerf_train_grads: %s", why);
+    if (int rc = plan_for("nerf_train_grads", desc, P)) return rc;
     TrainLayout L;
     make_train_layout(P, L);
     bool first = overwrite;
@@ -692,16 +690,16 @@ static int nerf_train_grads(const TrainArgs &a) {
     const snerf_stream_t stream = a.stream;
     const int wb = batch->white_background ? 1 : 0;
     auto fwd_train = [&](const NetArgs &n, const float *x, const float *dirs, const float *add, int64_t cnt, int spr, float *raw, float *act) {
-        if (precision == 0)
-            return snerf_mlp_fwd_train_f32(n.desc, reinterpret_cast<const float *>(n.packed), x, dirs, 0, add, cnt, spr, raw, act, stream);
-        return snerf_mlp_fwd_train_bf16_f32(n.desc, n.packed, precision, x, dirs, 0, add, cnt, spr, raw, act, stream);
+        MlpFwdCall c{n.desc, n.packed, x, dirs, 0, add, cnt, spr, raw, stream};
+        c.act = act;
+        c.train = true;
+        return mlp_forward(precision, c);
     };
     auto bwd = [&](const NetArgs &n, const float *act, const BwdSet &t, int64_t cnt, bool accumulate, snerf_stream_t st, int64_t n_beside) {
-        if (precision == 0)
-            return launch_bwd(n.desc, reinterpret_cast<const float *>(n.packed_t), act, t.d_raw, cnt, t.dy, t.gpart, n.grad, nullptr, nullptr,
-                              0, 1, nullptr, nullptr, st, accumulate, false, n_beside);
-        return launch_bwd_bf16(n.desc, n.packed_t, precision, act, t.d_raw, cnt, t.dy, t.gpart, n.grad, nullptr, nullptr, 0, 1, nullptr,
-                               nullptr, st, accumulate);
+        MlpBwdCall c{n.desc, n.packed_t, act, t.d_raw, cnt, t.dy, t.gpart, n.grad, st};
+        c.accumulate = accumulate;
+        c.n_beside = n_beside;
+        return mlp_backward(precision, c);
     };
     // (the weight-gradient launches of a chunk small enough for the concurrent backward split their jobs for each net's share of the
     // chip - by the size rule alone, with or without an auxiliary stream: the summation order, hence every bit of the gradients,
@@ -1001,17 +999,18 @@ static int smpl_nerf_train_grads(const TrainArgs &a) {
     const int wb = batch->white_background ? 1 : 0;
     const int pose_dim = W.desc->pose_dim;
     auto fwd_train = [&](const NetArgs &n, const float *x, const float *sd, int64_t cnt, int spr, float *raw, float *act) {
-        if (precision == 0)
-            return snerf_mlp_fwd_train_f32(n.desc, reinterpret_cast<const float *>(n.packed), x, sd, 1, nullptr, cnt, spr, raw, act, stream);
-        return snerf_mlp_fwd_train_bf16_f32(n.desc, n.packed, precision, x, sd, 1, nullptr, cnt, spr, raw, act, stream);
+        MlpFwdCall c{n.desc, n.packed, x, sd, 1, nullptr, cnt, spr, raw, stream};
+        c.act = act;
+        c.train = true;
+        return mlp_forward(precision, c);
     };
     auto bwd_inputs = [&](const NetArgs &n, const float *act, const BwdSet &t, const float *x, const float *sd, int64_t cnt, int spr,
                           const WarpBwdSet &u, bool accumulate, snerf_stream_t st) {
-        if (precision == 0)
-            return launch_bwd(n.desc, reinterpret_cast<const float *>(n.packed_t), act, t.d_raw, cnt, t.dy, t.gpart, n.grad, x, sd, 1, spr,
-                              u.d_x, u.d_dirs, st, accumulate, concurrent, w.base.concurrent ? (spr == Nc ? cnt / Nc * N : cnt / N * Nc) : 0);
-        return launch_bwd_bf16(n.desc, n.packed_t, precision, act, t.d_raw, cnt, t.dy, t.gpart, n.grad, x, sd, 1, spr, u.d_x, u.d_dirs, st,
-                               accumulate);
+        MlpBwdCall c{n.desc, n.packed_t, act, t.d_raw, cnt, t.dy, t.gpart, n.grad, st, x, sd, 1, spr, u.d_x, u.d_dirs};
+        c.accumulate = accumulate;
+        c.beside_another_net = concurrent;
+        c.n_beside = w.base.concurrent ? (spr == Nc ? cnt / Nc * N : cnt / N * Nc) : 0;
+        return mlp_backward(precision, c);
     };
     auto sum3 = [&](const float *p, const float *q, const float *r, int64_t cnt, float *out, snerf_stream_t st) {
         hipLaunchKernelGGL(sum3_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, (hipStream_t)st, p, q, r, cnt, out);

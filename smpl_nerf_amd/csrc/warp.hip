@@ -297,9 +297,7 @@ extern "C" int snerf_warp_train_sizes(const snerf_warp_desc *desc, int64_t n, in
                                       int64_t *packed_t_floats, int64_t *gpart_floats) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "warp_train_sizes: desc is null");
-    if (make_warp_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "warp_train_sizes: %s", why);
+    if (int rc = plan_for("warp_train_sizes", desc, P)) return rc;
     if (n < 0) return fail(SNERF_E_BADARG, "warp_train_sizes: negative n");
     TrainLayout L;
     warp_train_layout(P, L);
@@ -314,9 +312,7 @@ extern "C" int snerf_warp_pack_t_f32(const snerf_warp_desc *desc, const float *p
                                      snerf_stream_t stream) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "warp_pack_t: desc is null");
-    if (make_warp_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "warp_pack_t: %s", why);
+    if (int rc = plan_for("warp_pack_t", desc, P)) return rc;
     if (!params_flat || !packed_t) return fail(SNERF_E_BADARG, "warp_pack_t: null pointer");
     if (!aligned(packed_t, 16)) return fail(SNERF_E_ALIGN, "warp_pack_t: packed_t must be 16-byte aligned");
     BwdPlan B;
@@ -336,9 +332,7 @@ extern "C" int snerf_warp_bwd_f32(const snerf_warp_desc *desc, const float *pack
 int snerf::launch_warp_bwd(const snerf_warp_desc *desc, const float *packed_t, const float *act, const float *d_warp, int64_t n,
                            float *dy, float *gpart, float *flat_grad, snerf_stream_t stream, bool accumulate) {
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "warp_bwd: desc is null");
-    if (make_warp_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "warp_bwd: %s", why);
+    if (int rc = plan_for("warp_bwd", desc, P)) return rc;
     if (n < 0) return fail(SNERF_E_BADARG, "warp_bwd: negative n");
     if (n == 0) return SNERF_OK;
     if (!packed_t || !act || !d_warp || !dy || !gpart || !flat_grad) return fail(SNERF_E_BADARG, "warp_bwd: null pointer");
@@ -355,24 +349,21 @@ int snerf::launch_warp_bwd(const snerf_warp_desc *desc, const float *packed_t, c
         if (P.width == 256) hipLaunchKernelGGL((warp_bwd_light_kernel<256, LW>), dim3((unsigned)g), dim3(LW * 64), 0, s, A, n_tiles);
         else hipLaunchKernelGGL((warp_bwd_light_kernel<128, LW>), dim3((unsigned)g), dim3(LW * 64), 0, s, A, n_tiles);
     }
-    int rc = check_launch("warp_bwd");
-    if (rc) return rc;
+    if (int rc = check_launch("warp_bwd")) return rc;
     return launch_wgrad(P, L, act, dy, n, gpart, flat_grad, s, 0, accumulate);
 }
 
 extern "C" int64_t snerf_warp_param_floats(const snerf_warp_desc *desc) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc || make_warp_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "warp: bad descriptor");
+    if (int rc = plan_for("warp_param_floats", desc, P)) return rc;
     return P.param_floats;
 }
 
 extern "C" int64_t snerf_warp_packed_floats(const snerf_warp_desc *desc) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc || make_warp_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "warp: bad descriptor");
+    if (int rc = plan_for("warp_packed_floats", desc, P)) return rc;
     return (int64_t)(P.total_slabs + SLAB_PAD) * SLAB_FLOATS;
 }
 
@@ -380,18 +371,13 @@ extern "C" int snerf_warp_pack_f32(const snerf_warp_desc *desc, const float *par
                                    snerf_stream_t stream) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "warp_pack: desc is null");
-    if (make_warp_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "warp_pack: %s", why);
+    if (int rc = plan_for("warp_pack", desc, P)) return rc;
     if (!params_flat || !packed) return fail(SNERF_E_BADARG, "warp_pack: null pointer");
     if (!aligned(packed, 16)) return fail(SNERF_E_ALIGN, "warp_pack: packed must be 16-byte aligned");
     return launch_pack(P, params_flat, packed, (hipStream_t)stream, "warp_pack");
 }
 
 namespace snerf {
-static int launch_warp_fwd(const snerf_warp_desc *desc, const float *packed, const float *x, const float *pose_enc,
-                           const float *o, int64_t n, int samples_per_ray, float *warp, float *warped, float *sdirs,
-                           float *act, snerf_stream_t stream, void *workspace = nullptr, int64_t workspace_bytes = 0);
 // bytes of the per-ray pose-fold table of an inference call, 0 when the fold does not apply (warp_ray_bias_kernel)
 static int64_t warp_fold_bytes(const Plan &P, int64_t n, int spr) {
     const int T = P.width / 16, nkb0 = P.pos_nkb + P.add_nkb;
@@ -405,9 +391,7 @@ static int64_t warp_fold_bytes(const Plan &P, int64_t n, int spr) {
 extern "C" int64_t snerf_warp_fold_workspace_bytes(const snerf_warp_desc *desc, int64_t n, int samples_per_ray) {
     using namespace snerf;
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "warp_fold_workspace_bytes: desc is null");
-    if (make_warp_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "warp_fold_workspace_bytes: %s", why);
+    if (int rc = plan_for("warp_fold_workspace_bytes", desc, P)) return rc;
     if (n < 0 || samples_per_ray < 1) return fail(SNERF_E_BADARG, "warp_fold_workspace_bytes: bad n/samples_per_ray");
     return warp_fold_bytes(P, n, samples_per_ray);
 }
@@ -416,57 +400,39 @@ extern "C" int snerf_warp_fwd_ws_f32(const snerf_warp_desc *desc, const float *p
                                      float *warp, float *warped, float *sdirs, void *workspace, int64_t workspace_bytes,
                                      snerf_stream_t stream) {
     if (workspace_bytes < 0) return snerf::fail(SNERF_E_BADARG, "warp_fwd: negative workspace_bytes");
-    return snerf::launch_warp_fwd(desc, packed, x, pose_enc, o, n, samples_per_ray, warp, warped, sdirs, nullptr, stream,
-                                  workspace, workspace ? workspace_bytes : 0);
+    snerf::WarpFwdCall c{desc, packed, x, pose_enc, o, n, samples_per_ray, warp, warped, sdirs, stream};
+    c.workspace = workspace;
+    c.workspace_bytes = workspace ? workspace_bytes : 0;
+    return snerf::launch_warp_fwd(c);
 }
 extern "C" int snerf_warp_fwd_f32(const snerf_warp_desc *desc, const float *packed, const float *x,
                                   const float *pose_enc, const float *o, int64_t n, int samples_per_ray,
                                   float *warp, float *warped, float *sdirs, snerf_stream_t stream) {
-    return snerf::launch_warp_fwd(desc, packed, x, pose_enc, o, n, samples_per_ray, warp, warped, sdirs, nullptr, stream);
+    return snerf::launch_warp_fwd({desc, packed, x, pose_enc, o, n, samples_per_ray, warp, warped, sdirs, stream});
 }
 extern "C" int snerf_warp_fwd_train_f32(const snerf_warp_desc *desc, const float *packed, const float *x,
                                         const float *pose_enc, const float *o, int64_t n, int samples_per_ray,
                                         float *warp, float *warped, float *sdirs, float *act, snerf_stream_t stream) {
     if (!act) return snerf::fail(SNERF_E_BADARG, "warp_fwd_train: act is null");
-    return snerf::launch_warp_fwd(desc, packed, x, pose_enc, o, n, samples_per_ray, warp, warped, sdirs, act, stream);
+    snerf::WarpFwdCall c{desc, packed, x, pose_enc, o, n, samples_per_ray, warp, warped, sdirs, stream};
+    c.act = act;
+    return snerf::launch_warp_fwd(c);
 }
-static int snerf::launch_warp_fwd(const snerf_warp_desc *desc, const float *packed, const float *x, const float *pose_enc,
-                                  const float *o, int64_t n, int samples_per_ray, float *warp, float *warped,
-                                  float *sdirs, float *act, snerf_stream_t stream, void *workspace, int64_t workspace_bytes) {
+// c.act: the training forward; c.workspace: inference with room for the per-ray fold
+int snerf::launch_warp_fwd(const WarpFwdCall &c) {
     Plan P;
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "warp_fwd: desc is null");
-    if (make_warp_plan(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "warp_fwd: %s", why);
-    if (n < 0 || samples_per_ray < 1) return fail(SNERF_E_BADARG, "warp_fwd: bad n/samples_per_ray");
-    if (n == 0) return SNERF_OK;
-    if (!packed || !warp) return fail(SNERF_E_BADARG, "warp_fwd: null pointer");
-    if (P.pos_dim && !x) return fail(SNERF_E_BADARG, "warp_fwd: x is null");
-    if (P.add_dim && !pose_enc) return fail(SNERF_E_BADARG, "warp_fwd: pose_enc is null");
-    if (warped && !x) return fail(SNERF_E_BADARG, "warp_fwd: warped requested without x");
-    if (sdirs && (!warped || !o)) return fail(SNERF_E_BADARG, "warp_fwd: sdirs needs warped and o");
-    if (!aligned(packed, 16)) return fail(SNERF_E_ALIGN, "warp_fwd: packed must be 16-byte aligned");
-    WarpArgs A{};
-    A.packed = packed;
-    A.x = P.pos_dim ? x : (warped ? x : nullptr);
-    A.add = pose_enc;
-    A.o = o;
-    A.warp = warp;
-    A.warped = warped;
-    A.sdirs = sdirs;
-    A.n = n;
-    A.spr = samples_per_ray;
-    A.pos_L = desc->pos_freqs;
-    A.pos_id = desc->pos_identity ? 1 : 0;
-    A.pos_nkb = P.pos_nkb;
-    A.add_dim = P.add_dim;
-    A.add_nkb = P.add_nkb;
-    A.act = act;
-    hipStream_t s = (hipStream_t)stream;
+    int rc = plan_for("warp_fwd", c.desc, P);
+    if (rc || (rc = check_warp_fwd_args("warp_fwd", P, c, false))) return rc;
+    if (c.n == 0) return SNERF_OK;
+    const int64_t n = c.n;
+    float *const act = c.act;
+    WarpArgs A = fill_warp_args(P, c);
+    if (!P.pos_dim && !c.warped) A.x = nullptr;   // (encoded mode: every input column comes from the pose encoding)
+    hipStream_t s = (hipStream_t)c.stream;
     {   // the LDS-resident persistent kernel whenever the net fits the 160 KiB of a CU (else the slab-streaming kernel)
-        const bool resident = true;
         const int T = P.width / 16, nkb0 = P.pos_nkb + P.add_nkb;
         const int bytes = warp_resident_bytes(T, nkb0);
-        if (resident && bytes <= 160 * 1024) {
+        if (bytes <= 160 * 1024) {
             // inference: 16 waves (121 registers: 4 waves per SIMD cover each other's sincos phases); training forward: 8
             const int RW = act ? 8 : 16;
             A.l1_slab = P.layer[1].first_slab;
@@ -476,16 +442,16 @@ static int snerf::launch_warp_fwd(const snerf_warp_desc *desc, const float *pack
             const int64_t g = A.n_tiles < n_cu ? A.n_tiles : n_cu;
             // inference with pose columns, at least one position k-block and a workspace: the per-ray fold (warp_ray_bias_kernel),
             // its table in the CALLER's workspace (snerf_warp_fold_workspace_bytes); no workspace: the per-sample form
-            if (!act && workspace) {
-                if (const int64_t need = warp_fold_bytes(P, n, samples_per_ray)) {
-                    if (workspace_bytes < need)
+            if (!act && c.workspace) {
+                if (const int64_t need = warp_fold_bytes(P, n, c.spr)) {
+                    if (c.workspace_bytes < need)
                         return fail(SNERF_E_BADARG, "warp_fwd: workspace of %lld bytes, the per-ray fold needs %lld "
-                                    "(snerf_warp_fold_workspace_bytes)", (long long)workspace_bytes, (long long)need);
-                    if (!aligned(workspace, 16)) return fail(SNERF_E_ALIGN, "warp_fwd: workspace must be 16-byte aligned");
-                    float *ray_bias = reinterpret_cast<float *>(workspace);
+                                    "(snerf_warp_fold_workspace_bytes)", (long long)c.workspace_bytes, (long long)need);
+                    if (!aligned(c.workspace, 16)) return fail(SNERF_E_ALIGN, "warp_fwd: workspace must be 16-byte aligned");
+                    float *ray_bias = reinterpret_cast<float *>(c.workspace);
                     const int64_t floats = need / (int64_t)sizeof(float);
-                    hipLaunchKernelGGL(warp_ray_bias_kernel, dim3((unsigned)((floats + 255) / 256)), dim3(256), 0, s, packed, pose_enc,
-                                       n / samples_per_ray, P.add_dim, P.pos_nkb, P.add_nkb, T, ray_bias);
+                    hipLaunchKernelGGL(warp_ray_bias_kernel, dim3((unsigned)((floats + 255) / 256)), dim3(256), 0, s, A.packed, c.pose_enc,
+                                       n / c.spr, P.add_dim, P.pos_nkb, P.add_nkb, T, ray_bias);
                     A.ray_bias = ray_bias;
                 }
             }

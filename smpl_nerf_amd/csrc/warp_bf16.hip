@@ -81,12 +81,23 @@ __global__ __launch_bounds__(NWAVES * 64) void warp_fwd_bf16_kernel(WarpArgs A, 
     if (blockIdx.x < n_tiles) wait_pair<WNS, 0>(pipe.fa0, pipe.fa1);
 }
 
-static int warp_plan32(const snerf_warp_desc *desc, Plan &P, const char *what) {
-    const char *why;
-    if (!desc) return fail(SNERF_E_BADARG, "%s: desc is null", what);
-    if (make_warp_plan(*desc, P, why, 32) != 0) return fail(SNERF_E_BADARG, "%s: %s", what, why);
-    if (desc->width != 256) return fail(SNERF_E_BADARG, "%s: the split-bf16 path supports width 256 only", what);
-    return SNERF_OK;
+// snerf_warp_fwd_bf16_f32
+int launch_warp_fwd_bf16(const WarpFwdCall &c) {
+    Plan P;
+    int rc = plan_for_256("warp_fwd_bf16", c.desc, P, 32);
+    if (rc || (rc = check_warp_fwd_args("warp_fwd_bf16", P, c, true))) return rc;
+    if (c.n == 0) return SNERF_OK;
+    const WarpArgs A = fill_warp_args(P, c);
+    constexpr int NW = 8;
+    const int lds = 3 * slab16_bytes(WNS);
+    const int n_cu = device_cu_count("warp_fwd_bf16");
+    if (n_cu < 1) return n_cu;
+    const int64_t n_tiles = (c.n + NW * 16 - 1) / (NW * 16);
+    const int64_t grid = n_tiles < n_cu ? n_tiles : n_cu;
+    if ((rc = launch_lds<warp_fwd_bf16_kernel<256, NW>>("warp_fwd_bf16", dim3((unsigned)grid), dim3(NW * 64), lds, (hipStream_t)c.stream, A,
+                                                        P.total_slabs, n_tiles)))
+        return rc;
+    return check_launch("warp_fwd_bf16");
 }
 
 }  // namespace snerf
@@ -94,8 +105,7 @@ static int warp_plan32(const snerf_warp_desc *desc, Plan &P, const char *what) {
 extern "C" int64_t snerf_warp_packed_bf16_bytes(const snerf_warp_desc *desc) {
     using namespace snerf;
     Plan P;
-    int rc = warp_plan32(desc, P, "warp_packed_bf16_bytes");
-    if (rc) return rc;
+    if (int rc = plan_for_256("warp_packed_bf16_bytes", desc, P, 32)) return rc;
     return (int64_t)(P.total_slabs + SLAB_PAD) * slab16_bytes(WNS);
 }
 
@@ -103,8 +113,7 @@ extern "C" int snerf_warp_pack_bf16(const snerf_warp_desc *desc, const float *pa
                                     snerf_stream_t stream) {
     using namespace snerf;
     Plan P;
-    int rc = warp_plan32(desc, P, "warp_pack_bf16");
-    if (rc) return rc;
+    if (int rc = plan_for_256("warp_pack_bf16", desc, P, 32)) return rc;
     if (!params_flat || !packed) return fail(SNERF_E_BADARG, "warp_pack_bf16: null pointer");
     if (!aligned(packed, 16)) return fail(SNERF_E_ALIGN, "warp_pack_bf16: packed must be 16-byte aligned");
     return launch_pack_bf16(P, WNS, params_flat, packed, (hipStream_t)stream, "warp_pack_bf16");
@@ -113,39 +122,5 @@ extern "C" int snerf_warp_pack_bf16(const snerf_warp_desc *desc, const float *pa
 extern "C" int snerf_warp_fwd_bf16_f32(const snerf_warp_desc *desc, const void *packed, const float *x,
                                        const float *pose_enc, const float *o, int64_t n, int samples_per_ray,
                                        float *warp, float *warped, float *sdirs, snerf_stream_t stream) {
-    using namespace snerf;
-    Plan P;
-    int rc = warp_plan32(desc, P, "warp_fwd_bf16");
-    if (rc) return rc;
-    if (n < 0 || samples_per_ray < 1) return fail(SNERF_E_BADARG, "warp_fwd_bf16: bad n/samples_per_ray");
-    if (n == 0) return SNERF_OK;
-    if (!packed || !x || !warp) return fail(SNERF_E_BADARG, "warp_fwd_bf16: null pointer");
-    if (P.add_dim && !pose_enc) return fail(SNERF_E_BADARG, "warp_fwd_bf16: pose_enc is null");
-    if (sdirs && (!warped || !o)) return fail(SNERF_E_BADARG, "warp_fwd_bf16: sdirs needs warped and o");
-    if (!aligned(packed, 16)) return fail(SNERF_E_ALIGN, "warp_fwd_bf16: packed must be 16-byte aligned");
-    WarpArgs A{};
-    A.packed = reinterpret_cast<const float *>(packed);
-    A.x = x;
-    A.add = pose_enc;
-    A.o = o;
-    A.warp = warp;
-    A.warped = warped;
-    A.sdirs = sdirs;
-    A.n = n;
-    A.spr = samples_per_ray;
-    A.pos_L = desc->pos_freqs;
-    A.pos_id = desc->pos_identity ? 1 : 0;
-    A.pos_nkb = P.pos_nkb;
-    A.add_dim = P.add_dim;
-    A.add_nkb = P.add_nkb;
-    constexpr int NW = 8;
-    const int lds = 3 * slab16_bytes(WNS);
-    const int n_cu = device_cu_count("warp_fwd_bf16");
-    if (n_cu < 1) return n_cu;
-    const int64_t n_tiles = (n + NW * 16 - 1) / (NW * 16);
-    const int64_t grid = n_tiles < n_cu ? n_tiles : n_cu;
-    if ((rc = launch_lds<warp_fwd_bf16_kernel<256, NW>>("warp_fwd_bf16", dim3((unsigned)grid), dim3(NW * 64), lds, (hipStream_t)stream, A, P.total_slabs,
-                                                        n_tiles)))
-        return rc;
-    return check_launch("warp_fwd_bf16");
+    return snerf::launch_warp_fwd_bf16({desc, packed, x, pose_enc, o, n, samples_per_ray, warp, warped, sdirs, stream});
 }

@@ -254,3 +254,198 @@ def test_training_buffer_sizes_of_widths_above_256(lib):
     tiny = _lib.MlpDesc(2, 512, 0, 1, 0, 1, 0, 0, 1)
     assert lib.snerf_mlp_param_floats(tiny) < 0
     assert lib.snerf_mlp_pack_f32(tiny, None, None, None) == -1 and b"two k-blocks" in lib.snerf_last_error_string()
+
+
+# ---- the per-net entries: what each refuses on the host, and with which code -------------------------------------------------
+# Every row is one call that differs from the entry's BASE call (n = 16 samples in rays of 4, every pointer the fake address 64)
+# in the arguments named; BASE itself is never called.  A row is refused on the host (code < 0) or is an empty call (n == 0), so
+# nothing is ever launched on the fake pointers.  (-1 = SNERF_E_BADARG, -2 = SNERF_E_ALIGN; the text is a part of
+# snerf_last_error_string() that names the argument.)  A tuple of names stands for one row per name; EMPTY: n = 0 with every
+# pointer null ("EMPTY d_x": every pointer but d_x).
+_NET = _lib.MlpDesc(8, 256, 10, 0, 4, 0, 6, 1 << 4, 1, 0)        # reads dirs and per-ray additional inputs; a width every entry has
+_NET_W1 = _lib.MlpDesc(8, 1, 10, 0, 4, 0, 6, 1 << 4, 1, 0)
+_WARP = _lib.WarpDesc(256, 10, 0, 40)
+_WARP_W0 = _lib.WarpDesc(0, 10, 0, 40)                            # (a WarpFieldNet of width 1 is valid)
+EMPTY = "EMPTY"
+_FWD = "desc packed x dirs dps add n spr raw"
+_BWD_IN = "x dirs dps spr n dy gpart flat_grad d_x d_dirs stream"
+_WFWD = "desc packed x pose_enc o n spr warp warped sdirs"
+NET_ENTRIES = {
+    "snerf_mlp_fwd_f32": _FWD + " stream",
+    "snerf_mlp_fwd_ws_f32": _FWD + " workspace workspace_bytes stream",
+    "snerf_mlp_fwd_train_f32": _FWD + " act stream",
+    "snerf_mlp_fwd_encoded_f32": "desc packed x n row_floats raw stream",
+    "snerf_mlp_fwd_encoded_train_f32": "desc packed x n row_floats raw act stream",
+    "snerf_mlp_fwd_bf16_f32": "desc packed nsplit x dirs dps add n spr raw stream",
+    "snerf_mlp_fwd_train_bf16_f32": "desc packed nsplit x dirs dps add n spr raw act stream",
+    "snerf_mlp_bwd_f32": "desc packed_t act d_raw n dy gpart flat_grad stream",
+    "snerf_mlp_bwd_inputs_f32": "desc packed_t act d_raw " + _BWD_IN,
+    "snerf_mlp_bwd_bf16_f32": "desc packed_t nsplit act d_raw n dy gpart flat_grad stream",
+    "snerf_mlp_bwd_inputs_bf16_f32": "desc packed_t nsplit act d_raw " + _BWD_IN,
+    "snerf_warp_fwd_f32": _WFWD + " stream",
+    "snerf_warp_fwd_ws_f32": _WFWD + " workspace workspace_bytes stream",
+    "snerf_warp_fwd_train_f32": _WFWD + " act stream",
+    "snerf_warp_fwd_bf16_f32": _WFWD + " stream",
+    "snerf_warp_bwd_f32": "desc packed_t act d_warp n dy gpart flat_grad stream",
+    # pack and size entries that take a descriptor
+    "snerf_mlp_param_floats": "desc", "snerf_mlp_packed_floats": "desc",
+    "snerf_mlp_pack_f32": "desc params packed stream",
+    "snerf_mlp_pack_t_f32": "desc params packed input_grad stream",
+    "snerf_mlp_fold_workspace_bytes": "desc n spr",
+    "snerf_mlp_train_sizes": "desc n o0 o1 o2 o3 o4",
+    "snerf_mlp_dy_layout": "desc o0 o1 o2 o3",
+    "snerf_mlp_stream_slots": "desc o0 o1 input_grad stream",
+    "snerf_mlp_packed_bf16_bytes": "desc nsplit",
+    "snerf_mlp_pack_bf16": "desc params packed nsplit stream",
+    "snerf_mlp_packed_t_bf16_bytes": "desc nsplit input_grad",
+    "snerf_mlp_pack_t_bf16": "desc params packed nsplit input_grad stream",
+    "snerf_warp_param_floats": "desc", "snerf_warp_packed_floats": "desc",
+    "snerf_warp_pack_f32": "desc params packed stream",
+    "snerf_warp_pack_t_f32": "desc params packed stream",
+    "snerf_warp_fold_workspace_bytes": "desc n spr",
+    "snerf_warp_train_sizes": "desc n o0 o1 o2 o3",
+    "snerf_warp_packed_bf16_bytes": "desc",
+    "snerf_warp_pack_bf16": "desc params packed stream",
+}
+_SCALARS = {"n": 16, "spr": 4, "dps": 0, "nsplit": 3, "row_floats": 200, "workspace_bytes": 0, "input_grad": 1, "stream": None,
+            "workspace": None, "o0": None, "o1": None, "o2": None, "o3": None, "o4": None}
+
+
+def _base(entry):
+    """The call every row of `entry` departs from.  Never made: with real buffers it would be a valid call."""
+    base = {a: _SCALARS.get(a, 64) for a in NET_ENTRIES[entry].split()}
+    base["desc"] = _WARP if "warp" in entry else _NET
+    return base
+
+
+_DESC = [({"desc": None}, -1, b"desc is null"), ({"desc": _NET_W1}, -1, b"width must be in [2, 512]")]
+_WDESC = [({"desc": None}, -1, b"desc is null"), ({"desc": _WARP_W0}, -1, b"width must be in [1, 256]")]
+_N_SPR = [({"n": -1}, -1, b"bad n/samples_per_ray"), ({"spr": 0}, -1, b"bad n/samples_per_ray"), (EMPTY, 0, b"")]
+_MLP_PTRS = [(("packed", "x", "raw"), -1, b"null pointer"), ({"dirs": None}, -1, b"dirs is null"), ({"add": None}, -1, b"add is null")]
+_DPS_BITS = [({"dps": 4, "n": 0}, -1, b"dirs_per_sample is a bit set"), ({"dps": -1, "n": 0}, -1, b"dirs_per_sample is a bit set")]
+_NSPLIT = [({"nsplit": 4, "n": 0}, -1, b"nsplit"), ({"nsplit": 0, "n": 0}, -1, b"nsplit"),
+           ({"desc": _lib.MlpDesc(8, 128, 10, 0, 4, 0, 6, 1 << 4, 1, 0)}, -1, b"width 256 only")]
+_NSPLIT_PACK = [({"nsplit": 4}, -1, b"nsplit"), _NSPLIT[2]]
+_BWD = [({"n": -1}, -1, b"negative n"),
+        (("packed_t", "act", "dy", "gpart", "flat_grad"), -1, b"null pointer"),
+        ({"packed_t": 68}, -2, b"aligned"), ({"act": 68}, -2, b"aligned"), ({"dy": 68}, -2, b"aligned"), ({"gpart": 68}, -2, b"aligned")]
+_MLP_BWD = _BWD + [({"d_raw": None}, -1, b"null pointer"), ({"d_raw": 68}, -2, b"aligned")]
+_BWD_INPUTS = [(EMPTY, -1, b"d_x is null"), (EMPTY + " d_x", 0, b""), ({"d_x": None, "n": 0}, -1, b"d_x is null"), ({"d_x": None}, -1, b"d_x is null"),
+               (("x", "dirs", "d_dirs"), -1, b"input gradients need"), ({"spr": 0}, -1, b"input gradients need")]
+_WARP_PTRS = [(("packed", "warp"), -1, b"null pointer"), ({"pose_enc": None}, -1, b"pose_enc is null"),
+              ({"warped": None}, -1, b"sdirs needs warped and o"), ({"o": None}, -1, b"sdirs needs warped and o"),
+              ({"packed": 68}, -2, b"packed must be 16-byte aligned")]
+_WARP_X = [({"x": None}, -1, b"x is null"), ({"x": None, "sdirs": None}, -1, b"x is null")]
+_PACK = [(("params", "packed"), -1, b"null pointer"), ({"packed": 68}, -2, b"aligned")]
+NET_ROWS = {
+    "snerf_mlp_fwd_f32": _DESC + _N_SPR + _MLP_PTRS + _DPS_BITS + [({"packed": 68}, -2, b"packed/raw"), ({"raw": 68}, -2, b"packed/raw")],
+    "snerf_mlp_fwd_ws_f32": _DESC + _N_SPR + _MLP_PTRS + _DPS_BITS + [
+        ({"packed": 68}, -2, b"packed/raw"), ({"raw": 68}, -2, b"packed/raw"),
+        ({"workspace": 64, "workspace_bytes": -1}, -1, b"negative workspace_bytes"),
+        ({"workspace": 64, "workspace_bytes": -1, "n": 0}, 0, b"")],          # (an empty call returns before it looks at the workspace)
+    "snerf_mlp_fwd_train_f32": _DESC + _N_SPR + _MLP_PTRS + [
+        ({"act": None}, -1, b"null pointer"), ({"dps": 4, "n": 0}, 0, b""),    # (dirs_per_sample is a boolean here)
+        ({"packed": 68}, -2, b"packed/raw/act"), ({"raw": 68}, -2, b"packed/raw/act"), ({"act": 68}, -2, b"packed/raw/act")],
+    "snerf_mlp_fwd_encoded_f32": _DESC + [
+        ({"n": -1}, -1, b"bad n"), (EMPTY, 0, b""), (("packed", "x", "raw"), -1, b"null pointer"),
+        ({"packed": 68}, -2, b"packed/raw"), ({"raw": 68}, -2, b"packed/raw"),
+        ({"row_floats": 65}, -1, b"too short"), ({"row_floats": 1 << 31}, -1, b"row of"), ({"row_floats": 0, "n": 0}, 0, b"")],
+    "snerf_mlp_fwd_encoded_train_f32": _DESC + [
+        ({"n": -1}, -1, b"bad n"), (EMPTY, 0, b""), (("packed", "x", "raw", "act"), -1, b"null pointer"),
+        ({"packed": 68}, -2, b"packed/raw/act"), ({"raw": 68}, -2, b"packed/raw/act"), ({"act": 68}, -2, b"packed/raw/act"),
+        ({"row_floats": 65}, -1, b"too short"), ({"row_floats": 1 << 31}, -1, b"row of"), ({"row_floats": 0, "n": 0}, 0, b"")],
+    "snerf_mlp_fwd_bf16_f32": _DESC + _N_SPR + _MLP_PTRS + _NSPLIT + [
+        ({"dps": 4, "n": 0}, 0, b""), ({"packed": 68}, -2, b"packed/raw"), ({"raw": 68}, -2, b"packed/raw")],
+    "snerf_mlp_fwd_train_bf16_f32": _DESC + _N_SPR + _MLP_PTRS + _NSPLIT + [
+        ({"act": None}, -1, b"null pointer"), ({"dps": 4, "n": 0}, 0, b""),
+        ({"packed": 68}, -2, b"packed/raw/act"), ({"raw": 68}, -2, b"packed/raw/act"), ({"act": 68}, -2, b"packed/raw/act")],
+    "snerf_mlp_bwd_f32": _DESC + _MLP_BWD + [(EMPTY, 0, b"")],
+    "snerf_mlp_bwd_inputs_f32": _DESC + _MLP_BWD + _BWD_INPUTS,
+    "snerf_mlp_bwd_bf16_f32": _DESC + _MLP_BWD + _NSPLIT + [(EMPTY, 0, b"")],
+    "snerf_mlp_bwd_inputs_bf16_f32": _DESC + _MLP_BWD + _BWD_INPUTS + _NSPLIT,
+    "snerf_warp_fwd_f32": _WDESC + _N_SPR + _WARP_PTRS + _WARP_X,
+    "snerf_warp_fwd_ws_f32": _WDESC + _N_SPR + _WARP_PTRS + _WARP_X + [
+        ({"workspace": 64, "workspace_bytes": -1}, -1, b"negative workspace_bytes"),
+        ({"workspace": 64, "workspace_bytes": -1, "n": 0}, -1, b"negative workspace_bytes")],
+    "snerf_warp_fwd_train_f32": _WDESC + _N_SPR[:2] + _WARP_PTRS + _WARP_X + [
+        (EMPTY, -1, b"act is null"), (EMPTY + " act", 0, b""), ({"act": None, "n": 0}, -1, b"act is null"), ({"act": None}, -1, b"act is null")],
+    # the split-bf16 warp requires x in every call
+    "snerf_warp_fwd_bf16_f32": _WDESC + _N_SPR + _WARP_PTRS + [
+        ({"x": None}, -1, b"null pointer"), ({"x": None, "warped": None, "sdirs": None}, -1, b"null pointer"),
+        ({"desc": _lib.WarpDesc(128, 10, 0, 40)}, -1, b"width 256 only")],
+    "snerf_warp_bwd_f32": _WDESC + _BWD + [({"d_warp": None}, -1, b"null pointer"), (EMPTY, 0, b"")],
+    # (snerf_*_param_floats / _packed_floats name the net, not the reason, in one of the two builds this table is run against)
+    "snerf_mlp_param_floats": [({"desc": None}, -1, b"mlp"), ({"desc": _NET_W1}, -1, b"mlp")],
+    "snerf_mlp_packed_floats": [({"desc": None}, -1, b"mlp"), ({"desc": _NET_W1}, -1, b"mlp")],
+    "snerf_mlp_pack_f32": _DESC + _PACK,
+    "snerf_mlp_pack_t_f32": _DESC + _PACK,
+    "snerf_mlp_fold_workspace_bytes": _DESC + [({"n": -1}, -1, b"bad n/samples_per_ray"), ({"spr": 0}, -1, b"bad n/samples_per_ray")],
+    "snerf_mlp_train_sizes": _DESC + [({"n": -1}, -1, b"negative n")],
+    "snerf_mlp_dy_layout": _DESC,
+    "snerf_mlp_stream_slots": _DESC,
+    "snerf_mlp_packed_bf16_bytes": _DESC + _NSPLIT_PACK,
+    "snerf_mlp_pack_bf16": _DESC + _PACK + _NSPLIT_PACK,
+    "snerf_mlp_packed_t_bf16_bytes": _DESC + _NSPLIT_PACK,
+    "snerf_mlp_pack_t_bf16": _DESC + _PACK + _NSPLIT_PACK,
+    "snerf_warp_param_floats": [({"desc": None}, -1, b"warp"), ({"desc": _WARP_W0}, -1, b"warp")],
+    "snerf_warp_packed_floats": [({"desc": None}, -1, b"warp"), ({"desc": _WARP_W0}, -1, b"warp")],
+    "snerf_warp_pack_f32": _WDESC + _PACK,
+    "snerf_warp_pack_t_f32": _WDESC + _PACK,
+    "snerf_warp_fold_workspace_bytes": _WDESC + [({"n": -1}, -1, b"bad n/samples_per_ray"), ({"spr": 0}, -1, b"bad n/samples_per_ray")],
+    "snerf_warp_train_sizes": _WDESC + [({"n": -1}, -1, b"negative n")],
+    "snerf_warp_packed_bf16_bytes": _WDESC + [({"desc": _lib.WarpDesc(128, 10, 0, 40)}, -1, b"width 256 only")],
+    "snerf_warp_pack_bf16": _WDESC + _PACK + [({"desc": _lib.WarpDesc(128, 10, 0, 40)}, -1, b"width 256 only")],
+}
+
+
+def _net_rows(table):
+    out = []
+    for entry, rows in table.items():
+        base = _base(entry)
+        for change, code, text in rows:
+            if isinstance(change, str) and change.startswith(EMPTY):
+                changes = [dict({a: None for a, v in base.items() if v == 64 and a not in change.split()[1:]}, n=0)]
+            elif isinstance(change, tuple):
+                changes = [{a: None} for a in change]
+            else:
+                changes = [change]
+            for ch in changes:
+                assert ch and set(ch) <= set(base) and any(base[a] is not ch[a] for a in ch), (entry, ch)   # departs from BASE
+                assert code < 0 or ch.get("n") == 0, (entry, ch)                                            # refused, or empty
+                label = ",".join(f"{a}={'bad' if a == 'desc' and v is not None else v}" for a, v in ch.items())
+                out.append(pytest.param(entry, ch, code, text, id=f"{entry[6:]}-{label}-{len(out)}"))
+    return out
+
+
+def _call(lib, entry, change):
+    args = dict(_base(entry), **change)
+    rc = getattr(lib, entry)(*[args[a] for a in NET_ENTRIES[entry].split()])
+    return rc, lib.snerf_last_error_string()
+
+
+def test_net_entry_table_covers_every_entry():
+    assert set(NET_ROWS) == set(NET_ENTRIES)
+    for entry, names in NET_ENTRIES.items():
+        assert len(names.split()) == len(_lib.SIGNATURES[entry][1]), entry
+
+
+@pytest.mark.parametrize("entry,change,code,text", _net_rows(NET_ROWS))
+def test_net_entries_refuse_on_the_host(lib, entry, change, code, text):
+    rc, err = _call(lib, entry, change)
+    assert rc == code, (rc, err)
+    assert text in err, err
+
+
+# Calls wrong in two ways at once, where the copies of the forward checks disagreed before they became one: the encoded inference
+# looked at the row length first, the encoded training forward at the alignment.  One order now: alignment first.
+NET_ROWS_TWO_FAULTS = {
+    "snerf_mlp_fwd_encoded_f32": [({"packed": 68, "row_floats": 65}, -2, b"aligned"), ({"raw": 68, "row_floats": 65}, -2, b"aligned")],
+    "snerf_mlp_fwd_encoded_train_f32": [({"packed": 68, "row_floats": 65}, -2, b"aligned"), ({"act": 68, "row_floats": 65}, -2, b"aligned")],
+}
+
+
+@pytest.mark.parametrize("entry,change,code,text", _net_rows(NET_ROWS_TWO_FAULTS))
+def test_net_entries_checked_in_one_order_when_wrong_twice(lib, entry, change, code, text):
+    rc, err = _call(lib, entry, change)
+    assert rc == code, (rc, err)
+    assert text in err, err
