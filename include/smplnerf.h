@@ -519,6 +519,25 @@ SNERF_API int64_t snerf_ray_mesh_workspace_bytes(int F);   /* -1 on a bad F */
 SNERF_API int snerf_ray_mesh_hits_f32(const float *origins, const float *dirs, const float *vertices, const int32_t *faces, int64_t R,
                               int V, int F, int max_hits, float *t_hits, int32_t *n_hits, void *workspace,
                               int64_t workspace_bytes, snerf_stream_t stream);
+/* The first hit of every ray, with its face and where on it (render.py:222-319, get_warp: what create_dataset.py saves as the depth
+ * and the warp image of datasets/single_sample_dataset.py).  Inputs, intersection rule, workspace and the order of the host
+ * checks are snerf_ray_mesh_hits_f32's; t equals its t_hits[r, 0] with max_hits = 1, bit for bit.
+ *   The first hit of ray r is its hit with the smallest t; of hits with equal t it is the one with the smaller face index.
+ * -> t [R]: the hit parameter, +inf on a miss; face [R] int32: the index into faces, -1 on a miss; uv [R,2]: u and v of that pair
+ *   as the rule divides them, 0 on a miss.  The hit point is (1 - u - v) a + u b + v c.
+ * canon, warp, depth: all NULL, or all non-NULL.  canon [V,3] is the same mesh in another (the canonical) pose, and then
+ *   depth [R] = t |d|, |d| = sqrtf((dx dx + dy dy) + dz dz): the distance of the hit from the origin, 0 on a miss (the marker of
+ *              single_sample_dataset.py:116);
+ *   warp [R,3] = ((ca + u (cb - ca)) + v (cc - ca)) - (o + d t) with ca, cb, cc the rows of canon that faces[face] names:
+ *              the hit point's way to the same surface point of the canonical body, 0 on a miss.
+ *   The reference solves goal_vertices^T x = hit for x per ray and forms canonical_vertices^T x; x = (1 - u - v, u, v) wherever
+ *   the face's plane misses the world origin, and its solve is singular where it does not - which is not kept.
+ * Every element of every non-NULL output is written; no atomics, nothing of size R F; two calls give the same bits.
+ * Argument checks as above (R = 0: SNERF_OK whatever the pointers are); a null t, face or uv and a mix of null and non-null among
+ *   canon, warp and depth are SNERF_E_BADARG. */
+SNERF_API int snerf_ray_mesh_first_hit_f32(const float *origins, const float *dirs, const float *vertices, const int32_t *faces,
+                              int64_t R, int V, int F, const float *canon, float *t, int32_t *face, float *uv, float *warp,
+                              float *depth, void *workspace, int64_t workspace_bytes, snerf_stream_t stream);
 /* The sphere warp (:128-159).  samples [n,3]; goal, canon [V,3]: ONE body in the goal and in the canonical pose (the data set has
  * one pose per image).  d_v = sqrtf(|p - g_v|^2), the square summed as (dx^2 + dy^2) + dz^2, and the three-way weight
  * w(d) = 1 where d < radius, 0 where d > radius, d itself where they are equal (the reference's two masked assignments leave an

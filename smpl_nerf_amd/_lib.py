@@ -146,6 +146,7 @@ SIGNATURES = {
     # the vertex_sphere model: ray-mesh hits (csrc/ray_mesh.hip) and the sphere warp (csrc/vertex_sphere.hip)
     "snerf_ray_mesh_workspace_bytes": (c_int64, [c_int]),
     "snerf_ray_mesh_hits_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, c_int64, _P]),
+    "snerf_ray_mesh_first_hit_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     "snerf_vertex_sphere_warp_f32": (c_int, [_P, _P, _P, c_int64, c_int, c_float, c_int, _P, _P, _P, _P]),
     # image scores: SSIM with its backward and the squared error of MSE / PSNR (csrc/ssim.hip)
     "snerf_ssim_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int]),

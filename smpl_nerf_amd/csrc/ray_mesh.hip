@@ -14,6 +14,13 @@
 // products and sums kept apart (-ffp-contract=off) - against 36 bytes per face from the scalar cache per WAVE, four faces per wait;
 // the three divisions of the rule run only for the pairs that pass a test on u and v formed with the hardware reciprocal, widened
 // by 1e-5 so that it never decides: the decision is taken on the divided values.
+//
+// The first hit (render.py:222-319, get_warp: one intersector call, then two Python loops over the rays): the same walk and the same
+// pair rule (rm_pair below, shared by both kernels), but a lane keeps (t, face, u, v) of its nearest hit, replaced only on a strict
+// t <.  A wave walks its slice in ascending face order, the slices ascend with the wave index and wave 0 merges in wave order with the
+// same strict <, so equal t goes to the smaller face index.  The face index is the walk's own counter.  With `canon` wave 0 then
+// gathers, per hit ray, the three indices of its face and nine floats of the canonical body: depth = t |d| and
+// warp = (ca + u (cb - ca) + v (cc - ca)) - (o + d t).  The extra state is written inside the hit branch only.
 #include <math.h>
 
 #include "pair_walk.h"
@@ -58,6 +65,38 @@ __device__ __forceinline__ void rm_insert(float (&list)[KC], float t) {
 
 __device__ __forceinline__ float dot3(float x0, float x1, float x2, float y0, float y1, float y2) { return x0 * y0 + x1 * y1 + x2 * y2; }
 
+// one ray of a lane
+struct RmRay {
+    float ox, oy, oz, dx, dy, dz;
+};
+
+__device__ __forceinline__ RmRay rm_load_ray(const float *origins, const float *dirs, int64_t rr) {
+    return {origins[rr * 3 + 0], origins[rr * 3 + 1], origins[rr * 3 + 2], dirs[rr * 3 + 0], dirs[rr * 3 + 1], dirs[rr * 3 + 2]};
+}
+
+// The pair rule, for both kernels: the ray against T, the nine floats (a, e1, e2) of one face at a wave-uniform address;
+// hit(t, u, v) runs for a pair that is one.
+template <class Hit>
+__device__ __forceinline__ void rm_pair(const RmRay &y, const float *T, Hit &&hit) {
+    const float px = y.dy * T[8] - y.dz * T[7], py = y.dz * T[6] - y.dx * T[8], pz = y.dx * T[7] - y.dy * T[6];   // p = d x e2
+    const float det = dot3(T[3], T[4], T[5], px, py, pz);
+    const float sx = y.ox - T[0], sy = y.oy - T[1], sz = y.oz - T[2];
+    const float un = dot3(sx, sy, sz, px, py, pz);
+    const float qx = sy * T[5] - sz * T[4], qy = sz * T[3] - sx * T[5], qz = sx * T[4] - sy * T[3];   // q = s x e1
+    const float vn = dot3(y.dx, y.dy, y.dz, qx, qy, qz);
+    // the wide test: u and v through the hardware reciprocal (1 ulp), 1e-5 to spare; a tiny det goes to the exact rule as it is
+    const float inv = __builtin_amdgcn_rcpf(det);
+    const float ur = un * inv, vr = vn * inv;
+    const bool maybe = (ur >= -1e-5f && vr >= -1e-5f && ur + vr <= 1.f + 1e-5f) || fabsf(det) < 1e-30f;
+    if (maybe && det != 0.f) {
+        const float u = un / det, v = vn / det;
+        if (u >= 0.f && v >= 0.f && u + v <= 1.f) {
+            const float t = dot3(T[6], T[7], T[8], qx, qy, qz) / det;
+            if (t > 0.f) hit(t, u, v);
+        }
+    }
+}
+
 template <int KC>
 __global__ __launch_bounds__(RM_WAVES * 64) void ray_mesh_hits_kernel(RmArgs A) {
     __shared__ float part[RM_WAVES][KC][WAVE];
@@ -65,36 +104,18 @@ __global__ __launch_bounds__(RM_WAVES * 64) void ray_mesh_hits_kernel(RmArgs A) 
     const int lane = lane_id(), wave = wave_index();
     const int64_t r = (int64_t)blockIdx.x * WAVE + lane;
     const bool valid = r < A.R;
-    const int64_t rr = tail_index(r, A.R, valid);
-    const float ox = A.origins[rr * 3 + 0], oy = A.origins[rr * 3 + 1], oz = A.origins[rr * 3 + 2];
-    const float dx = A.dirs[rr * 3 + 0], dy = A.dirs[rr * 3 + 1], dz = A.dirs[rr * 3 + 2];
+    const RmRay y = rm_load_ray(A.origins, A.dirs, tail_index(r, A.R, valid));
     const Slice sl = wave_slice(A.F, RM_WAVES, wave);
     float list[KC];
 #pragma unroll
     for (int i = 0; i < KC; ++i) list[i] = INFINITY;
     int hits = 0;
 
-    auto pair = [&](const float *T) {   // T: the nine floats of one face, wave-uniform
-        const float px = dy * T[8] - dz * T[7], py = dz * T[6] - dx * T[8], pz = dx * T[7] - dy * T[6];   // p = d x e2
-        const float det = dot3(T[3], T[4], T[5], px, py, pz);
-        const float sx = ox - T[0], sy = oy - T[1], sz = oz - T[2];
-        const float un = dot3(sx, sy, sz, px, py, pz);
-        const float qx = sy * T[5] - sz * T[4], qy = sz * T[3] - sx * T[5], qz = sx * T[4] - sy * T[3];   // q = s x e1
-        const float vn = dot3(dx, dy, dz, qx, qy, qz);
-        // the wide test: u and v through the hardware reciprocal (1 ulp), 1e-5 to spare; a tiny det goes to the exact rule as it is
-        const float inv = __builtin_amdgcn_rcpf(det);
-        const float ur = un * inv, vr = vn * inv;
-        const bool maybe = (ur >= -1e-5f && vr >= -1e-5f && ur + vr <= 1.f + 1e-5f) || fabsf(det) < 1e-30f;
-        if (maybe && det != 0.f) {
-            const float u = un / det, v = vn / det;
-            if (u >= 0.f && v >= 0.f && u + v <= 1.f) {
-                const float t = dot3(T[6], T[7], T[8], qx, qy, qz) / det;
-                if (t > 0.f) {
-                    ++hits;
-                    rm_insert<KC>(list, t);
-                }
-            }
-        }
+    auto pair = [&](const float *T) {
+        rm_pair(y, T, [&](float t, float, float) {
+            ++hits;
+            rm_insert<KC>(list, t);
+        });
     };
 
     // (the walk indexes tri in 32 bits: the host refuses 9 F at 2^31 and above)
@@ -122,6 +143,64 @@ __global__ __launch_bounds__(RM_WAVES * 64) void ray_mesh_hits_kernel(RmArgs A) 
         if (i < A.K) A.t_hits[r * A.K + i] = list[i];
 }
 
+struct RmFirstArgs {
+    const float *origins, *dirs, *tri, *canon;   // canon [V, 3] or null: then warp and depth are null too
+    const int32_t *faces;
+    float *t, *uv, *warp, *depth;
+    int32_t *face;
+    int64_t R;
+    int F;
+};
+
+__global__ __launch_bounds__(RM_WAVES * 64) void ray_mesh_first_hit_kernel(RmFirstArgs A) {
+    __shared__ float part[RM_WAVES][4][WAVE];   // t, face (its bits), u, v of each wave's nearest hit
+    const int lane = lane_id(), wave = wave_index();
+    const int64_t r = (int64_t)blockIdx.x * WAVE + lane;
+    const bool valid = r < A.R;
+    const RmRay y = rm_load_ray(A.origins, A.dirs, tail_index(r, A.R, valid));
+    const Slice sl = wave_slice(A.F, RM_WAVES, wave);
+    float best = INFINITY, bu = 0.f, bv = 0.f;
+    int bf = -1;
+
+    auto pair = [&](int f, const float *T) {
+        rm_pair(y, T, [&](float t, float u, float v) {
+            if (t < best) best = t, bf = f, bu = u, bv = v;   // strict: of equal t the face seen first, the smaller index, stays
+        });
+    };
+
+    walk4<9>(
+        A.tri, sl.lo, sl.hi,
+        [&](int f, const float *T) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pair(f + j, T + 9 * j);
+        },
+        [&](int f, const float *T) { pair(f, T); });
+
+    put_partials(part[wave], lane, best, __int_as_float(bf), bu, bv);
+    __syncthreads();
+    if (wave != 0 || !valid) return;
+    for (int w = 1; w < RM_WAVES; ++w)   // in wave order = ascending face order
+        if (part[w][0][lane] < best) best = part[w][0][lane], bf = __float_as_int(part[w][1][lane]), bu = part[w][2][lane], bv = part[w][3][lane];
+    A.t[r] = best;
+    A.face[r] = bf;
+    A.uv[r * 2 + 0] = bu;
+    A.uv[r * 2 + 1] = bv;
+    if (!A.canon) return;
+    float wx = 0.f, wy = 0.f, wz = 0.f, depth = 0.f;
+    if (bf >= 0) {
+        const float *ca = A.canon + (int64_t)A.faces[bf * 3 + 0] * 3, *cb = A.canon + (int64_t)A.faces[bf * 3 + 1] * 3,
+                    *cc = A.canon + (int64_t)A.faces[bf * 3 + 2] * 3;
+        depth = best * sqrtf(dist2(y.dx, y.dy, y.dz));
+        wx = ((ca[0] + bu * (cb[0] - ca[0])) + bv * (cc[0] - ca[0])) - (y.ox + y.dx * best);
+        wy = ((ca[1] + bu * (cb[1] - ca[1])) + bv * (cc[1] - ca[1])) - (y.oy + y.dy * best);
+        wz = ((ca[2] + bu * (cb[2] - ca[2])) + bv * (cc[2] - ca[2])) - (y.oz + y.dz * best);
+    }
+    A.depth[r] = depth;
+    A.warp[r * 3 + 0] = wx;
+    A.warp[r * 3 + 1] = wy;
+    A.warp[r * 3 + 2] = wz;
+}
+
 template <int KC>
 static void rm_launch(const RmArgs &A, unsigned blocks, hipStream_t s) {
     hipLaunchKernelGGL(ray_mesh_hits_kernel<KC>, dim3(blocks), dim3(RM_WAVES * 64), 0, s, A);
@@ -135,28 +214,54 @@ extern "C" int64_t snerf_ray_mesh_workspace_bytes(int F) {
     return (int64_t)F * 9 * (int64_t)sizeof(float);
 }
 
+// The checks both entries make, in one order; bad_pointers: what is wrong with the entry's own pointers, or null - looked at only
+// with R > 0.  On SNERF_OK with R > 0 the pre-pass has been launched and `blocks` is the grid.
+static int rm_prepare(const char *op, const char *bad_pointers, const float *vertices, const int32_t *faces, int64_t R, int V, int F,
+                      void *workspace, int64_t workspace_bytes, hipStream_t s, int64_t &blocks) {
+    using namespace snerf;
+    if (int rc = check_walk_count(op, "V", V, 3)) return rc;
+    if (int rc = check_walk_count(op, "F", F, 9)) return rc;
+    if (R == 0) return SNERF_OK;
+    if (bad_pointers) return fail(SNERF_E_BADARG, "%s: %s", op, bad_pointers);
+    if (!workspace || workspace_bytes < (int64_t)F * 9 * (int64_t)sizeof(float))
+        return fail(SNERF_E_BADARG, "%s: workspace missing or smaller than snerf_ray_mesh_workspace_bytes()", op);
+    if (int rc = chunk_blocks(op, "R", R, blocks)) return rc;
+    hipLaunchKernelGGL(ray_mesh_faces_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, vertices, faces, F, (float *)workspace);
+    return SNERF_OK;
+}
+
 extern "C" int snerf_ray_mesh_hits_f32(const float *origins, const float *dirs, const float *vertices, const int32_t *faces, int64_t R,
                                        int V, int F, int max_hits, float *t_hits, int32_t *n_hits, void *workspace,
                                        int64_t workspace_bytes, snerf_stream_t stream) {
     using namespace snerf;
     if (R < 0) return fail(SNERF_E_BADARG, "ray_mesh_hits: R must not be negative");
     if (max_hits < 1 || max_hits > RM_MAX_HITS) return fail(SNERF_E_BADARG, "ray_mesh_hits: max_hits must be 1 .. %d", RM_MAX_HITS);
-    if (int rc = check_walk_count("ray_mesh_hits", "V", V, 3)) return rc;
-    if (int rc = check_walk_count("ray_mesh_hits", "F", F, 9)) return rc;
-    if (R == 0) return SNERF_OK;
-    if (!origins || !dirs || !vertices || !faces || !t_hits || !n_hits)
-        return fail(SNERF_E_BADARG, "ray_mesh_hits: null pointer (origins, dirs, vertices, faces, t_hits, n_hits)");
-    if (!workspace || workspace_bytes < (int64_t)F * 9 * (int64_t)sizeof(float))
-        return fail(SNERF_E_BADARG, "ray_mesh_hits: workspace missing or smaller than snerf_ray_mesh_workspace_bytes()");
-    int64_t blocks;
-    if (int rc = chunk_blocks("ray_mesh_hits", "R", R, blocks)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    float *tri = (float *)workspace;
-    hipLaunchKernelGGL(ray_mesh_faces_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, vertices, faces, F, tri);
-    RmArgs A{origins, dirs, tri, t_hits, n_hits, R, F, max_hits};
+    int64_t blocks = 0;
+    const char *bad = !origins || !dirs || !vertices || !faces || !t_hits || !n_hits ? "null pointer (origins, dirs, vertices, faces, t_hits, n_hits)" : nullptr;
+    if (int rc = rm_prepare("ray_mesh_hits", bad, vertices, faces, R, V, F, workspace, workspace_bytes, s, blocks)) return rc;
+    if (R == 0) return SNERF_OK;
+    RmArgs A{origins, dirs, (const float *)workspace, t_hits, n_hits, R, F, max_hits};
     if (max_hits == 1) rm_launch<1>(A, (unsigned)blocks, s);
     else if (max_hits <= 4) rm_launch<4>(A, (unsigned)blocks, s);
     else if (max_hits <= 8) rm_launch<8>(A, (unsigned)blocks, s);
     else rm_launch<16>(A, (unsigned)blocks, s);
     return check_launch("ray_mesh_hits");
+}
+
+extern "C" int snerf_ray_mesh_first_hit_f32(const float *origins, const float *dirs, const float *vertices, const int32_t *faces, int64_t R,
+                                            int V, int F, const float *canon, float *t, int32_t *face, float *uv, float *warp, float *depth,
+                                            void *workspace, int64_t workspace_bytes, snerf_stream_t stream) {
+    using namespace snerf;
+    if (R < 0) return fail(SNERF_E_BADARG, "ray_mesh_first_hit: R must not be negative");
+    hipStream_t s = (hipStream_t)stream;
+    int64_t blocks = 0;
+    const char *bad = !origins || !dirs || !vertices || !faces || !t || !face || !uv ? "null pointer (origins, dirs, vertices, faces, t, face, uv)"
+                      : (canon && warp && depth) || (!canon && !warp && !depth) ? nullptr
+                                                                                : "canon, warp and depth must be all null or all non-null";
+    if (int rc = rm_prepare("ray_mesh_first_hit", bad, vertices, faces, R, V, F, workspace, workspace_bytes, s, blocks)) return rc;
+    if (R == 0) return SNERF_OK;
+    RmFirstArgs A{origins, dirs, (const float *)workspace, canon, faces, t, uv, warp, depth, face, R, F};
+    hipLaunchKernelGGL(ray_mesh_first_hit_kernel, dim3((unsigned)blocks), dim3(RM_WAVES * 64), 0, s, A);
+    return check_launch("ray_mesh_first_hit");
 }

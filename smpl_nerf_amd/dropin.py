@@ -46,6 +46,7 @@ REPLACEMENTS = {
     "models.append_to_nerf_pipeline": {"AppendToNerfPipeline": pipelines.AppendToNerfPipeline},
     "models.dynamic_pipeline": {"DynamicPipeline": pipelines.DynamicPipeline},
     "models.vertex_sphere_pipeline": {"VertexSpherePipeline": pipelines.VertexSpherePipeline},
+    "models.singe_sample_pipeline": {"SmplPipeline": pipelines.SingleSamplePipeline},      # (the reference's spelling)
 }
 _NAMES = {name: obj for table in REPLACEMENTS.values() for name, obj in table.items()}
 _originals = {}      # name -> the reference's own object (once seen), to recognise `from x import y` copies

@@ -10,6 +10,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     GaussianMixture / gaussian_mixture_pdf   utils.py:72-111 (the canonical-density term of SmplNerfSolver's loss)
     smpl_lbs            the body model the reference takes from smplx (train.py:214): SMPL linear blend skinning
     ray_mesh_hits / vertex_sphere_warp   datasets/vertex_sphere_dataset.py:84-116 (trimesh's intersector) and :128-159 (the true warp)
+    ray_mesh_first_hit                   render.py:222-319 (get_warp: the depth and the true warp of the single-sample model)
     ssim / image_scores util/scores.py:88-173 (ssim) and :11-48 (img2mse, img2psnr): the scores of print_scores, on the device
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
@@ -686,6 +687,34 @@ def smpl_lbs(model_buffers, betas, body_pose, global_orient=None):
 # ------------------------------------------------------------------------------------------------
 # The vertex_sphere model (datasets/vertex_sphere_dataset.py:84-160): ray-mesh hits and the sphere warp
 # ------------------------------------------------------------------------------------------------
+def _ray_mesh_inputs(op, origins, directions, vertices, faces, faces_checked):
+    """The checks of both ray-mesh operators, in one order -> (o, d, vertices, faces) detached and contiguous."""
+    # the table's own checks come first and need no device: a bad table is refused wherever it lives
+    if faces.dtype != torch.int32:
+        raise RuntimeError(f"{op}: `faces` must be int32 (got {faces.dtype})")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise RuntimeError(f"{op}: vertices {tuple(vertices.shape)} must be [V >= 1, 3] and faces {tuple(faces.shape)} [F >= 1, 3]")
+    V = vertices.shape[0]
+    if not faces_checked:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= V:
+            raise RuntimeError(f"{op}: faces index vertices {lo} .. {hi}, outside [0, {V})")
+    for nm, t in (("origins", origins), ("directions", directions), ("vertices", vertices)):
+        _need_cuda(nm, t)
+    if not faces.is_cuda:
+        raise RuntimeError(f"smpl_nerf_amd: `faces` must live on the GPU (got {faces.device}); there is no CPU path")
+    if origins.dim() != 2 or origins.shape[1] != 3 or directions.shape != origins.shape:
+        raise RuntimeError(f"{op}: origins {tuple(origins.shape)} and directions {tuple(directions.shape)} must both be [R, 3]")
+    return tuple(t.detach().contiguous() for t in (origins, directions, vertices, faces))
+
+
+def _ray_mesh_workspace(lib, F, dev):
+    nbytes = lib.snerf_ray_mesh_workspace_bytes(F)
+    if nbytes < 0:
+        check(-1, "snerf_ray_mesh_workspace_bytes")
+    return torch.empty((nbytes,), device=dev, dtype=torch.uint8), nbytes
+
+
 def ray_mesh_hits(origins, directions, vertices, faces, max_hits: int = 1, faces_checked: bool = False):
     """All hits of R rays on one triangle mesh (csrc/ray_mesh.hip; include/smplnerf.h states the rule: two-sided Moeller-Trumbore in
     fp32): what the reference asks trimesh's RayMeshIntersector for one ray at a time (:85-89).  origins, directions [R,3] fp32,
@@ -693,37 +722,47 @@ def ray_mesh_hits(origins, directions, vertices, faces, max_hits: int = 1, faces
     order, padded with +inf, in units of |direction|; n_hits [R] int32: the number of hits, which may exceed K).  The face table
     is range-checked against V before anything is launched (one device reduction and a host read); faces_checked=True skips
     that for a table that has been through it.  The workspace (36 F bytes) is allocated here.  Nothing of size R F is built."""
-    # the table's own checks come first and need no device: a bad table is refused wherever it lives
-    if faces.dtype != torch.int32:
-        raise RuntimeError(f"ray_mesh_hits: `faces` must be int32 (got {faces.dtype})")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-        raise RuntimeError(f"ray_mesh_hits: vertices {tuple(vertices.shape)} must be [V >= 1, 3] and faces {tuple(faces.shape)} [F >= 1, 3]")
-    R, V, F, dev = origins.shape[0], vertices.shape[0], faces.shape[0], origins.device
-    if not faces_checked:
-        lo, hi = (int(x) for x in torch.aminmax(faces))
-        if lo < 0 or hi >= V:
-            raise RuntimeError(f"ray_mesh_hits: faces index vertices {lo} .. {hi}, outside [0, {V})")
-    for nm, t in (("origins", origins), ("directions", directions), ("vertices", vertices)):
-        _need_cuda(nm, t)
-    if not faces.is_cuda:
-        raise RuntimeError(f"smpl_nerf_amd: `faces` must live on the GPU (got {faces.device}); there is no CPU path")
-    if origins.dim() != 2 or origins.shape[1] != 3 or directions.shape != origins.shape:
-        raise RuntimeError(f"ray_mesh_hits: origins {tuple(origins.shape)} and directions {tuple(directions.shape)} must both be [R, 3]")
+    o, d, vt, fc = _ray_mesh_inputs("ray_mesh_hits", origins, directions, vertices, faces, faces_checked)
+    R, V, F, dev = o.shape[0], vt.shape[0], fc.shape[0], o.device
     K = int(max_hits)
     if not 1 <= K <= 16:
         raise RuntimeError(f"ray_mesh_hits: max_hits must be 1 .. 16, got {max_hits}")
-    o, d, vt, fc = (t.detach().contiguous() for t in (origins, directions, vertices, faces))
     t_hits = torch.empty((R, K), device=dev, dtype=torch.float32)
     n_hits = torch.empty((R,), device=dev, dtype=torch.int32)
     lib = _lib.load()
-    nbytes = lib.snerf_ray_mesh_workspace_bytes(F)
-    if nbytes < 0:
-        check(-1, "snerf_ray_mesh_workspace_bytes")
-    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    ws, nbytes = _ray_mesh_workspace(lib, F, dev)
     with torch.cuda.device(dev), _lib.timed(f"ray_mesh_hits[F={F},K={K}]"):
         check(lib.snerf_ray_mesh_hits_f32(ptr(o), ptr(d), ptr(vt), ptr(fc), R, V, F, K, ptr(t_hits), ptr(n_hits), ptr(ws), nbytes,
                                           current_stream()), "snerf_ray_mesh_hits_f32")
     return t_hits, n_hits
+
+
+def ray_mesh_first_hit(origins, directions, vertices, faces, canon=None, faces_checked: bool = False):
+    """The first hit of R rays on one triangle mesh, with its face and where on it (csrc/ray_mesh.hip, the rule and the walk of
+    ray_mesh_hits; include/smplnerf.h, snerf_ray_mesh_first_hit_f32): render.py:222-319's get_warp without its two Python loops
+    over the rays.  Inputs and checks as ray_mesh_hits -> (t [R] fp32: the smallest hit parameter, +inf on a miss; face [R] int32:
+    the face hit, -1 on a miss, the smaller index where two faces are hit at equal t; uv [R,2] fp32: u and v of the hit - the
+    point is (1 - u - v) a + u b + v c - zero on a miss).  With canon [V,3], the same mesh in the canonical pose, also
+    (warp [R,3]: the same surface point of canon minus the hit point; depth [R]: t |direction|), both zero on a miss.  The outputs
+    are data: no grad_fn, whatever the inputs require.  Nothing of size R F is built."""
+    if canon is not None and canon.shape != vertices.shape:
+        raise RuntimeError(f"ray_mesh_first_hit: canon {tuple(canon.shape)} must have the shape of vertices {tuple(vertices.shape)}")
+    o, d, vt, fc = _ray_mesh_inputs("ray_mesh_first_hit", origins, directions, vertices, faces, faces_checked)
+    R, V, F, dev = o.shape[0], vt.shape[0], fc.shape[0], o.device
+    cn = None
+    if canon is not None:
+        _need_cuda("canon", canon)
+        cn = canon.detach().contiguous()
+    t = torch.empty((R,), device=dev, dtype=torch.float32)
+    face = torch.empty((R,), device=dev, dtype=torch.int32)
+    uv = torch.empty((R, 2), device=dev, dtype=torch.float32)
+    warp, depth = (torch.empty((R, 3), device=dev, dtype=torch.float32), torch.empty((R,), device=dev, dtype=torch.float32)) if cn is not None else (None, None)
+    lib = _lib.load()
+    ws, nbytes = _ray_mesh_workspace(lib, F, dev)
+    with torch.cuda.device(dev), _lib.timed(f"ray_mesh_first_hit[F={F}]"):
+        check(lib.snerf_ray_mesh_first_hit_f32(ptr(o), ptr(d), ptr(vt), ptr(fc), R, V, F, ptr(cn), ptr(t), ptr(face), ptr(uv), ptr(warp),
+                                               ptr(depth), ptr(ws), nbytes, current_stream()), "snerf_ray_mesh_first_hit_f32")
+    return (t, face, uv) if cn is None else (t, face, uv, warp, depth)
 
 
 def vertex_sphere_warp(samples, goal, canon, radius, by_mean: bool = False, want_indices: bool = False):

@@ -453,6 +453,33 @@ class VertexSpherePipeline(NerfPipeline):
         return rgb, rgb, warp, ray_samples, warped, densities                                      # :48
 
 
+class SingleSamplePipeline(NerfPipeline):
+    """models/singe_sample_pipeline.py:6-40 drop-in (SmplPipeline; the module name is the reference's spelling): a surface colour
+    field.  Every ray carries ONE sample, placed on the body, and its true warp (single_sample.SingleSampleRays computes both with
+    ops.ray_mesh_first_hit): data = [ray_sample [B,3], ray_translation, ray_direction, goal_pose, warp [B,3], rgb_truth].
+    warped = ray_sample + warp (:29), the view direction warped - o (:32), the coarse net on their encodings (the fused
+    encode + MLP with one sample per ray) and rgb = sigmoid(raw[..., :3]) (:39): no density, no compositing.  Returns (rgb, rgb).
+    The constructor is the reference's: there is no fine net."""
+
+    def __init__(self, model_coarse, args, position_encoder, direction_encoder):
+        super().__init__(model_coarse, model_coarse, args, position_encoder, direction_encoder)
+
+    def _single_call_ok(self, data) -> bool:
+        return False      # (no single-call entry renders without compositing)
+
+    def render_rays(self, data):
+        with torch.no_grad():
+            return self._forward_calls(data)
+
+    def _forward_calls(self, data):
+        ray_sample, ray_translation, _, _, warp, _ = data
+        warped = ray_sample + warp                                                                 # :29
+        raw = self.model_coarse.forward_fused(warped, warped - ray_translation, 1, self.position_encoder,
+                                              self.direction_encoder)                              # :30-38
+        rgb = torch.sigmoid(raw[..., :3])                                                          # :39
+        return rgb, rgb                                                                            # :40
+
+
 class AppendSmplParamsPipeline(NerfPipeline):
     """models/append_smpl_params_pipeline.py:7-91 drop-in (the paper's headline model): NerfPipeline whose nets
     read [pose | PE(x) | PE(d)] rows, the pose being the 69 SMPL body-pose parameters of the ray's frame,
