@@ -58,7 +58,10 @@ extern "C" {
                              auxiliary stream: small chunks run the coarse chain beside the fine chain); snerf_mlp_desc.width
                              up to 512
                              0.1.9: + snerf_nerf_train_step_dp_ig_f32; the data-parallel steps issue the same collectives on every
-                             rank whatever its batch size (B == 0 included); SNERF_RCCL_LIB; snerf_linear_* / snerf_relu_bwd_f32 (any --netwidth) */
+                             rank whatever its batch size (B == 0 included); SNERF_RCCL_LIB; snerf_linear_* / snerf_relu_bwd_f32 (any --netwidth)
+                             (same version): + snerf_mlp_packed_infer_floats, snerf_mlp_pack_infer_f32, snerf_mlp_fwd_infer_f32 and
+                             precision SNERF_FP32_INFER of the render entries: fp32 inference on a stream with the activation-free
+                             layers composed (13 % fewer matrix operations); existing entries and streams are unchanged */
 
 #define SNERF_OK 0
 #define SNERF_E_BADARG (-1)   /* null pointer, negative size, unsupported shape */
@@ -256,6 +259,29 @@ SNERF_API int64_t snerf_mlp_fold_workspace_bytes(const snerf_mlp_desc *desc, int
 SNERF_API int snerf_mlp_fwd_ws_f32(const snerf_mlp_desc *desc, const float *packed, const float *x, const float *dirs,
                          int dirs_per_sample, const float *add, int64_t n, int samples_per_ray, float *raw, void *workspace,
                          int64_t workspace_bytes, snerf_stream_t stream);
+
+/* ---- fp32 inference on the composed stream ------------------------------------------------------------------
+ * additional_linear_layer, sigma_out_layer, directional_input and directional_net[0] (models/render_ray_net.py:51-59) follow
+ * each other without an activation: for fixed weights, sigma = (w_s W_a) h + (w_s b_a + b_s) and the input of the last ReLU
+ * = (W_n W_d1 W_a) h + (W_n W_d2) PE(d) + (W_n (W_d1 b_a + b_d) + b_n), h the last trunk activation.  The inference stream
+ * holds the trunk and the rgb head as snerf_mlp_pack_f32 does and these two composed layers (every composed entry a float64
+ * sum in a fixed order, rounded once to fp32): 67 slabs instead of 77 for the default net, 2088 instead of 2408 matrix
+ * operations per 16 samples - 2 x 525 952 FLOP per evaluation executed for the reference network's 1 215 744.  Results
+ * differ from snerf_mlp_fwd_f32's at round-off level (same error class against float64).  Re-pack after every weight update.
+ * snerf_mlp_packed_infer_floats: floats of stream + scratch (float64 intermediates behind the stream: the library
+ * allocates nothing); 0 - not an error - when there is no inference stream for the net (widths above 256,
+ * SNERF_MLP_COMPOSE=0 in the environment): the caller then uses snerf_mlp_pack_f32 / snerf_mlp_fwd_ws_f32.
+ * snerf_mlp_fwd_infer_f32: arguments and per-ray fold as snerf_mlp_fwd_ws_f32 (workspace NULL: the per-sample form);
+ * small calls equal the same rows of a large call bit for bit.  No training forward reads this stream. */
+SNERF_API int64_t snerf_mlp_packed_infer_floats(const snerf_mlp_desc *desc);
+SNERF_API int snerf_mlp_pack_infer_f32(const snerf_mlp_desc *desc, const float *params_flat, float *packed_infer,
+                             snerf_stream_t stream);
+SNERF_API int snerf_mlp_fwd_infer_f32(const snerf_mlp_desc *desc, const float *packed_infer, const float *x, const float *dirs,
+                            int dirs_per_sample, const float *add, int64_t n, int samples_per_ray, float *raw, void *workspace,
+                            int64_t workspace_bytes, snerf_stream_t stream);
+/* `precision` of snerf_render_rays_f32 / _add_f32 / _smpl_f32: the fp32 kernels, packed_* from snerf_mlp_pack_infer_f32
+ * (the warp net of _smpl_f32 runs its fp32 kernel on snerf_warp_pack_f32's stream). */
+#define SNERF_FP32_INFER 32
 
 /* ---- a2 on the bf16 matrix cores with fp32-class accuracy (split-bf16, inference) -------------------------
  * Every fp32 operand is split into nsplit bf16 parts and the cross terms are accumulated in fp32:
@@ -599,7 +625,8 @@ SNERF_API int snerf_raygen_f64(const double *poses, int64_t n_frames, int H, int
 /* ---- a3: the whole NerfPipeline.forward for inference in one call (models/nerf_pipeline.py:14-67) -------------
  * Five launches on `stream`: fused encode+MLP (coarse) -> composite -> inverse-CDF sampler + merge + points ->
  * fused encode+MLP (fine) -> composite.  precision: 0 = fp32 kernel (packed_* from snerf_mlp_pack_f32), 2 / 3 / 16 =
- * split-bf16 / split-fp16 with that nsplit (packed_* from snerf_mlp_pack_bf16).  Inputs as the Solver hands them over
+ * split-bf16 / split-fp16 with that nsplit (packed_* from snerf_mlp_pack_bf16), SNERF_FP32_INFER (32) = fp32 kernel, packed_*
+ * from snerf_mlp_pack_infer_f32.  Inputs as the Solver hands them over
  * (solver/nerf_solver.py:77-81): ray_samples [B,Nc,3], rays_o [B,3], rays_d [B,3], z_vals [B,Nc]; u [Nf] =
  * linspace(0,1,Nf) (utils.py:204-205); noise_coarse [B,Nc] / noise_fine [B,Nc+Nf] nullable (sigma noise,
  * utils.py:171-173).  Nf == 0 is run_fine = 0: the fine outputs are copies of the coarse ones (:43-44).

@@ -12,7 +12,8 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libsmplnerf_hip.so")
 SPLIT_F16X3 = 16   # include/smplnerf.h SNERF_SPLIT_F16X3: nsplit / precision code of the two-part fp16 kernel
-REFERENCE_SUM = 0x100   # include/smplnerf.h SNERF_REFERENCE_SUM: ORed into a precision, the sampler sums in torch's CPU order
+FP32_INFER = 32    # include/smplnerf.h SNERF_FP32_INFER: precision code of the render entries - fp32 kernels, composed inference streams
+REFERENCE_SUM = 0x100  # include/smplnerf.h SNERF_REFERENCE_SUM: ORed into a precision, the sampler sums in torch's CPU order
 
 SNERF_OK = 0
 
@@ -167,6 +168,10 @@ SIGNATURES = {
                                       c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "snerf_mlp_fold_workspace_bytes": (c_int64, [POINTER(MlpDesc), c_int64, c_int]),
     "snerf_mlp_fwd_ws_f32": (c_int, [POINTER(MlpDesc), _P, _P, _P, c_int, _P, c_int64, c_int, _P, _P, c_int64, _P]),
+    # fp32 inference on the composed stream (csrc/mlp_plan.h: make_plan_infer)
+    "snerf_mlp_packed_infer_floats": (c_int64, [POINTER(MlpDesc)]),
+    "snerf_mlp_pack_infer_f32": (c_int, [POINTER(MlpDesc), _P, _P, _P]),
+    "snerf_mlp_fwd_infer_f32": (c_int, [POINTER(MlpDesc), _P, _P, _P, c_int, _P, c_int64, c_int, _P, _P, c_int64, _P]),
     "snerf_warp_fold_workspace_bytes": (c_int64, [POINTER(WarpDesc), c_int64, c_int]),
     "snerf_warp_fwd_ws_f32": (c_int, [POINTER(WarpDesc), _P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, c_int64, _P]),
     "snerf_dy_contract_scratch_floats": (c_int64, [c_int64, c_int, c_int]),

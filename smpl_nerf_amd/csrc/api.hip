@@ -77,6 +77,7 @@ const Tuning &tuning() {
         Tuning k;
         k.warp_fold = flag("SNERF_WARP_FOLD", true);
         k.mlp_fold = flag("SNERF_MLP_FOLD", true);
+        k.mlp_compose = flag("SNERF_MLP_COMPOSE", true);
         return k;
     }();
     return t;

@@ -21,7 +21,10 @@
 //     rolling on from tile to tile;
 //   * positional encodings are evaluated in registers, straight into B-operand layout, with
 //     full-range sincosf (arguments reach 2^9*|x|); they are recomputed at the skip layer instead of
-//     being kept live.
+//     being kept live;
+//   * inference may run on a second, composed stream (mlp_plan.h: make_plan_infer; snerf_mlp_pack_infer_f32 below): the four
+//     layers behind the trunk that follow each other without an activation as two affine maps of the trunk's output - the
+//     same kernels with FwdArgs::composed set, 2088 instead of 2408 (k-block, tile) units per 16 samples of the default net.
 #include <stdlib.h>
 
 #include "mlp_device.h"
@@ -36,7 +39,7 @@ namespace snerf {
 // streams are re-packed behind Adam)
 constexpr int PACK_PARTS = (SLAB_FLOATS + 255) / 256;
 __global__ __launch_bounds__(256) void mlp_pack_kernel(Plan P, const float *__restrict__ params,
-                                                       float *__restrict__ packed) {
+                                                       float *__restrict__ packed, const float *__restrict__ composed_params) {
     const int slab = blockIdx.x / PACK_PARTS;
     const int e = (blockIdx.x - slab * PACK_PARTS) * 256 + threadIdx.x;
     if (e >= SLAB_FLOATS) return;
@@ -49,7 +52,91 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(Plan P, const float *__re
     while (li + 1 < P.nlayers && slab >= P.layer[li + 1].first_slab) ++li;
     const Layer &Ly = P.layer[li];
     const int64_t src = fwd_slab_src(Ly, slab - Ly.first_slab, e);
-    dst[e] = src >= 0 ? params[src] : 0.f;
+    // (a composed plan: sigma' and dir-net' index the composed parameters - mlp_plan.h: make_plan_infer)
+    const float *from = (P.composed && (li == P.n_hidden + 1 || li == P.n_hidden + 2)) ? composed_params : params;
+    dst[e] = src >= 0 ? from[src] : 0.f;
+}
+
+// ---- the composed parameters of an inference stream (mlp_plan.h: make_plan_infer), from params_flat.  Every entry is a float64 sum
+// in the order of its index (products and sums rounded to float64 one by one), rounded once to fp32.  Two launches: the float64
+// intermediate M = [W_d1 W_a | W_d1 b_a + b_d] ([WD, W + 1]) first, then the entries of sigma' and dir-net'.
+struct ComposeSrc {
+    int W, WD, dir_dim;
+    int64_t wa, ba, ws, bs, wd, bd, wn, bn;   // params_flat offsets of additional_linear_layer, sigma_out_layer, directional_input, directional_net[0]
+    int64_t sig_w, sig_b, dn_w, dn_b;         // composed-parameter offsets of sigma' and dir-net'
+};
+static ComposeSrc compose_src(const Plan &R, const Plan &P) {
+    const int nh = R.n_hidden;
+    const Layer &La = R.layer[nh + 1], &Ls = R.layer[nh + 2], &Ld = R.layer[nh + 3], &Ln = R.layer[nh + 4];
+    ComposeSrc c;
+    c.W = La.n_out;
+    c.WD = Ld.n_out;
+    c.dir_dim = Ld.n_in - La.n_out;
+    c.wa = La.w_off, c.ba = La.b_off, c.ws = Ls.w_off, c.bs = Ls.b_off;
+    c.wd = Ld.w_off, c.bd = Ld.b_off, c.wn = Ln.w_off, c.bn = Ln.b_off;
+    c.sig_w = P.layer[nh + 1].w_off, c.sig_b = P.layer[nh + 1].b_off;
+    c.dn_w = P.layer[nh + 2].w_off, c.dn_b = P.layer[nh + 2].b_off;
+    return c;
+}
+__global__ __launch_bounds__(256) void mlp_compose_mid_kernel(ComposeSrc c, const float *__restrict__ params, double *__restrict__ mid) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= c.WD * (c.W + 1)) return;
+    const int j = e / (c.W + 1), k = e - j * (c.W + 1);
+    const float *wd = params + c.wd + (int64_t)j * (c.W + c.dir_dim);
+    double sum = 0.0;
+    if (k < c.W) {
+        for (int m = 0; m < c.W; ++m) sum += (double)wd[m] * (double)params[c.wa + (int64_t)m * c.W + k];
+    } else {
+        for (int m = 0; m < c.W; ++m) sum += (double)wd[m] * (double)params[c.ba + m];
+        sum += (double)params[c.bd + j];
+    }
+    mid[e] = sum;
+}
+__global__ __launch_bounds__(256) void mlp_compose_out_kernel(ComposeSrc c, const float *__restrict__ params, const double *__restrict__ mid,
+                                                              float *__restrict__ out) {
+    const int n_in = c.W + c.dir_dim;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int n_sig = c.W + 1, n_dn = c.WD * (n_in + 1);
+    if (e >= n_sig + n_dn) return;
+    double sum = 0.0;
+    if (e < n_sig) {   // sigma' = w_s W_a, bias w_s b_a + b_s
+        const int k = e;
+        if (k < c.W) {
+            for (int m = 0; m < c.W; ++m) sum += (double)params[c.ws + m] * (double)params[c.wa + (int64_t)m * c.W + k];
+            out[c.sig_w + k] = (float)sum;
+        } else {
+            for (int m = 0; m < c.W; ++m) sum += (double)params[c.ws + m] * (double)params[c.ba + m];
+            sum += (double)params[c.bs];
+            out[c.sig_b] = (float)sum;
+        }
+        return;
+    }
+    const int q = e - n_sig, i = q / (n_in + 1), k = q - i * (n_in + 1);
+    const float *wn = params + c.wn + (int64_t)i * c.WD;
+    if (k < c.W) {            // W_n (W_d1 W_a)
+        for (int j = 0; j < c.WD; ++j) sum += (double)wn[j] * mid[(int64_t)j * (c.W + 1) + k];
+        out[c.dn_w + (int64_t)i * n_in + k] = (float)sum;
+    } else if (k < n_in) {    // W_n W_d2
+        for (int j = 0; j < c.WD; ++j) sum += (double)wn[j] * (double)params[c.wd + (int64_t)j * n_in + k];
+        out[c.dn_w + (int64_t)i * n_in + k] = (float)sum;
+    } else {                  // W_n (W_d1 b_a + b_d) + b_n
+        for (int j = 0; j < c.WD; ++j) sum += (double)wn[j] * mid[(int64_t)j * (c.W + 1) + c.W];
+        sum += (double)params[c.bn + i];
+        out[c.dn_b + i] = (float)sum;
+    }
+}
+// scratch of snerf_mlp_pack_infer_f32 behind the pad slabs of the stream: the float64 intermediate, then the composed parameters
+struct InferScratch {
+    int64_t mid, comp, total;   // float offsets from the start of the stream; floats of stream + scratch
+};
+static InferScratch infer_scratch(const Plan &R, const Plan &P) {
+    InferScratch s;
+    const int nh = R.n_hidden;
+    const int64_t mid_doubles = (int64_t)R.layer[nh + 3].n_out * (R.layer[nh + 1].n_out + 1);
+    s.mid = (int64_t)(P.total_slabs + SLAB_PAD) * SLAB_FLOATS;   // (a multiple of 8 bytes from a 16-byte aligned base)
+    s.comp = s.mid + 2 * mid_doubles;
+    s.total = (s.comp + P.comp_floats + 3) / 4 * 4;
+    return s;
 }
 
 // TRAIN additionally stores every layer input (post-activation) for the backward kernels.
@@ -69,6 +156,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     const int wave = tid >> 6;
     const int enc_pos_off = A.add_first ? A.add_dim : 0, enc_add_off = A.add_first ? 0 : A.pos_dim;
     const int enc_dir_off = A.enc_stride - A.dir_dim;  // directions = x[..., -dir_dim:] (:43)
+    const bool composed = !TRAIN && A.composed != 0;
 
     // Persistent workgroups: one per CU (the 99 / 132 KiB ring allows no more), each walking the sample tiles blockIdx.x,
     // blockIdx.x + gridDim.x, ...  The weight ring keeps rolling from one tile into the next (the stream wraps around),
@@ -107,7 +195,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
         c.enc = A.x + sc * A.enc_stride;
     } else {
         if (!PREFETCH) load_raw(tile);
-        // the one point of a tile that waits for plain loads (the prefetched inputs: a full drain, once per 77 slabs); without it
+        // the one point of a tile that waits for plain loads (the prefetched inputs: a full drain, once per pass over the stream); without it
         // hipcc waits at every use of a position in the encoder loops, draining the weight ring's DMA there
         if (PREFETCH) asm volatile("" : "+v"(raw_in[0]), "+v"(raw_in[1]), "+v"(raw_in[2]), "+v"(raw_in[3]), "+v"(raw_in[4]), "+v"(raw_in[5]));
         c.px = raw_in[0];
@@ -194,7 +282,9 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
             store_mask(A.act, A.act_mask, i + 1, A.n, sample, c.g, in);
         }
     }
-    {  // additional_linear_layer, no activation (:51)
+    // Inference on the composed stream (mlp_plan.h: make_plan_infer; uniform over the launch): additional_linear_layer and
+    // directional_net[0] are not in the stream - sigma' and dir-net' (with the ReLU of directional_net[0]) read the trunk's output
+    if (!composed) {  // additional_linear_layer, no activation (:51)
         LayerRun<T, NT, Pipe> run(pipe, lane);
         run.init(acc);
 #pragma unroll
@@ -223,12 +313,13 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
             run.step(b, accd);
         }
         run.finish();
-        copy_into(ind, accd);
+        if (composed) relu_into(ind, accd);
+        else copy_into(ind, accd);
         if (TRAIN && valid) store_tiles(A.act, A.act_h1, A.n, sample, c.g, ind);
         // lands behind the last two layers (a workgroup's last tile fetches its own inputs again: no branch around the loads)
         if (PREFETCH) load_raw(tile + gridDim.x < A.n_tiles ? tile + gridDim.x : tile);
     }
-    {  // directional_net[0] + relu (:58-59)
+    if (!composed) {  // directional_net[0] + relu (:58-59)
         LayerRun<TD, NT, Pipe> run(pipe, lane);
         run.init(accd);
 #pragma unroll
@@ -267,8 +358,8 @@ __global__ __launch_bounds__(NWAVES * 64) void mlp_fwd_fold_kernel(FwdArgs A) {
     mlp_fwd_body<WIDTH, NWAVES, false, false, true>(A);
 }
 
-int launch_pack(const Plan &P, const float *params_flat, float *packed, hipStream_t s, const char *what) {
-    hipLaunchKernelGGL(mlp_pack_kernel, dim3((P.total_slabs + SLAB_PAD) * PACK_PARTS), dim3(256), 0, s, P, params_flat, packed);
+int launch_pack(const Plan &P, const float *params_flat, float *packed, hipStream_t s, const char *what, const float *composed_params) {
+    hipLaunchKernelGGL(mlp_pack_kernel, dim3((P.total_slabs + SLAB_PAD) * PACK_PARTS), dim3(256), 0, s, P, params_flat, packed, composed_params);
     return check_launch(what);
 }
 
@@ -397,9 +488,12 @@ static int launch_fwd(const Plan &P, const FwdArgs &A, hipStream_t s) {
 
 // snerf_mlp_fwd_f32 / _fwd_ws_f32 (inference) and snerf_mlp_fwd_train_f32
 int launch_mlp_fwd(const MlpFwdCall &c) {
-    const char *what = c.train ? "mlp_fwd_train" : "mlp_fwd";
+    const char *what = c.train ? "mlp_fwd_train" : c.infer ? "mlp_fwd_infer" : "mlp_fwd";
     Plan P;
-    if (int rc = plan_for(what, c.desc, P)) return rc;
+    if (c.infer && c.train) return fail(SNERF_E_BADARG, "mlp_fwd_infer: the inference stream has no training forward");
+    if (int rc = c.infer ? plan_infer_for(what, c.desc, P) : plan_for(what, c.desc, P)) return rc;
+    if (c.infer && !tuning().mlp_compose)
+        return fail(SNERF_E_BADARG, "mlp_fwd_infer: no inference stream with SNERF_MLP_COMPOSE=0 (snerf_mlp_packed_infer_floats returns 0)");
     // the inference reads dirs_per_sample as a bit set, and refuses a bad one in an empty call as well
     if (!c.train && (c.dirs_per_sample & ~(SNERF_FWD_DIRS_PER_SAMPLE | SNERF_FWD_NO_RAY_FOLD)))
         return fail(SNERF_E_BADARG, "mlp_fwd: dirs_per_sample is a bit set of SNERF_FWD_DIRS_PER_SAMPLE | SNERF_FWD_NO_RAY_FOLD (got %d)",
@@ -460,6 +554,46 @@ extern "C" int snerf_mlp_pack_f32(const snerf_mlp_desc *desc, const float *param
     if (!params_flat || !packed) return fail(SNERF_E_BADARG, "mlp_pack: null pointer");
     if (!aligned(packed, 16)) return fail(SNERF_E_ALIGN, "mlp_pack: packed must be 16-byte aligned");
     return launch_pack(P, params_flat, packed, (hipStream_t)stream, "mlp_pack");
+}
+
+extern "C" int64_t snerf_mlp_packed_infer_floats(const snerf_mlp_desc *desc) {
+    using namespace snerf;
+    Plan R, P;
+    if (int rc = plan_for("mlp_packed_infer_floats", desc, R)) return rc;
+    const char *why;
+    if (!tuning().mlp_compose || make_plan_infer(*desc, P, why) != 0) return 0;   // no inference stream: the caller uses the regular one
+    return infer_scratch(R, P).total;
+}
+
+extern "C" int snerf_mlp_pack_infer_f32(const snerf_mlp_desc *desc, const float *params_flat, float *packed_infer,
+                                        snerf_stream_t stream) {
+    using namespace snerf;
+    Plan R, P;
+    if (int rc = plan_for("mlp_pack_infer", desc, R)) return rc;
+    if (int rc = plan_infer_for("mlp_pack_infer", desc, P)) return rc;
+    if (!tuning().mlp_compose)
+        return fail(SNERF_E_BADARG, "mlp_pack_infer: no inference stream with SNERF_MLP_COMPOSE=0 (snerf_mlp_packed_infer_floats returns 0)");
+    if (!params_flat || !packed_infer) return fail(SNERF_E_BADARG, "mlp_pack_infer: null pointer");
+    if (!aligned(packed_infer, 16)) return fail(SNERF_E_ALIGN, "mlp_pack_infer: packed_infer must be 16-byte aligned");
+    const InferScratch sc = infer_scratch(R, P);
+    const ComposeSrc c = compose_src(R, P);
+    double *mid = reinterpret_cast<double *>(packed_infer + sc.mid);
+    float *comp = packed_infer + sc.comp;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(mlp_compose_mid_kernel, dim3((c.WD * (c.W + 1) + 255) / 256), dim3(256), 0, s, c, params_flat, mid);
+    hipLaunchKernelGGL(mlp_compose_out_kernel, dim3((c.W + 1 + c.WD * (c.W + c.dir_dim + 1) + 255) / 256), dim3(256), 0, s, c, params_flat, mid,
+                       comp);
+    return launch_pack(P, params_flat, packed_infer, s, "mlp_pack_infer", comp);
+}
+
+extern "C" int snerf_mlp_fwd_infer_f32(const snerf_mlp_desc *desc, const float *packed_infer, const float *x, const float *dirs,
+                                       int dirs_per_sample, const float *add, int64_t n, int samples_per_ray, float *raw,
+                                       void *workspace, int64_t workspace_bytes, snerf_stream_t stream) {
+    snerf::MlpFwdCall c{desc, packed_infer, x, dirs, dirs_per_sample, add, n, samples_per_ray, raw, stream};
+    c.workspace = workspace;
+    c.workspace_bytes = workspace_bytes;
+    c.infer = true;
+    return snerf::launch_mlp_fwd(c);
 }
 
 extern "C" int64_t snerf_mlp_fold_workspace_bytes(const snerf_mlp_desc *desc, int64_t n, int samples_per_ray) {

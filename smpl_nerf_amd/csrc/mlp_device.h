@@ -30,6 +30,13 @@ int plan_for(const char *what, const Desc *desc, Plan &P, int kw = 16) {
     if (make_plan(*desc, P, why, kw) != 0) return fail(SNERF_E_BADARG, "%s: %s", what, why);
     return SNERF_OK;
 }
+// ... of the fp32 inference entries: the composed plan (mlp_plan.h: make_plan_infer)
+inline int plan_infer_for(const char *what, const snerf_mlp_desc *desc, Plan &P) {
+    const char *why;
+    if (!desc) return fail(SNERF_E_BADARG, "%s: desc is null", what);
+    if (make_plan_infer(*desc, P, why) != 0) return fail(SNERF_E_BADARG, "%s: %s", what, why);
+    return SNERF_OK;
+}
 // ... of the split-precision entries, whose kernels exist for width 256 alone
 template <class Desc>
 int plan_for_256(const char *what, const Desc *desc, Plan &P, int kw) {
@@ -54,6 +61,7 @@ struct MlpFwdCall {
     bool train = false;
     void *workspace = nullptr;     // fp32 inference: room for the per-ray fold table (snerf_mlp_fold_workspace_bytes)
     int64_t workspace_bytes = 0;
+    bool infer = false;            // fp32 inference on the composed stream: `packed` comes from snerf_mlp_pack_infer_f32
 };
 struct MlpBwdCall {
     const snerf_mlp_desc *desc;
@@ -76,8 +84,16 @@ int launch_mlp_fwd_bf16(int nsplit, const MlpFwdCall &c);
 // snerf_mlp_bwd_inputs_f32 and their split-precision twins)
 int launch_bwd(const MlpBwdCall &c);
 int launch_bwd_bf16(int nsplit, const MlpBwdCall &c);
-// `precision` of the one-call entries: 0 = the fp32 kernels, otherwise the nsplit of the split-precision ones
-inline int mlp_forward(int precision, const MlpFwdCall &c) { return precision == 0 ? launch_mlp_fwd(c) : launch_mlp_fwd_bf16(precision, c); }
+// `precision` of the one-call entries: 0 = the fp32 kernels, SNERF_FP32_INFER = the fp32 kernels on the composed inference stream
+// (render entries only), otherwise the nsplit of the split-precision ones
+inline int mlp_forward(int precision, const MlpFwdCall &c) {
+    if (precision == SNERF_FP32_INFER) {
+        MlpFwdCall ci = c;
+        ci.infer = true;
+        return launch_mlp_fwd(ci);
+    }
+    return precision == 0 ? launch_mlp_fwd(c) : launch_mlp_fwd_bf16(precision, c);
+}
 inline int mlp_backward(int precision, const MlpBwdCall &c) { return precision == 0 ? launch_bwd(c) : launch_bwd_bf16(precision, c); }
 // defined in warp.hip: the body of snerf_warp_bwd_f32
 int launch_warp_bwd(const snerf_warp_desc *desc, const float *packed_t, const float *act, const float *d_warp, int64_t n, float *dy,
@@ -97,8 +113,9 @@ template <bool TRAIN>
 int launch_fwd_lat(const Plan &P, const FwdArgs &A, hipStream_t s, int64_t first_sample);
 LatChoice lat_choose_bwd(const Plan &P, int64_t n, bool input_grad, bool beside_another_net = false);
 int launch_bwd_lat(const Plan &P, const BwdArgs &A, hipStream_t s, int64_t first_sample);
-// defined in mlp.hip: packs params_flat into the slab stream described by `P` (any plan)
-int launch_pack(const Plan &P, const float *params_flat, float *packed, hipStream_t s, const char *what);
+// defined in mlp.hip: packs params_flat into the slab stream described by `P` (any plan; a composed plan takes its composed layers
+// from `composed_params`)
+int launch_pack(const Plan &P, const float *params_flat, float *packed, hipStream_t s, const char *what, const float *composed_params = nullptr);
 
 // ------------------------------------------------------------------------------------------------
 // forward kernel
@@ -135,6 +152,7 @@ struct FwdArgs {
     int pos_nkb16, add_nkb16, dir_nkb16;
     int total_slabs;   // slabs of the weight stream (persistent workgroups wrap around)
     int64_t n_tiles;   // sample tiles (NWAVES x 16 samples)
+    int composed;      // inference on the stream of make_plan_infer: behind the trunk come sigma', dir-net' (ReLU) and the rgb head
 };
 
 // ---- host: what every forward entry (mlp.hip, mlp_bf16.hip) checks and fills alike; `what` prefixes every error text ----
@@ -177,6 +195,7 @@ inline FwdArgs fill_fwd_args(const Plan &P, const MlpFwdCall &c) {
     A.add_first = (P.add_dim && desc->add_first) ? 1 : 0;
     A.use_dir = desc->use_dir ? 1 : 0;
     A.enc_stride = P.pos_dim + P.add_dim + (desc->use_dir ? P.dir_dim : 0);
+    A.composed = P.composed;
     return A;
 }
 // the activation buffer of a training forward; P16: the 16-wide plan, whose TrainLayout (mlp_plan.h) the backward kernels read

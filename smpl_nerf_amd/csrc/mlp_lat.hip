@@ -220,6 +220,26 @@ static void lat_table_fwd(const Plan &P, const TrainLayout &L, const LatLds &Lo,
             o.b_base0 = Lo.act[(l + 1) & 1], o.b_stride0 = LAT_ACT_BYTES, o.b_n0 = 16;   // it; additional_linear_layer (:51): no activation
             o.b_base1 = Lo.pe, o.b_stride1 = Lo.pe_stride;
         }
+        if (P.composed && l > nh) {
+            // the composed inference stream (mlp_plan.h: make_plan_infer): sigma' and dir-net' read the trunk's output x, the
+            // rgb head reads dir-net''s; the other buffer takes dir-net''s output and, in its last KiB, sigma
+            const int x_buf = Lo.act[nh & 1], d_buf = Lo.act[(nh + 1) & 1];
+            o.out_base = d_buf;
+            if (l == nh + 1) {            // sigma' on wave 4, beside dir-net'
+                o.wave0 = 4;
+                o.b_base0 = x_buf, o.b_stride0 = LAT_ACT_BYTES, o.b_n0 = NONE;
+                o.op = LAT_HEAD_SIGMA;
+            } else if (l == nh + 2) {     // dir-net' + relu: x and the direction encoding
+                o.b_base0 = x_buf, o.b_stride0 = LAT_ACT_BYTES, o.b_n0 = 16;
+                o.b_base1 = Lo.pe + Lo.pe_dir, o.b_stride1 = Lo.pe_stride;
+                o.op = LAT_RELU | LAT_BARRIER;
+            } else {                      // rgb_out_layer (:60) on wave 5
+                o.wave0 = 5;
+                o.b_base0 = d_buf, o.b_stride0 = LAT_ACT_BYTES, o.b_n0 = NONE;
+                o.op = LAT_HEAD_RGB;
+            }
+            continue;
+        }
         if (l <= nh + 1) {
             o.out_base = Lo.act[l & 1];
             o.op = (l <= nh ? LAT_RELU : 0) | LAT_BARRIER;
@@ -578,7 +598,9 @@ static int lat_s_max_fwd(const Plan &P) {
     return lat_lds_fwd(s_max, P).total > 160 * 1024 ? 0 : s_max;
 }
 // plain RenderRayNet plans of width 256; per-ray additional inputs of up to 128 k-blocks (what fits the LDS beside one sample tile)
-static bool lat_covers(const Plan &P) { return lat_enabled() && P.width == 256 && P.add_nkb <= 100 && P.nlayers == P.n_hidden + 6; }
+static bool lat_covers(const Plan &P) {
+    return lat_enabled() && P.width == 256 && P.add_nkb <= 100 && P.nlayers == P.n_hidden + (P.composed ? 4 : 6);
+}
 
 template <bool TRAIN>
 LatChoice lat_choose_fwd(const Plan &P, int64_t n) {

@@ -68,6 +68,8 @@ struct Plan {
     int kw;  // features per k-block: 16 (fp32 MFMA 16x16x4 path) or 32 (split-bf16 MFMA 16x16x32 path)
     int pos_dim, dir_dim, add_dim;
     int64_t param_floats;
+    int composed;   // 1: the inference plan of make_plan_infer (the activation-free layers composed), 0: every other plan
+    int64_t comp_floats;   // composed plans: floats of the composed parameters (w_off / b_off of layers n_hidden + 1, + 2 index them)
     Layer layer[MAX_LAYERS];
 };
 
@@ -108,6 +110,8 @@ __host__ __device__ inline int pe_slot_col32(int L, int ident, int kb, int g, in
 inline int make_plan(const snerf_mlp_desc &d, Plan &P, const char *&why, int kw = 16) {
     why = "";
     P.kw = kw;
+    P.composed = 0;
+    P.comp_floats = 0;
     if (d.n_layers < 1 || d.n_layers > 16) { why = "n_layers must be in [1,16]"; return -1; }
     if (d.width < 2 || d.width > MAX_WIDTH) {
         why = "width must be in [2, 512] (the layer chain lives in registers: two accumulator sets of width x 16 samples per wave)";
@@ -198,6 +202,43 @@ inline int make_plan(const snerf_mlp_desc &d, Plan &P, const char *&why, int kw 
             why = "width above 256 needs at least 17 input columns (two k-blocks) in every layer";
             return -1;
         }
+    return 0;
+}
+
+// The inference plan: additional_linear_layer (:51), sigma_out_layer (:52), directional_input (:54-57) and directional_net[0]
+// (:58) follow each other without an activation, so for fixed weights they are two affine maps of the last trunk activation h:
+//     sigma    = (w_s W_a) h + (w_s b_a + b_s)                                               sigma'   [1, W]
+//     pre_relu = (W_n W_d1 W_a) h + (W_n W_d2) PE(d) + (W_n (W_d1 b_a + b_d) + b_n)          dir-net' [WD, W + dir_dim]
+// (W_d1 = W_d[:, :W], W_d2 = W_d[:, W:]).  Layers 0 .. n_hidden (the trunk) and the rgb head are those of make_plan, parameter
+// offsets included; layers n_hidden + 1 (sigma') and n_hidden + 2 (dir-net', ReLU) have the shapes of sigma_out_layer and
+// directional_input and take their values from the composed parameters (w_off / b_off index that vector: mlp.hip packs it).
+// Default net: 60 + 1 + 5 + 1 = 67 slabs instead of 77.  Inference only, fp32 only, widths up to 256.
+inline int make_plan_infer(const snerf_mlp_desc &d, Plan &P, const char *&why) {
+    Plan R;
+    if (int rc = make_plan(d, R, why, 16)) return rc;
+    if (R.width > 256) { why = "no inference stream above width 256"; return -1; }
+    P = R;
+    const int nh = R.n_hidden;
+    P.layer[nh + 1] = R.layer[nh + 2];
+    P.layer[nh + 2] = R.layer[nh + 3];
+    P.layer[nh + 3] = R.layer[nh + 5];
+    P.nlayers = nh + 4;
+    P.composed = 1;
+    int slab = R.layer[nh].first_slab + R.layer[nh].nslab;
+    int64_t off = 0;
+    for (int l = nh + 1; l < P.nlayers; ++l) {
+        Layer &Ly = P.layer[l];
+        Ly.first_slab = slab;
+        slab += Ly.nslab;
+        if (l < nh + 3) {
+            Ly.w_off = off;
+            off += (int64_t)Ly.n_out * Ly.n_in;
+            Ly.b_off = off;
+            off += Ly.n_out;
+        }
+    }
+    P.comp_floats = off;
+    P.total_slabs = slab;
     return 0;
 }
 
@@ -460,6 +501,8 @@ inline int make_warp_plan(const snerf_warp_desc &d, Plan &P, const char *&why, i
     const int WK = d.width <= 128 ? 128 : 256;   // other widths run zero-padded inside the next kernel width (make_plan)
     P.width = WK;
     P.kw = kw;
+    P.composed = 0;
+    P.comp_floats = 0;
     P.n_hidden = 0;
     P.pos_dim = 3 * (pid + 2 * d.pos_freqs);
     P.dir_dim = 0;

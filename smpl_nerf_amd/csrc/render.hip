@@ -118,8 +118,8 @@ static int snerf::render_rays_impl(const snerf_mlp_desc *desc_coarse, const void
     using namespace snerf;
     const bool refsum = (precision & SNERF_REFERENCE_SUM) != 0;
     precision &= ~SNERF_REFERENCE_SUM;
-    if (precision != 0 && precision != 2 && precision != 3 && precision != SNERF_SPLIT_F16X3)
-        return fail(SNERF_E_BADARG, "render_rays: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)");
+    if (precision != 0 && precision != 2 && precision != 3 && precision != SNERF_SPLIT_F16X3 && precision != SNERF_FP32_INFER)
+        return fail(SNERF_E_BADARG, "render_rays: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6), 16 (f16x3) or 32 (fp32, inference streams)");
     if (B < 0 || Nc < 1 || Nf < 0) return fail(SNERF_E_BADARG, "render_rays: bad B/Nc/Nf");
     if (B == 0) return SNERF_OK;
     if (!desc_coarse || !packed_coarse || !ray_samples || !rays_d || !z_vals || !workspace || !rgb || !rgb_fine ||
@@ -193,8 +193,8 @@ extern "C" int snerf_render_rays_smpl_f32(const snerf_mlp_desc *desc_coarse, con
     using namespace snerf;
     const bool refsum = (precision & SNERF_REFERENCE_SUM) != 0;
     precision &= ~SNERF_REFERENCE_SUM;
-    if (precision != 0 && precision != 2 && precision != 3 && precision != SNERF_SPLIT_F16X3)
-        return fail(SNERF_E_BADARG, "render_rays_smpl: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6) or 16 (f16x3)");
+    if (precision != 0 && precision != 2 && precision != 3 && precision != SNERF_SPLIT_F16X3 && precision != SNERF_FP32_INFER)
+        return fail(SNERF_E_BADARG, "render_rays_smpl: precision must be 0 (fp32), 2 (bf16x3), 3 (bf16x6), 16 (f16x3) or 32 (fp32, inference streams)");
     if (B < 0 || Nc < 1 || Nf < 1) return fail(SNERF_E_BADARG, "render_rays_smpl: bad B/Nc/Nf");
     if (B == 0) return SNERF_OK;
     if (!desc_coarse || !packed_coarse || !desc_fine || !packed_fine || !desc_warp || !packed_warp || !ray_samples ||

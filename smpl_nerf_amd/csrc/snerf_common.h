@@ -84,10 +84,11 @@ inline int tile_waves(int width, int64_t n, int n_cu) { return (width > 256 || n
 
 // Tuning knobs: environment variables read ONCE, at the first call that consults them (INTEGRATION.md lists every knob of the
 // library and of the Python host).  r06: the A/B switches of rounds 2-5 whose experiments are decided are gone (their patches
-// and scripts under tools/ab/ are the record); what is left switches the per-ray folds of inference off.
+// and scripts under tools/ab/ are the record); what is left switches the per-ray folds and the composed stream of inference off.
 struct Tuning {
     bool warp_fold;   // SNERF_WARP_FOLD=0   warp inference: pose k-blocks per sample instead of the per-ray fold
     bool mlp_fold;    // SNERF_MLP_FOLD=0    fp32 inference: per-ray additional inputs as k-blocks per sample
+    bool mlp_compose; // SNERF_MLP_COMPOSE=0 fp32 inference: no composed stream (snerf_mlp_packed_infer_floats returns 0: the regular one)
 };
 const Tuning &tuning();
 

@@ -72,6 +72,7 @@ inline WarpArgs fill_warp_args(const Plan &P, const WarpFwdCall &c) {
 int launch_warp_fwd(const WarpFwdCall &c);
 int launch_warp_fwd_bf16(const WarpFwdCall &c);
 // `precision` of the one-call entries: 0 = the fp32 kernels, otherwise the split-bf16 one (which has one format)
-inline int warp_forward(int precision, const WarpFwdCall &c) { return precision == 0 ? launch_warp_fwd(c) : launch_warp_fwd_bf16(c); }
+// (SNERF_FP32_INFER concerns the render nets' stream: the warp net runs its fp32 kernels)
+inline int warp_forward(int precision, const WarpFwdCall &c) { return (precision == 0 || precision == SNERF_FP32_INFER) ? launch_warp_fwd(c) : launch_warp_fwd_bf16(c); }
 
 }  // namespace snerf

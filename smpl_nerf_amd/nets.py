@@ -184,6 +184,13 @@ def _launch_forward(net, desc, ns, x, d, per_sample, spr, add, raw, act=None, li
                 check(lib.snerf_mlp_fwd_bf16_f32(desc, ptr(packed), ns, ptr(x), ptr(d), per_sample, ptr(add), n, int(spr),
                                                  ptr(raw), current_stream()), "snerf_mlp_fwd_bf16_f32")
         else:
+            # (no-grad inference of a net in eval mode: the composed inference stream; like_training keeps the training forward's bits)
+            packed_i = None if (train or like_training) else net.packed_weights_infer(desc)
+            if packed_i is not None:
+                ws, nb = _fold_workspace(lib.snerf_mlp_fold_workspace_bytes, desc, n, spr, raw.device) if add is not None else (None, 0)
+                check(lib.snerf_mlp_fwd_infer_f32(desc, ptr(packed_i), ptr(x), ptr(d), per_sample, ptr(add), n, int(spr), ptr(raw),
+                                                  ptr(ws), nb, current_stream()), "snerf_mlp_fwd_infer_f32")
+                return
             packed = net.packed_weights(desc, training=True)
             if train:
                 check(lib.snerf_mlp_fwd_train_f32(desc, ptr(packed), ptr(x), ptr(d), per_sample, ptr(add), n, int(spr),
@@ -415,13 +422,21 @@ class _PackedWeightsEpoch:
             return sink
         return torch.empty(numel, device=dev, dtype=torch.float32)
 
-    def _cached_pack(self, cache, key, params, build, keep_others=False):
+    # optimiser steps that refreshed the regular fp32 stream IN PLACE (the one-call training entries: its cache entry stays valid
+    # and current); a stream derived from the parameters that the step does not refresh - the composed inference stream - carries
+    # this count in its stamp and goes stale with every such step
+    _inplace_refreshes = 0
+
+    def _note_inplace_refresh(self):
+        self._inplace_refreshes += 1
+
+    def _cached_pack(self, cache, key, params, build, keep_others=False, extra=()):
         """Weight stream `key`, rebuilt by build(flat fp32 parameter vector) only when a parameter changed: the cache is
         keyed on (data_ptr, autograd version) of every parameter and the weights epoch (mark_weights_changed)."""
         dev = params[0].device
         if not params[0].is_cuda:
             raise RuntimeError(f"{type(self).__name__}: parameters must be on the GPU (smpl_nerf_amd has no CPU path)")
-        stamp = (str(dev), self._weights_epoch) + tuple((p.data_ptr(), p._version) for p in params)
+        stamp = (str(dev), self._weights_epoch) + tuple(extra) + tuple((p.data_ptr(), p._version) for p in params)
         hit = cache.get(key)
         if hit is not None and hit[0] == stamp:
             return hit[1]
@@ -570,6 +585,38 @@ class RenderRayNet(_PackedWeightsEpoch, nn.Module):
 
         return self._cached_pack(self._pack_cache, self._desc_key(desc), self._ordered_params(), build)
 
+    def packed_weights_infer(self, desc: MlpDesc):
+        """The composed fp32 inference stream for `desc` (snerf_mlp_pack_infer_f32: the activation-free layers behind the
+        trunk as two affine maps, 67 slabs instead of 77 for the default net), or None where the regular stream is to be used:
+        no such stream for the net (snerf_mlp_packed_infer_floats == 0: widths above 256, SNERF_MLP_COMPOSE=0), or a net in
+        train() mode - whose no-grad results stay those of the training forward, bit for bit (a validation pass, like
+        DataParallelTrainer's, switches to eval()).  Cached like packed_weights; stale whenever that stream is, and after
+        every optimiser step that refreshed that stream in place."""
+        if self.training or self._layered:
+            return None
+        lib = _lib.load()
+        key = self._desc_key(desc)
+        sizes = self.__dict__.setdefault("_infer_floats", {})
+        n_pack = sizes.get(key)
+        if n_pack is None:
+            n_pack = int(lib.snerf_mlp_packed_infer_floats(desc))
+            if n_pack < 0:
+                check(n_pack, "snerf_mlp_packed_infer_floats")
+            sizes[key] = n_pack
+        if n_pack == 0:
+            return None
+        self._begin_inference()
+
+        def build(flat, dev):
+            if flat.numel() != lib.snerf_mlp_param_floats(desc):
+                raise RuntimeError(f"RenderRayNet: {flat.numel()} parameters but the descriptor expects {lib.snerf_mlp_param_floats(desc)}")
+            packed = torch.empty(n_pack, device=dev, dtype=torch.float32)
+            check(lib.snerf_mlp_pack_infer_f32(desc, ptr(flat), ptr(packed), current_stream()), "snerf_mlp_pack_infer_f32")
+            return packed
+
+        return self._cached_pack(self._pack_cache, key + ("infer",), self._ordered_params(), build, keep_others=True,
+                                 extra=(self._inplace_refreshes,))
+
     def packed_weights_bf16(self, desc: MlpDesc, nsplit: int, training: bool = False) -> torch.Tensor:
         """Split-bf16 / two-part fp16 weight stream (snerf_mlp_pack_bf16), cached like packed_weights."""
         if not training:
@@ -685,8 +732,14 @@ class RenderRayNet(_PackedWeightsEpoch, nn.Module):
                 check(lib.snerf_mlp_fwd_bf16_f32(desc, ptr(packed), ns, ptr(x), ptr(d), per_sample, ptr(add), n,
                                                  int(samples_per_ray), ptr(raw), current_stream()), "snerf_mlp_fwd_bf16_f32")
             return raw
-        packed = self.packed_weights(desc)
         ws, nb = _fold_workspace(lib.snerf_mlp_fold_workspace_bytes, desc, n, samples_per_ray, x.device) if add is not None else (None, 0)
+        packed_i = self.packed_weights_infer(desc)
+        if packed_i is not None:     # a net in eval mode: the composed inference stream (same kernel, 67 slabs instead of 77)
+            with torch.cuda.device(x.device), _lib.timed(f"mlp_fwd[n={n}]"):
+                check(lib.snerf_mlp_fwd_infer_f32(desc, ptr(packed_i), ptr(x), ptr(d), per_sample, ptr(add), n,
+                                                  int(samples_per_ray), ptr(raw), ptr(ws), nb, current_stream()), "snerf_mlp_fwd_infer_f32")
+            return raw
+        packed = self.packed_weights(desc)
         with torch.cuda.device(x.device), _lib.timed(f"mlp_fwd[n={n}]"):
             check(lib.snerf_mlp_fwd_ws_f32(desc, ptr(packed), ptr(x), ptr(d), per_sample, ptr(add), n,
                                            int(samples_per_ray), ptr(raw), ptr(ws), nb, current_stream()), "snerf_mlp_fwd_ws_f32")

@@ -87,6 +87,18 @@ class PipelineArgs:
         return cls(**d)
 
 
+def _infer_streams(prec, nets, descs, packed):
+    """fp32 render calls of nets in eval mode run on the composed inference streams (nets.RenderRayNet.packed_weights_infer):
+    (SNERF_FP32_INFER, those streams) when every net has one, else the regular fp32 streams; split-precision streams pass."""
+    from . import _lib
+    if prec != 0:
+        return prec, packed
+    infer = [m.packed_weights_infer(d) for m, d in zip(nets, descs)]
+    if any(p is None for p in infer):
+        return prec, [m.packed_weights(d) for m, d in zip(nets, descs)]
+    return _lib.FP32_INFER, infer
+
+
 def _sampler_prec(prec: int, args) -> int:
     """The precision code of a render entry with SNERF_REFERENCE_SUM ORed in when strict mode's sum runs on the device."""
     from . import _lib
@@ -197,7 +209,8 @@ class NerfPipeline(nn.Module):
         for m in (mc, mf):
             d = m.desc_for_encoders(self.position_encoder, self.direction_encoder, False)
             descs.append(d)
-            packed.append(m.packed_weights(d) if prec == 0 else m.packed_weights_bf16(d, prec))
+            packed.append(None if prec == 0 else m.packed_weights_bf16(d, prec))
+        prec, packed = _infer_streams(prec, (mc, mf), descs, packed)
         lib = _lib.load()
         ws = torch.empty(int(lib.snerf_render_rays_workspace_bytes(B, Nc, Nf)), device=dev, dtype=torch.uint8)
         rgb, rgb_fine, samples_fine, dens = _render_outputs(B, N, 1, dev)
@@ -307,10 +320,11 @@ class SmplNerfPipeline(NerfPipeline):
         for m in (mc, mf):
             d = m.desc_for_encoders(self.position_encoder, self.direction_encoder, False)
             descs.append(d)
-            packed.append(m.packed_weights(d) if prec == 0 else m.packed_weights_bf16(d, prec))
+            packed.append(None if prec == 0 else m.packed_weights_bf16(d, prec))
+        prec, packed = _infer_streams(prec, (mc, mf), descs, packed)
         pe = self.position_encoder
         wdesc = _lib.WarpDesc(mw.width, pe.number_frequencies, 1 if pe.include_identity else 0, mw.direcions_dim)
-        wpacked = mw._packed(wdesc) if prec == 0 else mw._packed_bf16(wdesc)
+        wpacked = mw._packed(wdesc) if prec in (0, _lib.FP32_INFER) else mw._packed_bf16(wdesc)
         lib = _lib.load()
         ws = torch.empty(int(lib.snerf_render_rays_smpl_workspace_bytes(B, Nc, Nf)), device=dev, dtype=torch.uint8)
         rgb, rgb_fine, warp_f, samples_f, warped_f, dens = _render_outputs(B, N, 3, dev)
@@ -551,7 +565,8 @@ class AppendSmplParamsPipeline(NerfPipeline):
         for m in (mc, mf):
             d = m.desc_for_encoders(self.position_encoder, self.direction_encoder, True)
             descs.append(d)
-            packed.append(m.packed_weights(d) if prec == 0 else m.packed_weights_bf16(d, prec))
+            packed.append(None if prec == 0 else m.packed_weights_bf16(d, prec))
+        prec, packed = _infer_streams(prec, (mc, mf), descs, packed)
         lib = _lib.load()
         need = int(lib.snerf_render_rays_add_workspace_bytes(descs[0], descs[1], B, Nc, Nf))
         if need < 0:

@@ -554,6 +554,7 @@ class DataParallelTrainer:
                 packed.append(m.packed_weights(d, training=True))
                 packed_t.append(m.packed_weights_t(d, ig))
                 sf, st = self._slot_tables(oc, m, d, ig)
+                m._note_inplace_refresh()      # (the step refreshes these streams in place: the composed inference stream goes stale)
             adam[k] = _lib.AdamNet(ctypes.pointer(d), oc["seg"][k][0], ns, packed[k].data_ptr(), packed_t[k].data_ptr(),
                                    _lib.ptr(sf), _lib.ptr(st))
         return SimpleNamespace(ns=ns, descs=descs, packed=packed, packed_t=packed_t, adam=adam, n_adam=2 if Nf else 1)
