@@ -17,6 +17,21 @@ REFERENCE_SUM = 0x100  # include/smplnerf.h SNERF_REFERENCE_SUM: ORed into a pre
 
 SNERF_OK = 0
 
+# `precision` of a net -> nsplit / precision code of its matrix-core arithmetic (include/smplnerf.h); 0 = the exact fp32 kernels
+PRECISIONS = {"fp32": 0, "bf16x3": 2, "bf16x6": 3, "f16x3": SPLIT_F16X3}
+
+
+def precision_code(nets, what="render_rays") -> int:
+    """The one precision code of `nets`, which one call or one render runs together.  The split-precision kernels exist for width
+    256: with any other width among them the code is 0 (exact fp32), as is that of a name the table does not hold."""
+    name, code = nets[0].precision, None      # (plain loops: every launch of the launch-by-launch forward asks, for one net)
+    for m in nets:
+        if m.precision != name:
+            raise RuntimeError(f"{what}: all nets must use the same precision mode (set_precision)")
+        if m.width != 256:
+            code = 0
+    return PRECISIONS.get(name, 0) if code is None else code
+
 
 class MlpDesc(ctypes.Structure):
     """struct snerf_mlp_desc (include/smplnerf.h) - mirrors RenderRayNet.__init__ (models/render_ray_net.py:8)."""

@@ -6,6 +6,7 @@ The nn.Linear children only hold the parameters; they are never called.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -133,9 +134,7 @@ def _grads_from_flat(flat, shapes):
 
 def _split_code(net, per_sample):
     """nsplit / precision code of the net's matrix-core arithmetic for a fused call (0 = exact fp32 kernels)."""
-    if net.width != 256 or per_sample == _ENCODED_ROWS:
-        return 0
-    return {"bf16x6": 3, "bf16x3": 2, "f16x3": _lib.SPLIT_F16X3}.get(net.precision, 0)
+    return 0 if per_sample == _ENCODED_ROWS else _lib.precision_code((net,))
 
 
 def _fold_workspace(size_fn, desc, n, spr, dev):
@@ -156,18 +155,25 @@ def _train_sizes(desc, n):
     return sizes[0].value, sizes[1].value, sizes[3].value
 
 
-def _launch_forward(net, desc, ns, x, d, per_sample, spr, add, raw, act=None, like_training=False):
+def _launch_forward(net, desc, ns, x, d, per_sample, spr, add, raw, act=None, like_training=False, composed=True, inference=False,
+                    count=True):
     """One launch of the fused encode + MLP kernel on n = raw.shape[0] samples: inference (act None) or the training
-    forward that also saves the layer inputs into `act`.  like_training: an inference launch whose `raw` must equal the
-    training forward's bit for bit (the block-wise backward recomputes with the training kernel): no per-ray fold of the
-    additional inputs (include/smplnerf.h: SNERF_FWD_NO_RAY_FOLD)."""
+    forward that also saves the layer inputs into `act`.  Which entry and which weight stream a forward runs on is decided here alone.
+    like_training: an inference launch whose `raw` must equal the training forward's bit for bit (the block-wise backward
+    recomputes with the training kernel): the regular stream, and no workspace and so no per-ray fold of the additional inputs.
+    composed = False: the regular fp32 stream also for a net in eval mode.  AppendVerticesNet.forward_rays asks for it: it never ran
+    on the composed inference stream, and moving it there changes its bits and its speed - a change of its own, not a side effect.
+    inference: a no-grad forward outside a training step, so fetching the streams applies the weights epoch's inference rule
+    (_PackedWeightsEpoch._begin_inference); the launches of an autograd step do not.
+    count = False: not through _lib.timed() (RenderRayNet.forward(x) on encoded rows never counted in _lib.CALLS)."""
     lib = _lib.load()
     n = raw.shape[0]
     train = act is not None
+    training = not inference
     tag = "mlp_fwd_train" if train else "mlp_fwd"
-    with torch.cuda.device(raw.device), _lib.timed(f"{tag}[n={n}]"):
+    with torch.cuda.device(raw.device), (_lib.timed(f"{tag}[n={n}]") if count else contextlib.nullcontext()):
         if per_sample == _ENCODED_ROWS:      # x holds already-encoded rows (RenderRayNet.forward(x))
-            packed = net.packed_weights(desc, training=True)
+            packed = net.packed_weights(desc, training)
             if train:
                 check(lib.snerf_mlp_fwd_encoded_train_f32(desc, ptr(packed), ptr(x), n, x.shape[1], ptr(raw), ptr(act),
                                                           current_stream()), "snerf_mlp_fwd_encoded_train_f32")
@@ -175,33 +181,30 @@ def _launch_forward(net, desc, ns, x, d, per_sample, spr, add, raw, act=None, li
                 check(lib.snerf_mlp_fwd_encoded_f32(desc, ptr(packed), ptr(x), n, x.shape[1], ptr(raw), current_stream()),
                       "snerf_mlp_fwd_encoded_f32")
         elif ns:                             # on the 16-bit matrix cores; saved activations are fp32 all the same
-            packed = net.packed_weights_bf16(desc, ns, training=True)
+            packed = net.packed_weights_bf16(desc, ns, training)
             if train:
                 check(lib.snerf_mlp_fwd_train_bf16_f32(desc, ptr(packed), ns, ptr(x), ptr(d), per_sample, ptr(add), n,
                                                        int(spr), ptr(raw), ptr(act), current_stream()),
                       "snerf_mlp_fwd_train_bf16_f32")
-            else:
+            else:      # ("f16x3": two fp16 parts, inference kernel only)
                 check(lib.snerf_mlp_fwd_bf16_f32(desc, ptr(packed), ns, ptr(x), ptr(d), per_sample, ptr(add), n, int(spr),
                                                  ptr(raw), current_stream()), "snerf_mlp_fwd_bf16_f32")
+        elif train:
+            packed = net.packed_weights(desc, True)
+            check(lib.snerf_mlp_fwd_train_f32(desc, ptr(packed), ptr(x), ptr(d), per_sample, ptr(add), n, int(spr),
+                                              ptr(raw), ptr(act), current_stream()), "snerf_mlp_fwd_train_f32")
         else:
-            # (no-grad inference of a net in eval mode: the composed inference stream; like_training keeps the training forward's bits)
-            packed_i = None if (train or like_training) else net.packed_weights_infer(desc)
-            if packed_i is not None:
-                ws, nb = _fold_workspace(lib.snerf_mlp_fold_workspace_bytes, desc, n, spr, raw.device) if add is not None else (None, 0)
-                check(lib.snerf_mlp_fwd_infer_f32(desc, ptr(packed_i), ptr(x), ptr(d), per_sample, ptr(add), n, int(spr), ptr(raw),
-                                                  ptr(ws), nb, current_stream()), "snerf_mlp_fwd_infer_f32")
-                return
-            packed = net.packed_weights(desc, training=True)
-            if train:
-                check(lib.snerf_mlp_fwd_train_f32(desc, ptr(packed), ptr(x), ptr(d), per_sample, ptr(add), n, int(spr),
-                                                  ptr(raw), ptr(act), current_stream()), "snerf_mlp_fwd_train_f32")
-            elif like_training or add is None:
-                check(lib.snerf_mlp_fwd_f32(desc, ptr(packed), ptr(x), ptr(d), per_sample, ptr(add), n, int(spr), ptr(raw),
-                                            current_stream()), "snerf_mlp_fwd_f32")
-            else:
-                ws, nb = _fold_workspace(lib.snerf_mlp_fold_workspace_bytes, desc, n, spr, raw.device)
-                check(lib.snerf_mlp_fwd_ws_f32(desc, ptr(packed), ptr(x), ptr(d), per_sample, ptr(add), n, int(spr), ptr(raw),
-                                               ptr(ws), nb, current_stream()), "snerf_mlp_fwd_ws_f32")
+            # the per-ray fold of the additional inputs wants a caller workspace; without one snerf_mlp_fwd_ws_f32 is snerf_mlp_fwd_f32
+            # (csrc/mlp.hip: both build the same MlpFwdCall) - the per-sample form that like_training asks for
+            ws, nb = (None, 0) if add is None or like_training else \
+                _fold_workspace(lib.snerf_mlp_fold_workspace_bytes, desc, n, spr, raw.device)
+            # a net in eval mode: the composed inference stream (same kernel, 67 slabs instead of 77 for the default net)
+            packed = net.packed_weights_infer(desc) if composed and not like_training else None
+            entry = "snerf_mlp_fwd_ws_f32" if packed is None else "snerf_mlp_fwd_infer_f32"
+            if packed is None:
+                packed = net.packed_weights(desc, training)
+            check(getattr(lib, entry)(desc, ptr(packed), ptr(x), ptr(d), per_sample, ptr(add), n, int(spr), ptr(raw), ptr(ws), nb,
+                                      current_stream()), entry)
 
 
 def _launch_backward(net, desc, ns, act, d_raw, n, sizes, flat, input_grad, x=None, d=None, per_sample=0, spr=1,
@@ -388,6 +391,12 @@ class _PackedWeightsEpoch:
     after a training forward starts another, and whoever updates weights behind autograd's back calls
     mark_weights_changed() (DataParallelTrainer.step does after every optimiser step)."""
 
+    def __init__(self):
+        super().__init__()
+        self._pack_cache, self._pack_t_cache = {}, {}      # forward streams / transposed streams (_STREAMS)
+        self._weights_epoch = 0            # see mark_weights_changed()
+        self._trained_since_pack = False
+
     def mark_weights_changed(self):
         """Call after changing parameter values in a way autograd's version counters do not see: fused optimisers,
         `p.data.copy_(...)` / `p.data[...] = ...` (`.data` has its own version counter), raw-pointer writes.  In-place ops
@@ -430,22 +439,72 @@ class _PackedWeightsEpoch:
     def _note_inplace_refresh(self):
         self._inplace_refreshes += 1
 
-    def _cached_pack(self, cache, key, params, build, keep_others=False, extra=()):
-        """Weight stream `key`, rebuilt by build(flat fp32 parameter vector) only when a parameter changed: the cache is
-        keyed on (data_ptr, autograd version) of every parameter and the weights epoch (mark_weights_changed)."""
+    def _stream(self, kind, desc, options=(), training=True):
+        """Weight stream `kind` (a row of _STREAMS) of the net for `desc` and the pack entry's `options`, re-packed only when a
+        parameter changed: the cache is keyed on (data_ptr, autograd version) of every parameter and the weights epoch
+        (mark_weights_changed).  training = False: fetched for inference, which may start a new epoch (_begin_inference)."""
+        size, pack, dtype, cache_name, keep_others, stamp_extra = _STREAMS[kind]
+        if not training:
+            self._begin_inference()
+        params = self._ordered_params()
         dev = params[0].device
         if not params[0].is_cuda:
             raise RuntimeError(f"{type(self).__name__}: parameters must be on the GPU (smpl_nerf_amd has no CPU path)")
-        stamp = (str(dev), self._weights_epoch) + tuple(extra) + tuple((p.data_ptr(), p._version) for p in params)
+        stamp = (str(dev), self._weights_epoch) + (tuple([getattr(self, a) for a in stamp_extra]) if stamp_extra else ()) + \
+            tuple((p.data_ptr(), p._version) for p in params)
+        cache, key = getattr(self, cache_name), _desc_key(desc) + (kind,) + options
         hit = cache.get(key)
         if hit is not None and hit[0] == stamp:
             return hit[1]
+        lib = _lib.load()
+        n_param = getattr(lib, self._param_floats_entry)(desc)
+        n_pack = size(desc, *options) if callable(size) else getattr(lib, size)(desc, *options)
+        if n_param < 0 or n_pack < 0:
+            check(int(min(n_param, n_pack)), getattr(size, "__name__", size))
         with torch.cuda.device(dev):
-            packed = build(flat_parameter_vector(params), dev)
+            flat = flat_parameter_vector(params)
+            if flat.numel() != n_param:
+                raise RuntimeError(f"{type(self).__name__}: {flat.numel()} parameters but the descriptor expects {n_param}")
+            packed = torch.empty(n_pack, device=dev, dtype=dtype)
+            check(getattr(lib, pack)(desc, ptr(flat), ptr(packed), *options, current_stream()), pack)
         if not keep_others:
             cache.clear()
         cache[key] = (stamp, packed)
         return packed
+
+    @property
+    def is_cuda(self):
+        return next(self.parameters()).is_cuda
+
+
+def _desc_key(desc):
+    """The fields of a descriptor as a tuple (cache keys); MlpDescs of RenderRayNet.make_desc carry theirs."""
+    key = getattr(desc, "_key", None)
+    return key if key is not None else tuple(getattr(desc, f[0]) for f in desc._fields_)
+
+
+def _packed_t_floats(desc, input_grad):
+    n_pack = ctypes.c_int64()
+    check(_lib.load().snerf_mlp_train_sizes(desc, 0, None, None, ctypes.byref(n_pack), None, None), "snerf_mlp_train_sizes")
+    return n_pack.value
+
+
+# The weight streams of the two nets, one row each:
+#   kind -> (size entry: elements of the stream for (desc, *options); pack entry: (desc, flat parameters, stream out, *options, hip stream);
+#            element type; the cache it lives in; whether a rebuild keeps the cache's other entries; what else its stamp carries)
+# options are (nsplit,), (input_grad,) or (nsplit, input_grad), as the pack entry takes them.  A re-packed forward stream means the
+# weights changed, and evicts the other forward streams of the net; the transposed streams (two per step: with and without input
+# gradients) and the composed inference stream (built beside the regular one it goes stale with) leave the others alone.  The composed
+# stream is derived from the parameters but not refreshed by the one-call training step: its stamp carries _inplace_refreshes.
+_STREAMS = {
+    "fwd": ("snerf_mlp_packed_floats", "snerf_mlp_pack_f32", torch.float32, "_pack_cache", False, ()),
+    "infer": ("snerf_mlp_packed_infer_floats", "snerf_mlp_pack_infer_f32", torch.float32, "_pack_cache", True, ("_inplace_refreshes",)),
+    "bf16": ("snerf_mlp_packed_bf16_bytes", "snerf_mlp_pack_bf16", torch.uint8, "_pack_cache", False, ()),
+    "t": (_packed_t_floats, "snerf_mlp_pack_t_f32", torch.float32, "_pack_t_cache", True, ()),
+    "t_bf16": ("snerf_mlp_packed_t_bf16_bytes", "snerf_mlp_pack_t_bf16", torch.uint8, "_pack_t_cache", True, ()),
+    "warp": ("snerf_warp_packed_floats", "snerf_warp_pack_f32", torch.float32, "_pack_cache", False, ()),
+    "warp_bf16": ("snerf_warp_packed_bf16_bytes", "snerf_warp_pack_bf16", torch.uint8, "_pack_cache", False, ()),
+}
 
 
 class RenderRayNet(_PackedWeightsEpoch, nn.Module):
@@ -485,10 +544,6 @@ class RenderRayNet(_PackedWeightsEpoch, nn.Module):
         for i in range(1):
             self.directional_net.append(torch.nn.Linear(directional_width, directional_width))
         self.rgb_out_layer = torch.nn.Linear(directional_width, 3)
-        self._pack_cache = {}
-        self._pack_t_cache = {}
-        self._weights_epoch = 0            # see mark_weights_changed()
-        self._trained_since_pack = False
         # matrix-core arithmetic of inference and of a training step's forward, dgrad and wide wgrad jobs: "fp32"
         # (v_mfma_f32_16x16x4_f32) or split-bf16 "bf16x6" (3 parts, fp32-class accuracy) / "bf16x3" (2 parts, ~1e-5
         # relative); activations, gradients, the narrow wgrad jobs and the reductions are fp32 in every mode
@@ -562,28 +617,13 @@ class RenderRayNet(_PackedWeightsEpoch, nn.Module):
             return self.make_desc(0, 0, d[0], d[1], self.positions_dim + self.additional_input_dim)
         return self.make_desc(p[0], p[1], d[0], d[1], self.additional_input_dim)
 
-    @staticmethod
-    def _desc_key(desc):
-        key = getattr(desc, "_key", None)
-        return key if key is not None else tuple(getattr(desc, f[0]) for f in desc._fields_)
+    _desc_key = staticmethod(_desc_key)
+    _param_floats_entry = "snerf_mlp_param_floats"
 
+    # -- the weight streams: thin calls of _PackedWeightsEpoch._stream (the rows of _STREAMS)
     def packed_weights(self, desc: MlpDesc, training: bool = False) -> torch.Tensor:
         """MFMA-ordered fp32 weight stream for `desc` (snerf_mlp_pack_f32), re-packed only when a parameter changed."""
-        if not training:
-            self._begin_inference()
-        lib = _lib.load()
-
-        def build(flat, dev):
-            n_param, n_pack = lib.snerf_mlp_param_floats(desc), lib.snerf_mlp_packed_floats(desc)
-            if n_param < 0 or n_pack < 0:
-                check(int(min(n_param, n_pack)), "snerf_mlp_packed_floats")
-            if flat.numel() != n_param:
-                raise RuntimeError(f"RenderRayNet: {flat.numel()} parameters but the descriptor expects {n_param}")
-            packed = torch.empty(n_pack, device=dev, dtype=torch.float32)
-            check(lib.snerf_mlp_pack_f32(desc, ptr(flat), ptr(packed), current_stream()), "snerf_mlp_pack_f32")
-            return packed
-
-        return self._cached_pack(self._pack_cache, self._desc_key(desc), self._ordered_params(), build)
+        return self._stream("fwd", desc, (), training)
 
     def packed_weights_infer(self, desc: MlpDesc):
         """The composed fp32 inference stream for `desc` (snerf_mlp_pack_infer_f32: the activation-free layers behind the
@@ -594,75 +634,27 @@ class RenderRayNet(_PackedWeightsEpoch, nn.Module):
         every optimiser step that refreshed that stream in place."""
         if self.training or self._layered:
             return None
-        lib = _lib.load()
-        key = self._desc_key(desc)
-        sizes = self.__dict__.setdefault("_infer_floats", {})
+        key = _desc_key(desc)
+        sizes = self.__dict__.setdefault("_infer_floats", {})      # (asked on every call, in front of the cache: kept per descriptor)
         n_pack = sizes.get(key)
         if n_pack is None:
-            n_pack = int(lib.snerf_mlp_packed_infer_floats(desc))
+            n_pack = int(_lib.load().snerf_mlp_packed_infer_floats(desc))
             if n_pack < 0:
                 check(n_pack, "snerf_mlp_packed_infer_floats")
             sizes[key] = n_pack
-        if n_pack == 0:
-            return None
-        self._begin_inference()
-
-        def build(flat, dev):
-            if flat.numel() != lib.snerf_mlp_param_floats(desc):
-                raise RuntimeError(f"RenderRayNet: {flat.numel()} parameters but the descriptor expects {lib.snerf_mlp_param_floats(desc)}")
-            packed = torch.empty(n_pack, device=dev, dtype=torch.float32)
-            check(lib.snerf_mlp_pack_infer_f32(desc, ptr(flat), ptr(packed), current_stream()), "snerf_mlp_pack_infer_f32")
-            return packed
-
-        return self._cached_pack(self._pack_cache, key + ("infer",), self._ordered_params(), build, keep_others=True,
-                                 extra=(self._inplace_refreshes,))
+        return self._stream("infer", desc, (), False) if n_pack else None
 
     def packed_weights_bf16(self, desc: MlpDesc, nsplit: int, training: bool = False) -> torch.Tensor:
         """Split-bf16 / two-part fp16 weight stream (snerf_mlp_pack_bf16), cached like packed_weights."""
-        if not training:
-            self._begin_inference()
-        lib = _lib.load()
-
-        def build(flat, dev):
-            nbytes = lib.snerf_mlp_packed_bf16_bytes(desc, nsplit)
-            if nbytes < 0:
-                check(int(nbytes), "snerf_mlp_packed_bf16_bytes")
-            packed = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            check(lib.snerf_mlp_pack_bf16(desc, ptr(flat), ptr(packed), nsplit, current_stream()), "snerf_mlp_pack_bf16")
-            return packed
-
-        return self._cached_pack(self._pack_cache, self._desc_key(desc) + ("bf16", nsplit), self._ordered_params(), build)
+        return self._stream("bf16", desc, (nsplit,), training)
 
     def packed_weights_t(self, desc: MlpDesc, input_grad: bool = False) -> torch.Tensor:
         """Transposed fp32 weight stream for the dgrad kernel (same caching rule as packed_weights)."""
-        lib = _lib.load()
-
-        def build(flat, dev):
-            n_pack = ctypes.c_int64()
-            check(lib.snerf_mlp_train_sizes(desc, 0, None, None, ctypes.byref(n_pack), None, None), "snerf_mlp_train_sizes")
-            packed = torch.empty(n_pack.value, device=dev, dtype=torch.float32)
-            check(lib.snerf_mlp_pack_t_f32(desc, ptr(flat), ptr(packed), 1 if input_grad else 0, current_stream()),
-                  "snerf_mlp_pack_t_f32")
-            return packed
-
-        return self._cached_pack(self._pack_t_cache, self._desc_key(desc) + (bool(input_grad),), self._ordered_params(),
-                                 build, keep_others=True)
+        return self._stream("t", desc, (1 if input_grad else 0,))
 
     def packed_weights_t_bf16(self, desc: MlpDesc, nsplit: int, input_grad: bool = False) -> torch.Tensor:
         """Split-bf16 transposed weight stream for the bf16 dgrad kernel (snerf_mlp_pack_t_bf16)."""
-        lib = _lib.load()
-
-        def build(flat, dev):
-            nbytes = lib.snerf_mlp_packed_t_bf16_bytes(desc, nsplit, 1 if input_grad else 0)
-            if nbytes < 0:
-                check(int(nbytes), "snerf_mlp_packed_t_bf16_bytes")
-            packed = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            check(lib.snerf_mlp_pack_t_bf16(desc, ptr(flat), ptr(packed), nsplit, 1 if input_grad else 0, current_stream()),
-                  "snerf_mlp_pack_t_bf16")
-            return packed
-
-        return self._cached_pack(self._pack_t_cache, self._desc_key(desc) + (bool(input_grad), "bf16", nsplit),
-                                 self._ordered_params(), build, keep_others=True)
+        return self._stream("t_bf16", desc, (nsplit, 1 if input_grad else 0))
 
     # ------------------------------------------------------------------ forward paths
     def forward(self, x):
@@ -684,12 +676,8 @@ class RenderRayNet(_PackedWeightsEpoch, nn.Module):
             # reference's smpl_nerf / dynamic / image-wise pipelines train upstream modules through model(inputs))
             raw = _FusedMlpFn.apply(self, desc, xf, None, _ENCODED_ROWS, 1, None, *self._ordered_params())
             return raw.reshape(x.shape[:-1] + (4,))
-        packed = self.packed_weights(desc)
         raw = torch.empty((n, 4), device=x.device, dtype=torch.float32)
-        lib = _lib.load()
-        with torch.cuda.device(x.device):
-            check(lib.snerf_mlp_fwd_encoded_f32(desc, ptr(packed), ptr(xf), n, xf.shape[1], ptr(raw),
-                                                current_stream()), "snerf_mlp_fwd_encoded_f32")
+        _launch_forward(self, desc, 0, xf, None, _ENCODED_ROWS, 1, None, raw, inference=True, count=False)
         return raw.reshape(x.shape[:-1] + (4,))
 
     def forward_fused(self, positions, directions, samples_per_ray, position_encoder, direction_encoder,
@@ -723,31 +711,8 @@ class RenderRayNet(_PackedWeightsEpoch, nn.Module):
                                         any(p.requires_grad for p in self.parameters())):
             return _FusedMlpFn.apply(self, desc, x, d, per_sample, int(samples_per_ray), add, *self._ordered_params())
         raw = torch.empty((n, 4), device=x.device, dtype=torch.float32)
-        lib = _lib.load()
-        if self.precision in ("bf16x6", "bf16x3", "f16x3") and self.width == 256:
-            # "f16x3": two fp16 parts (inference kernel only)
-            ns = {"bf16x6": 3, "bf16x3": 2, "f16x3": _lib.SPLIT_F16X3}[self.precision]
-            packed = self.packed_weights_bf16(desc, ns)
-            with torch.cuda.device(x.device), _lib.timed(f"mlp_fwd[n={n}]"):
-                check(lib.snerf_mlp_fwd_bf16_f32(desc, ptr(packed), ns, ptr(x), ptr(d), per_sample, ptr(add), n,
-                                                 int(samples_per_ray), ptr(raw), current_stream()), "snerf_mlp_fwd_bf16_f32")
-            return raw
-        ws, nb = _fold_workspace(lib.snerf_mlp_fold_workspace_bytes, desc, n, samples_per_ray, x.device) if add is not None else (None, 0)
-        packed_i = self.packed_weights_infer(desc)
-        if packed_i is not None:     # a net in eval mode: the composed inference stream (same kernel, 67 slabs instead of 77)
-            with torch.cuda.device(x.device), _lib.timed(f"mlp_fwd[n={n}]"):
-                check(lib.snerf_mlp_fwd_infer_f32(desc, ptr(packed_i), ptr(x), ptr(d), per_sample, ptr(add), n,
-                                                  int(samples_per_ray), ptr(raw), ptr(ws), nb, current_stream()), "snerf_mlp_fwd_infer_f32")
-            return raw
-        packed = self.packed_weights(desc)
-        with torch.cuda.device(x.device), _lib.timed(f"mlp_fwd[n={n}]"):
-            check(lib.snerf_mlp_fwd_ws_f32(desc, ptr(packed), ptr(x), ptr(d), per_sample, ptr(add), n,
-                                           int(samples_per_ray), ptr(raw), ptr(ws), nb, current_stream()), "snerf_mlp_fwd_ws_f32")
+        _launch_forward(self, desc, _split_code(self, per_sample), x, d, per_sample, samples_per_ray, add, raw, inference=True)
         return raw
-
-    @property
-    def is_cuda(self):
-        return next(self.parameters()).is_cuda
 
 
 class _WarpFn(torch.autograd.Function):
@@ -831,9 +796,6 @@ class WarpFieldNet(_PackedWeightsEpoch, nn.Module):
         self.width = width
         self.linear1 = torch.nn.Linear(positions_dim + pose_dim, width)
         self.linear2 = torch.nn.Linear(width, 3)
-        self._pack_cache = {}
-        self._weights_epoch = 0
-        self._trained_since_pack = False
         # "fp32" (v_mfma_f32_16x16x4_f32) or split-bf16: any of "bf16x6" / "bf16x3" runs the warp net with three parts
         # (fp32-class accuracy: the warp moves the sample in front of the position encoding's 2^9 band)
         self.precision = os.environ.get("SNERF_PRECISION", "fp32")
@@ -841,38 +803,21 @@ class WarpFieldNet(_PackedWeightsEpoch, nn.Module):
     def _params(self):
         return [self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias]
 
+    _ordered_params = _params      # (the C-ABI's params_flat order, under the name _PackedWeightsEpoch._stream asks for)
+    _param_floats_entry = "snerf_warp_param_floats"
+
     def _packed(self, desc, training: bool = False):
-        if not training:
-            self._begin_inference()
-        lib = _lib.load()
-
-        def build(flat, dev):
-            n_param, n_pack = lib.snerf_warp_param_floats(desc), lib.snerf_warp_packed_floats(desc)
-            if n_param < 0 or n_pack < 0:
-                check(int(min(n_param, n_pack)), "snerf_warp_packed_floats")
-            if flat.numel() != n_param:
-                raise RuntimeError(f"WarpFieldNet: {flat.numel()} parameters but the descriptor expects {n_param}")
-            packed = torch.empty(n_pack, device=dev, dtype=torch.float32)
-            check(lib.snerf_warp_pack_f32(desc, ptr(flat), ptr(packed), current_stream()), "snerf_warp_pack_f32")
-            return packed
-
-        return self._cached_pack(self._pack_cache, tuple(getattr(desc, f[0]) for f in desc._fields_), self._params(), build)
+        """fp32 weight stream of the fused forward (snerf_warp_pack_f32), re-packed only when a parameter changed."""
+        return self._stream("warp", desc, (), training)
 
     def _packed_bf16(self, desc):
         """Split-bf16 weight stream of the fused forward (snerf_warp_pack_bf16), cached like _packed."""
-        self._begin_inference()
-        lib = _lib.load()
+        return self._stream("warp_bf16", desc, (), False)
 
-        def build(flat, dev):
-            nbytes = lib.snerf_warp_packed_bf16_bytes(desc)
-            if nbytes < 0:
-                check(int(nbytes), "snerf_warp_packed_bf16_bytes")
-            packed = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            check(lib.snerf_warp_pack_bf16(desc, ptr(flat), ptr(packed), current_stream()), "snerf_warp_pack_bf16")
-            return packed
-
-        return self._cached_pack(self._pack_cache, tuple(getattr(desc, f[0]) for f in desc._fields_) + ("bf16",),
-                                 self._params(), build)
+    def desc_for_encoder(self, position_encoder) -> "_lib.WarpDesc":
+        """Descriptor of the fused (encode + warp) path for the pipeline's position encoder."""
+        return _lib.WarpDesc(self.width, position_encoder.number_frequencies, 1 if position_encoder.include_identity else 0,
+                             self.direcions_dim)
 
     def forward(self, x):
         """x [..., positions_dim + pose_dim] (already encoded) -> warp [..., 3] (models/warp_field_net.py:17-21);
@@ -902,10 +847,9 @@ class WarpFieldNet(_PackedWeightsEpoch, nn.Module):
     def forward_fused(self, positions, pose_encoding, ray_translation, samples_per_ray, position_encoder):
         """positions [n,3] (samples of a ray contiguous), pose_encoding [n/spr, pose_dim], ray_translation
         [n/spr, 3] -> (warp, warped = positions + warp, sdirs = warped - ray_translation), each [n,3]."""
-        pos_L, pos_id = position_encoder.number_frequencies, 1 if position_encoder.include_identity else 0
-        if 3 * (pos_id + 2 * pos_L) != self.positions_dim or pose_encoding.shape[-1] != self.direcions_dim:
+        desc = self.desc_for_encoder(position_encoder)
+        if 3 * (desc.pos_identity + 2 * desc.pos_freqs) != self.positions_dim or pose_encoding.shape[-1] != self.direcions_dim:
             raise RuntimeError("WarpFieldNet: encoder output sizes do not match positions_dim/pose_dim")
-        desc = _lib.WarpDesc(self.width, pos_L, pos_id, self.direcions_dim)
         _need_f32_cuda("WarpFieldNet.forward_fused", positions, pose_encoding, ray_translation)
         x = positions.reshape(-1, 3).contiguous()
         n = x.shape[0]
@@ -924,7 +868,7 @@ class WarpFieldNet(_PackedWeightsEpoch, nn.Module):
             return _WarpFn.apply(self, desc, x.detach(), pe, o.detach(), int(samples_per_ray), *self._params())
         warp, warped, sdirs = (torch.empty((n, 3), device=x.device, dtype=torch.float32) for _ in range(3))
         lib = _lib.load()
-        if self.precision in ("bf16x6", "bf16x3", "f16x3") and self.width == 256:
+        if _lib.precision_code((self,)):      # (any split mode runs the warp net with three bf16 parts)
             packed = self._packed_bf16(desc)
             with torch.cuda.device(x.device), _lib.timed(f"warp_fwd[n={n}]"):
                 check(lib.snerf_warp_fwd_bf16_f32(desc, ptr(packed), ptr(x), ptr(pe), ptr(o), n, int(samples_per_ray),
@@ -937,10 +881,6 @@ class WarpFieldNet(_PackedWeightsEpoch, nn.Module):
             check(lib.snerf_warp_fwd_ws_f32(desc, ptr(packed), ptr(x), ptr(pe), ptr(o), n, int(samples_per_ray), ptr(warp),
                                             ptr(warped), ptr(sdirs), ptr(ws), nb, current_stream()), "snerf_warp_fwd_ws_f32")
         return warp, warped, sdirs
-
-    @property
-    def is_cuda(self):
-        return next(self.parameters()).is_cuda
 
 
 class AppendVerticesNet(RenderRayNet):
@@ -967,14 +907,21 @@ class AppendVerticesNet(RenderRayNet):
             raise RuntimeError(f"AppendVerticesNet: directions_dim={self.direcions_dim} is not a 3-channel encoding")
         return MlpDesc(self.n_layers, self.width, 0, 0, d[0], d[1], self.positions_dim, self._skip_mask(), 1, 0)
 
-    def forward(self, x):
-        """x [..., positions_dim + additional_input_dim + directions_dim] -> [..., 4] (:43-66)."""
+    @contextlib.contextmanager
+    def _without_vertex_columns(self):
+        """additional_input_dim = 0 while RenderRayNet's code runs: the live columns are x[..., :positions_dim] and
+        x[..., -directions_dim:], the vertex columns between them feed only the dead branch."""
         keep = self.additional_input_dim
         try:
-            self.additional_input_dim = 0        # live columns: x[..., :positions_dim] and x[..., -directions_dim:]
-            return RenderRayNet.forward(self, x)
+            self.additional_input_dim = 0
+            yield
         finally:
             self.additional_input_dim = keep
+
+    def forward(self, x):
+        """x [..., positions_dim + additional_input_dim + directions_dim] -> [..., 4] (:43-66)."""
+        with self._without_vertex_columns():
+            return RenderRayNet.forward(self, x)
 
     def forward_rays(self, ray_inputs, directions, samples_per_ray, n):
         """ray_inputs [B, positions_dim] (the first positions_dim columns of the reference's input rows, a
@@ -989,29 +936,14 @@ class AppendVerticesNet(RenderRayNet):
             L, ident = _encoder_shape(self.direcions_dim)
             dn = d.detach() / torch.norm(d.detach(), dim=-1, keepdim=True)
             dd = PositionalEncoder(L, bool(ident)).encode(dn).repeat_interleave(int(samples_per_ray), dim=0)
-            keep = self.additional_input_dim
-            try:
-                self.additional_input_dim = 0
+            with self._without_vertex_columns():
                 return layered.render_ray_net(self, add.repeat_interleave(int(samples_per_ray), dim=0), dd)
-            finally:
-                self.additional_input_dim = keep
         dummy_x = torch.zeros((n, 3), device=add.device, dtype=torch.float32)   # no position encoder: never read for slots
         if torch.is_grad_enabled() and (add.requires_grad or any(p.requires_grad for p in self.parameters())):
             # `add` keeps its graph: the vertex floats come from smpl_model(smpl_estimator(images)), whose parameters
             # AppendVerticesSolver optimises in their own group (solver/append_vertices_solver.py)
             return _FusedMlpFn.apply(self, desc, dummy_x, d.detach(), 0, int(samples_per_ray), add, *self._ordered_params())
         raw = torch.empty((n, 4), device=add.device, dtype=torch.float32)
-        lib = _lib.load()
-        if self.precision in ("bf16x6", "bf16x3", "f16x3") and self.width == 256:
-            ns = {"bf16x6": 3, "bf16x3": 2, "f16x3": _lib.SPLIT_F16X3}[self.precision]
-            packed = self.packed_weights_bf16(desc, ns)
-            with torch.cuda.device(add.device), _lib.timed(f"mlp_fwd[n={n}]"):
-                check(lib.snerf_mlp_fwd_bf16_f32(desc, ptr(packed), ns, ptr(dummy_x), ptr(d), 0, ptr(add), n,
-                                                 int(samples_per_ray), ptr(raw), current_stream()), "snerf_mlp_fwd_bf16_f32")
-            return raw
-        packed = self.packed_weights(desc)
-        ws, nb = _fold_workspace(lib.snerf_mlp_fold_workspace_bytes, desc, n, samples_per_ray, add.device)
-        with torch.cuda.device(add.device), _lib.timed(f"mlp_fwd[n={n}]"):
-            check(lib.snerf_mlp_fwd_ws_f32(desc, ptr(packed), ptr(dummy_x), ptr(d), 0, ptr(add), n, int(samples_per_ray),
-                                           ptr(raw), ptr(ws), nb, current_stream()), "snerf_mlp_fwd_ws_f32")
+        # (composed = False: this call has always run on the regular stream, in eval() too - see _launch_forward)
+        _launch_forward(self, desc, _split_code(self, 0), dummy_x, d, 0, samples_per_ray, add, raw, composed=False, inference=True)
         return raw

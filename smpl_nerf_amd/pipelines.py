@@ -13,10 +13,14 @@ materialised in HBM.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import torch
 from torch import nn
 
+from . import _lib
 from . import ops
+from ._lib import check, current_stream, ptr
 
 
 class _NullCtx:
@@ -87,22 +91,9 @@ class PipelineArgs:
         return cls(**d)
 
 
-def _infer_streams(prec, nets, descs, packed):
-    """fp32 render calls of nets in eval mode run on the composed inference streams (nets.RenderRayNet.packed_weights_infer):
-    (SNERF_FP32_INFER, those streams) when every net has one, else the regular fp32 streams; split-precision streams pass."""
-    from . import _lib
-    if prec != 0:
-        return prec, packed
-    infer = [m.packed_weights_infer(d) for m, d in zip(nets, descs)]
-    if any(p is None for p in infer):
-        return prec, [m.packed_weights(d) for m, d in zip(nets, descs)]
-    return _lib.FP32_INFER, infer
-
-
-def _sampler_prec(prec: int, args) -> int:
-    """The precision code of a render entry with SNERF_REFERENCE_SUM ORed in when strict mode's sum runs on the device."""
-    from . import _lib
-    return prec | (_lib.REFERENCE_SUM if getattr(args, "strict_cumsum", 0) and ops.device_reference_sum_ok() else 0)
+def joints_38_41(goal_pose):
+    """The two joint angles the reference hard-codes (models/smpl_nerf_pipeline.py:28, append_to_nerf_pipeline.py:26)."""
+    return torch.stack([goal_pose[:, 38], goal_pose[:, 41]], axis=-1)
 
 
 class NerfPipeline(nn.Module):
@@ -119,7 +110,7 @@ class NerfPipeline(nn.Module):
     def set_precision(self, precision: str):
         """Matrix-core arithmetic of every net of the pipeline: "fp32" (exact fp32 MFMA), "bf16x6" (split-bf16, fp32-class
         accuracy - the parity mode on the bf16 matrix cores) or "bf16x3" (split-bf16, ~2^-16 relative)."""
-        if precision not in ("fp32", "bf16x6", "bf16x3", "f16x3"):
+        if precision not in _lib.PRECISIONS:
             raise ValueError(f"unknown precision {precision!r}")
         for m in self.modules():
             if hasattr(m, "precision") and m is not self:
@@ -131,11 +122,17 @@ class NerfPipeline(nn.Module):
         std = getattr(self.args, "sigma_noise_std", 0.)
         return torch.normal(0, std, shape, device=device) if std > 0. else None
 
+    def _net_desc(self, net):
+        """The descriptor of the fused (encode + MLP) path of one of the pipeline's two nets - what its launches, its single-call
+        entry and the one-call training step (trainer.py) all pass."""
+        return net.desc_for_encoders(self.position_encoder, self.direction_encoder, False)
+
     # keep_fine = True (checkers only: tools/ab/fuzz_*.py): forward() leaves the merged depths and the hierarchical sample points
     # - which are not outputs of the reference's forward - in `last_fine`; off by default (ADVICE r05: a [B, N, 3] tensor pinned
     # between calls, 38 MB for a 128 x 128 frame)
     keep_fine = False
     last_fine = None
+    _pose_in_batch = 0      # 1: data[4] is a goal pose, which the single-call entry reads through a raw fp32 device pointer
 
     def _single_call_ok(self, data) -> bool:
         """Inference (autograd off) goes through the single C-ABI call of render_rays() - what inference.py:251-252's
@@ -143,88 +140,132 @@ class NerfPipeline(nn.Module):
         them bit for bit).  The five-call form stays for autograd, for a _lib.profile() (which brackets every launch with an
         event pair: bench.py's roofline), for the checkers' keep_fine and for the strict sampler on hosts where it is a host
         round trip (ops.device_reference_sum_ok() false)."""
-        from . import _lib
-        if torch.is_grad_enabled() or _lib._PROFILE is not None or self.keep_fine:
+        if self._single_call is None or torch.is_grad_enabled() or _lib._PROFILE is not None or self.keep_fine:
             return False
         if getattr(self.args, "strict_cumsum", 0) and not ops.device_reference_sum_ok():
             return False
         nets = [self.model_coarse, self.model_fine] + ([self.model_warp_field] if hasattr(self, "model_warp_field") else [])
         if len({getattr(m, "precision", "fp32") for m in nets}) != 1 or any(getattr(m, "_layered", False) for m in nets):
             return False      # (nets above the fused kernels' widths run layer by layer: layered.py)
-        return all(torch.is_tensor(t) and t.is_cuda and (t.dtype == torch.float32) for t in data[:4])
+        return all(torch.is_tensor(t) and t.is_cuda and (t.dtype == torch.float32) for t in data[:4 + self._pose_in_batch])
 
     def forward(self, data):
         if self._single_call_ok(data):
             return self.render_rays(data)
         return self._forward_calls(data)
 
-    def _forward_calls(self, data):
-        ray_samples, ray_translation, ray_direction, z_vals, _ = data
+    def _march(self, data, stage, coarse_only=False):
+        """The ray march every pipeline with a compositing runs, launch by launch (models/nerf_pipeline.py:29-67): coarse stage ->
+        composite -> hierarchical samples on the un-warped ray -> fine stage -> composite.  What a pipeline adds is its stage:
+
+            stage(samples, samples per ray, fine: bool) -> (raw [B * n, 4], per-sample directions or None, (warp, warped) or ())
+            (warp and warped come back in the shape of the samples; a stage may leave them flat, [B * n, 3])
+
+        The coarse compositing scales the distances by the stage's per-sample directions where it returns some and by the ray
+        direction otherwise; the fine one always by the ray direction (models/smpl_nerf_pipeline.py:63 against :95-98).  A stage
+        that warps returns (warp, warped), and the result carries them around the samples: (rgb, rgb_fine, warp, samples, warped,
+        densities) instead of (rgb, rgb_fine, samples, densities).  The sigma noise of a compositing is drawn after its stage's
+        launch.  coarse_only: no fine pass whatever args.run_fine says, and the coarse weights are not asked for."""
+        ray_samples, ray_translation, ray_direction, z_vals = data[:4]
         args = self.args
         B, Nc = z_vals.shape
         wb = bool(args.white_background)
         dev = ray_samples.device
-        # coarse net on the given samples (:29-41)
-        raw = self.model_coarse.forward_fused(ray_samples, ray_direction, Nc, self.position_encoder,
-                                              self.direction_encoder)
-        rgb, weights, densities = ops.composite(raw.view(B, Nc, 4), z_vals, ray_direction, wb,
-                                                self._noise((B, Nc), dev))                        # :42
-        if not args.run_fine:
-            return rgb, rgb, ray_samples, densities                                               # :43-44
-        # hierarchical samples (:47) and the fine net on them (:49-60)
+
+        def outputs(rgb_fine, samples, densities, extra):
+            if not extra:
+                return rgb, rgb_fine, samples, densities
+            warp, warped = (t if t.shape == samples.shape else t.view(samples.shape) for t in extra)
+            return rgb, rgb_fine, warp, samples, warped, densities
+
+        raw, sdirs, extra = stage(ray_samples, Nc, False)
+        rgb, weights, densities = ops.composite(raw.view(B, Nc, 4), z_vals, ray_direction if sdirs is None else sdirs.view(B, Nc, 3),
+                                                wb, self._noise((B, Nc), dev), want_weights=not coarse_only)
+        if coarse_only or not args.run_fine:
+            return outputs(rgb, ray_samples, densities, extra)      # (the same tensor twice and the caller's own samples, quirk Q10)
         hs = ops.hierarchical_samples(ray_translation, ray_direction, z_vals, weights, args.number_fine_samples,
                                       strict=bool(getattr(args, "strict_cumsum", 0)))
         z_fine, ray_samples_fine = hs["z_fine"], hs["pts"]
         if self.keep_fine:
             self.last_fine = (z_fine, ray_samples_fine)
         N = z_fine.shape[1]
-        raw_fine = self.model_fine.forward_fused(ray_samples_fine, ray_direction, N, self.position_encoder,
-                                                 self.direction_encoder)
-        rgb_fine, _, densities_fine = ops.composite(raw_fine.view(B, N, 4), z_fine, ray_direction, wb,
-                                                    self._noise((B, N), dev), want_weights=False)  # :65
-        return rgb, rgb_fine, ray_samples_fine, densities_fine                                    # :67
+        raw_fine, _, extra = stage(ray_samples_fine, N, True)
+        rgb_fine, _, densities_fine = ops.composite(raw_fine.view(B, N, 4), z_fine, ray_direction, wb, self._noise((B, N), dev),
+                                                    want_weights=False)
+        return outputs(rgb_fine, ray_samples_fine, densities_fine, extra)
 
+    def _forward_calls(self, data):
+        ray_direction = data[2]
+
+        def stage(samples, n, fine):      # the net on the given samples (:29-41) / on the hierarchical ones (:49-60)
+            net = self.model_fine if fine else self.model_coarse
+            return net.forward_fused(samples, ray_direction, n, self.position_encoder, self.direction_encoder), None, ()
+
+        return self._march(data, stage)      # :42-44, :47, :65-67
 
     def render_rays(self, data):
-        """forward(data) for inference through the single C-ABI call snerf_render_rays_f32 (include/smplnerf.h):
-        same outputs, one host call instead of five - the entry point a non-Python host binds.  No autograd."""
-        from . import _lib
-        from ._lib import check, ptr, current_stream
-        if any(getattr(m, "_layered", False) for m in self.children()):      # (widths above the fused kernels': layered.py)
+        """forward(data) for inference through the pipeline's single C-ABI call (include/smplnerf.h: _single_call): same outputs,
+        one host call instead of five - the entry point a non-Python host binds.  No autograd.  A pipeline without such an entry,
+        and nets above the fused kernels' widths (layered.py), run forward()'s launches under no_grad - the same kernels, the same
+        results."""
+        if self._single_call is None or any(getattr(m, "_layered", False) for m in self.children()):
             with torch.no_grad():
                 return self._forward_calls(data)
-        ray_samples, ray_translation, ray_direction, z_vals, _ = data
+        return self._single_call(data)
+
+    def _render_setup(self, data, nets, workspace_entry, workspace_takes_descs=False, n_sample_tensors=1):
+        """What the single-call entries share.  `nets`: the coarse and the fine net, then whatever else must run in their precision.
+        Returns a record of the arguments in the entries' order - head (the two nets' descriptors and streams), mid (precision,
+        samples, origins, directions, depths), tail (u, coarse and fine sigma noise, B, Nc, Nf, white_background, workspace), outs
+        (_render_outputs) - with prec, the nets' precision code.  fp32 calls of nets in eval mode run on the composed inference
+        streams (nets.RenderRayNet.packed_weights_infer): SNERF_FP32_INFER and those streams when every net has one, else the
+        regular fp32 streams.  Both noise tensors are drawn here, coarse then fine, in front of the call."""
+        ray_samples, ray_translation, ray_direction, z_vals = data[:4]
         args = self.args
         B, Nc = z_vals.shape
         Nf = int(args.number_fine_samples) if args.run_fine else 0
         N = Nc + Nf
         dev = ray_samples.device
-        mc, mf = self.model_coarse, self.model_fine
-        if mc.precision != mf.precision:
-            raise RuntimeError("render_rays: both nets must use the same precision mode")
-        prec = {"fp32": 0, "bf16x3": 2, "bf16x6": 3, "f16x3": _lib.SPLIT_F16X3}[mc.precision]
-        if mc.width != 256 or mf.width != 256:
-            prec = 0      # the split-precision kernels exist for width 256; other widths run exact fp32 like forward() does
-        descs, packed = [], []
-        for m in (mc, mf):
-            d = m.desc_for_encoders(self.position_encoder, self.direction_encoder, False)
-            descs.append(d)
-            packed.append(None if prec == 0 else m.packed_weights_bf16(d, prec))
-        prec, packed = _infer_streams(prec, (mc, mf), descs, packed)
+        prec = _lib.precision_code(nets, "render_rays")
+        descs = [self._net_desc(m) for m in nets[:2]]
+        if prec:
+            packed = [m.packed_weights_bf16(d, prec) for m, d in zip(nets, descs)]
+        else:
+            packed = [m.packed_weights_infer(d) for m, d in zip(nets, descs)]
+            if any(p is None for p in packed):
+                packed = [m.packed_weights(d) for m, d in zip(nets, descs)]
+            else:
+                prec = _lib.FP32_INFER
         lib = _lib.load()
-        ws = torch.empty(int(lib.snerf_render_rays_workspace_bytes(B, Nc, Nf)), device=dev, dtype=torch.uint8)
-        rgb, rgb_fine, samples_fine, dens = _render_outputs(B, N, 1, dev)
+        need = int(getattr(lib, workspace_entry)(*(descs if workspace_takes_descs else ()), B, Nc, Nf))
+        if need < 0:
+            check(need, workspace_entry)
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        outs = _render_outputs(B, N, n_sample_tensors, dev)
         u = ops.uniform_u(Nf, dev) if Nf else None
         nc, nf = self._noise((B, Nc), dev), (self._noise((B, N), dev) if Nf else None)
         x, o, d, z = (t.contiguous() for t in (ray_samples, ray_translation, ray_direction, z_vals))
-        with _on_device(dev), _lib.timed("render_rays"):
-            check(lib.snerf_render_rays_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), _sampler_prec(prec, args), ptr(x), ptr(o),
-                                            ptr(d), ptr(z), ptr(u), ptr(nc), ptr(nf), B, Nc, Nf,
-                                            1 if args.white_background else 0, ptr(ws), ptr(rgb), ptr(rgb_fine),
-                                            ptr(samples_fine), ptr(dens), current_stream()), "snerf_render_rays_f32")
-        if not Nf:
-            return rgb, rgb, ray_samples, dens      # (:43-44: the same tensor twice and the caller's own samples, quirk Q10)
-        return rgb, rgb_fine, samples_fine, dens
+        # the precision argument: SNERF_REFERENCE_SUM ORed in when strict mode's sum runs on the device
+        strict = _lib.REFERENCE_SUM if getattr(args, "strict_cumsum", 0) and ops.device_reference_sum_ok() else 0
+        return SimpleNamespace(
+            lib=lib, dev=dev, prec=prec, outs=outs, head=(descs[0], ptr(packed[0]), descs[1], ptr(packed[1])),
+            mid=(prec | strict, ptr(x), ptr(o), ptr(d), ptr(z)),
+            tail=(ptr(u), ptr(nc), ptr(nf), B, Nc, Nf, 1 if args.white_background else 0, ptr(ws)),
+            keep=(packed, ws, u, nc, nf, x, o, d, z))      # (what only the pointers above refer to, alive until the call is enqueued)
+
+    def _render_result(self, data, r):
+        """The entry's outputs as forward() returns them; run_fine = 0: the coarse colour twice and the caller's own samples
+        (models/nerf_pipeline.py:43-44, append_smpl_params_pipeline.py:56-57, quirk Q10)."""
+        if self.args.run_fine:
+            return tuple(r.outs)
+        return r.outs[0], r.outs[0], data[0], r.outs[-1]
+
+    def _single_call(self, data):
+        """snerf_render_rays_f32."""
+        r = self._render_setup(data, (self.model_coarse, self.model_fine), "snerf_render_rays_workspace_bytes")
+        with _on_device(r.dev), _lib.timed("render_rays"):
+            check(r.lib.snerf_render_rays_f32(*r.head, *r.mid, *r.tail, *map(ptr, r.outs), current_stream()), "snerf_render_rays_f32")
+        return self._render_result(data, r)
 
 
 class SmplNerfPipeline(NerfPipeline):
@@ -244,100 +285,58 @@ class SmplNerfPipeline(NerfPipeline):
         """PositionalEncoder(0, True): the identity columns only (warp-net input of human_pose_encoding = 0)."""
         number_frequencies, include_identity, output_dim = 0, True, 1
 
+    _pose_in_batch = 1
+
     def __init__(self, model_coarse, model_fine, model_warp_field, args, position_encoder, direction_encoder,
                  human_pose_encoder):
         super().__init__(model_coarse, model_fine, args, position_encoder, direction_encoder)
         self.human_pose_encoder = human_pose_encoder
         self.model_warp_field = model_warp_field
 
-    def _stage(self, net, samples, ray_translation, pose_enc, n_per_ray, warp_encoder=None):
-        warp, warped, sdirs = self.model_warp_field.forward_fused(samples, pose_enc, ray_translation, n_per_ray,
-                                                                  warp_encoder or self.position_encoder)
-        raw = net.forward_fused(warped, sdirs, n_per_ray, self.position_encoder, self.direction_encoder)
-        return warp, warped, sdirs, raw
+    def _joint_pose(self, goal_pose):
+        """(the two joint angles [B, 2], their encoding): :28, :30 - what the warp net reads per ray."""
+        two = joints_38_41(goal_pose).contiguous()
+        return two, self.human_pose_encoder.encode(two).contiguous()
+
+    def _warp_desc(self):
+        """The warp net's descriptor with the encoded pose (the single-call entry and the one-call training step)."""
+        return self.model_warp_field.desc_for_encoder(self.position_encoder)
 
     def _single_call_ok(self, data) -> bool:
         # (the one-call entry covers the full coarse + fine march with the encoded pose)
-        return bool(self.args.human_pose_encoding and self.args.run_fine) and super()._single_call_ok(data) and \
-            torch.is_tensor(data[4]) and data[4].is_cuda and data[4].dtype == torch.float32
+        return bool(self.args.human_pose_encoding and self.args.run_fine) and super()._single_call_ok(data)
 
     def _forward_calls(self, data):
-        ray_samples, ray_translation, ray_direction, z_vals, goal_pose, _ = data
-        args = self.args
-        B, Nc = z_vals.shape
-        wb = bool(args.white_background)
-        dev = ray_samples.device
-        goal_pose = torch.stack([goal_pose[:, 38], goal_pose[:, 41]], axis=-1).contiguous()         # :28
-        pose_enc = self.human_pose_encoder.encode(goal_pose)                                       # :30
-        if args.human_pose_encoding:                                                               # :37-39
-            warp, warped, sdirs, raw = self._stage(self.model_coarse, ray_samples, ray_translation, pose_enc, Nc)
-        else:                                                                                      # :40-45
-            warp, warped, sdirs, raw = self._stage(self.model_coarse, ray_samples, ray_translation, goal_pose, Nc,
-                                                   self._RawPositions)
-        rgb, weights, densities = ops.composite(raw.view(B, Nc, 4), z_vals, sdirs.view(B, Nc, 3), wb,
-                                                self._noise((B, Nc), dev))                        # :63
-        if not args.run_fine:
-            return rgb, rgb, warp.view(B, Nc, 3), ray_samples, warped.view(B, Nc, 3), densities   # :64-65
-        hs = ops.hierarchical_samples(ray_translation, ray_direction, z_vals, weights, args.number_fine_samples,
-                                      strict=bool(getattr(args, "strict_cumsum", 0)))
-        z_fine, ray_samples_fine = hs["z_fine"], hs["pts"]                                         # :68
-        if self.keep_fine:
-            self.last_fine = (z_fine, ray_samples_fine)
-        N = z_fine.shape[1]
-        warp_f, warped_f, _, raw_f = self._stage(self.model_fine, ray_samples_fine, ray_translation, pose_enc, N)
-        rgb_fine, _, densities_fine = ops.composite(raw_f.view(B, N, 4), z_fine, ray_direction, wb,
-                                                    self._noise((B, N), dev), want_weights=False)  # :95-98
-        return (rgb, rgb_fine, warp_f.view(B, N, 3), ray_samples_fine, warped_f.view(B, N, 3), densities_fine)  # :100
+        ray_translation = data[1]
+        two, pose_enc = self._joint_pose(data[4])
 
+        def stage(samples, n, fine):
+            # the coarse stage of human_pose_encoding = 0 reads the raw angles beside un-encoded positions (:40-45); every other
+            # one the encoded pose (:37-39, :71-77)
+            raw_pose = not fine and not self.args.human_pose_encoding
+            warp, warped, sdirs = self.model_warp_field.forward_fused(
+                samples, two if raw_pose else pose_enc, ray_translation, n, self._RawPositions if raw_pose else self.position_encoder)
+            net = self.model_fine if fine else self.model_coarse
+            return net.forward_fused(warped, sdirs, n, self.position_encoder, self.direction_encoder), sdirs, (warp, warped)
 
-    def render_rays(self, data):
-        """forward(data) for inference through the single C-ABI call snerf_render_rays_smpl_f32.  The one-call entry covers
-        the full coarse + fine march with the encoded pose; run_fine = 0 and human_pose_encoding = 0 (three launches instead
-        of eight) go through forward() under no_grad - the same kernels, the same results."""
-        from . import _lib
-        from ._lib import check, ptr, current_stream
-        if any(getattr(m, "_layered", False) for m in self.children()):      # (widths above the fused kernels': layered.py)
+        return self._march(data, stage)      # :63-65, :68, :95-100
+
+    def _single_call(self, data):
+        """snerf_render_rays_smpl_f32.  The entry covers the full coarse + fine march with the encoded pose; run_fine = 0 and
+        human_pose_encoding = 0 (three launches instead of eight) go through forward()'s launches under no_grad."""
+        if not self.args.human_pose_encoding or not self.args.run_fine:
             with torch.no_grad():
                 return self._forward_calls(data)
-        ray_samples, ray_translation, ray_direction, z_vals, goal_pose, _ = data
-        args = self.args
-        if not args.human_pose_encoding or not args.run_fine:
-            with torch.no_grad():
-                return self._forward_calls(data)
-        B, Nc = z_vals.shape
-        Nf = int(args.number_fine_samples)
-        N = Nc + Nf
-        dev = ray_samples.device
-        mc, mf, mw = self.model_coarse, self.model_fine, self.model_warp_field
-        if not (mc.precision == mf.precision == mw.precision):
-            raise RuntimeError("render_rays: all nets must use the same precision mode (set_precision)")
-        prec = {"fp32": 0, "bf16x3": 2, "bf16x6": 3, "f16x3": _lib.SPLIT_F16X3}[mc.precision]
-        if any(m.width != 256 for m in (mc, mf, self.model_warp_field)):
-            prec = 0      # (split precision: width 256 only - other widths run exact fp32, like forward())
-        goal_pose = torch.stack([goal_pose[:, 38], goal_pose[:, 41]], axis=-1)
-        pose_enc = self.human_pose_encoder.encode(goal_pose.contiguous()).contiguous()
-        descs, packed = [], []
-        for m in (mc, mf):
-            d = m.desc_for_encoders(self.position_encoder, self.direction_encoder, False)
-            descs.append(d)
-            packed.append(None if prec == 0 else m.packed_weights_bf16(d, prec))
-        prec, packed = _infer_streams(prec, (mc, mf), descs, packed)
-        pe = self.position_encoder
-        wdesc = _lib.WarpDesc(mw.width, pe.number_frequencies, 1 if pe.include_identity else 0, mw.direcions_dim)
-        wpacked = mw._packed(wdesc) if prec in (0, _lib.FP32_INFER) else mw._packed_bf16(wdesc)
-        lib = _lib.load()
-        ws = torch.empty(int(lib.snerf_render_rays_smpl_workspace_bytes(B, Nc, Nf)), device=dev, dtype=torch.uint8)
-        rgb, rgb_fine, warp_f, samples_f, warped_f, dens = _render_outputs(B, N, 3, dev)
-        u = ops.uniform_u(Nf, dev)
-        nc, nf = self._noise((B, Nc), dev), self._noise((B, N), dev)
-        x, o, d, z = (t.contiguous() for t in (ray_samples, ray_translation, ray_direction, z_vals))
-        with _on_device(dev), _lib.timed("render_rays_smpl"):
-            check(lib.snerf_render_rays_smpl_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), wdesc, ptr(wpacked), _sampler_prec(prec, args),
-                                                 ptr(x), ptr(o), ptr(d), ptr(z), ptr(pose_enc), ptr(u), ptr(nc), ptr(nf), B, Nc,
-                                                 Nf, 1 if args.white_background else 0, ptr(ws), ptr(rgb), ptr(rgb_fine),
-                                                 ptr(warp_f), ptr(samples_f), ptr(warped_f), ptr(dens), current_stream()),
-                  "snerf_render_rays_smpl_f32")
-        return rgb, rgb_fine, warp_f, samples_f, warped_f, dens
+        mw = self.model_warp_field
+        pose_enc = self._joint_pose(data[4])[1]
+        r = self._render_setup(data, (self.model_coarse, self.model_fine, mw), "snerf_render_rays_smpl_workspace_bytes",
+                               n_sample_tensors=3)
+        wdesc = self._warp_desc()
+        wpacked = mw._packed(wdesc) if r.prec in (0, _lib.FP32_INFER) else mw._packed_bf16(wdesc)
+        with _on_device(r.dev), _lib.timed("render_rays_smpl"):
+            check(r.lib.snerf_render_rays_smpl_f32(*r.head, wdesc, ptr(wpacked), *r.mid, ptr(pose_enc), *r.tail, *map(ptr, r.outs),
+                                                   current_stream()), "snerf_render_rays_smpl_f32")
+        return tuple(r.outs)
 
 
 class AppendVerticesPipeline(NerfPipeline):
@@ -352,47 +351,36 @@ class AppendVerticesPipeline(NerfPipeline):
     ray direction.  That is what is evaluated here - without materialising the
     [B*N, 20754] fp32 input rows (83 KB per sample in the reference)."""
 
+    _single_call = None      # (estimator and body model are torch modules in front of the nets: no single-call entry)
+
     def __init__(self, model_coarse, model_fine, smpl_estimator, smpl_model, args, position_encoder,
                  direction_encoder):
         super().__init__(model_coarse, model_fine, args, position_encoder, direction_encoder)
         self.smpl_estimator = smpl_estimator
         self.smpl_model = smpl_model
 
-    def _single_call_ok(self, data) -> bool:
-        return False      # (estimator and body model are torch modules in front of the nets: no single-call entry)
+    def _net_desc(self, net):
+        return net.desc_for_rows()
 
-    def render_rays(self, data):
-        with torch.no_grad():
-            return self._forward_calls(data)
-
-    def _forward_calls(self, data):
-        ray_samples, ray_translation, ray_direction, z_vals, images, _ = data
-        args = self.args
-        B, Nc = z_vals.shape
-        wb = bool(args.white_background)
-        dev = ray_samples.device
+    def _vertex_rows(self, images, B, dev):
+        """Estimator -> body model -> the vertex floats the nets read, [B, positions_dim] (:30-41 and quirk Q7)."""
         goal_poses, betas = self.smpl_estimator(images)                                            # :30
         global_orient = torch.zeros([1, 3], device=dev).expand(B, -1)                              # :13, :36
         goal_models = self.smpl_model(betas=betas, return_verts=True, body_pose=goal_poses,
                                       global_orient=global_orient)                                 # :38-39
         vertices_flat = goal_models.vertices.reshape(B, -1)                                        # :41
-        pdim = self.model_coarse.positions_dim
-        ray_inputs = vertices_flat[:, :pdim]          # the columns AppendVerticesNet.forward actually reads
-        raw = self.model_coarse.forward_rays(ray_inputs, ray_direction, Nc, B * Nc)
-        rgb, weights, densities = ops.composite(raw.view(B, Nc, 4), z_vals, ray_direction, wb,
-                                                self._noise((B, Nc), dev))                        # :65
-        if not args.run_fine:
-            return rgb, rgb, ray_samples, densities                                               # :66-67
-        hs = ops.hierarchical_samples(ray_translation, ray_direction, z_vals, weights, args.number_fine_samples,
-                                      strict=bool(getattr(args, "strict_cumsum", 0)))
-        z_fine, ray_samples_fine = hs["z_fine"], hs["pts"]                                         # :70
-        if self.keep_fine:
-            self.last_fine = (z_fine, ray_samples_fine)
-        N = z_fine.shape[1]
-        raw_f = self.model_fine.forward_rays(ray_inputs, ray_direction, N, B * N)
-        rgb_fine, _, densities_fine = ops.composite(raw_f.view(B, N, 4), z_fine, ray_direction, wb,
-                                                    self._noise((B, N), dev), want_weights=False)  # :92
-        return rgb, rgb_fine, ray_samples_fine, densities_fine                                    # :94
+        return vertices_flat[:, :self.model_coarse.positions_dim]          # the columns AppendVerticesNet.forward actually reads
+
+    def _forward_calls(self, data):
+        ray_direction = data[2]
+        B = data[3].shape[0]
+        ray_inputs = self._vertex_rows(data[4], B, data[0].device)
+
+        def stage(samples, n, fine):
+            net = self.model_fine if fine else self.model_coarse
+            return net.forward_rays(ray_inputs, ray_direction, n, B * n), None, ()
+
+        return self._march(data, stage)      # :65-67, :70, :92-94
 
 
 class DynamicPipeline(NerfPipeline):
@@ -406,22 +394,17 @@ class DynamicPipeline(NerfPipeline):
     args.run_fine says (:83).  Returns (rgb, rgb, warp [B,S,3], ray_samples, warped [B,S,3], densities).  The loss reaches the
     estimator's poses through the warp (solver/dynamic_solver.py): both kernels are differentiable."""
 
+    _single_call = None      # (estimator and body model are torch modules in front of the warp: no single-call entry)
+
     def __init__(self, model_coarse, model_fine, smpl_estimator, smpl_model, args, position_encoder, direction_encoder):
         super().__init__(model_coarse, model_fine, args, position_encoder, direction_encoder)
         self.smpl_estimator = smpl_estimator
         self.smpl_model = smpl_model
 
-    def _single_call_ok(self, data) -> bool:
-        return False      # (estimator and body model are torch modules in front of the warp: no single-call entry)
-
-    def render_rays(self, data):
-        with torch.no_grad():
-            return self._forward_calls(data)
-
     def _forward_calls(self, data):
         ray_samples, ray_translation, ray_direction, z_vals, images, _ = data
         args = self.args
-        B, Nc = z_vals.shape
+        B = z_vals.shape[0]
         dev = ray_samples.device
         goal_poses, betas = self.smpl_estimator(images)                                            # :36
         global_orient = torch.zeros([1, 3], device=dev).expand(B, -1)                              # :18, :42
@@ -432,10 +415,11 @@ class DynamicPipeline(NerfPipeline):
                                global_orient=global_orient).vertices                               # :48-50
         warp, warped, sdirs = ops.vertex_attention_warp(ray_samples, goal, canonical.expand_as(goal), ray_translation,
                                                         args.warp_radius, args.warp_temperature)   # :51-70
-        raw = self.model_coarse.forward_fused(warped, sdirs, Nc, self.position_encoder, self.direction_encoder)   # :68-78
-        rgb, _, densities = ops.composite(raw.view(B, Nc, 4), z_vals, sdirs.view(B, Nc, 3), bool(args.white_background),
-                                          self._noise((B, Nc), dev), want_weights=False)           # :81
-        return rgb, rgb, warp.view(B, Nc, 3), ray_samples, warped.view(B, Nc, 3), densities        # :83
+
+        def stage(samples, n, fine):      # :68-78
+            return self.model_coarse.forward_fused(warped, sdirs, n, self.position_encoder, self.direction_encoder), sdirs, (warp, warped)
+
+        return self._march(data, stage, coarse_only=True)      # :81, :83
 
 
 class VertexSpherePipeline(NerfPipeline):
@@ -446,25 +430,19 @@ class VertexSpherePipeline(NerfPipeline):
     the compositing that scales distances by |warped - o| (:42) - DynamicPipeline's tail.  Returns (rgb, rgb, warp, ray_samples,
     warped [B,S,3], densities); with args.run_fine the reference's NotImplementedError (:50), raised before any launch."""
 
-    def _single_call_ok(self, data) -> bool:
-        return False      # (no single-call entry takes a warp from the batch)
-
-    def render_rays(self, data):
-        with torch.no_grad():
-            return self._forward_calls(data)
+    _single_call = None      # (no single-call entry takes a warp from the batch)
 
     def _forward_calls(self, data):
-        ray_samples, ray_translation, ray_direction, z_vals, warp, _ = data
-        args = self.args
-        if args.run_fine:
+        ray_samples, ray_translation, _, _, warp, _ = data
+        if self.args.run_fine:
             raise NotImplementedError('calculating the deterministic/true warp for the fine samples in not implemented yet')   # :50
-        B, Nc = z_vals.shape
         warped = ray_samples + warp                                                                # :28
         sdirs = warped - ray_translation[:, None, :]                                               # :31
-        raw = self.model_coarse.forward_fused(warped, sdirs, Nc, self.position_encoder, self.direction_encoder)   # :29-41
-        rgb, _, densities = ops.composite(raw.view(B, Nc, 4), z_vals, sdirs, bool(args.white_background),
-                                          self._noise((B, Nc), ray_samples.device), want_weights=False)           # :42
-        return rgb, rgb, warp, ray_samples, warped, densities                                      # :48
+
+        def stage(samples, n, fine):      # :29-41
+            return self.model_coarse.forward_fused(warped, sdirs, n, self.position_encoder, self.direction_encoder), sdirs, (warp, warped)
+
+        return self._march(data, stage, coarse_only=True)      # :42, :48
 
 
 class SingleSamplePipeline(NerfPipeline):
@@ -475,15 +453,10 @@ class SingleSamplePipeline(NerfPipeline):
     encode + MLP with one sample per ray) and rgb = sigmoid(raw[..., :3]) (:39): no density, no compositing.  Returns (rgb, rgb).
     The constructor is the reference's: there is no fine net."""
 
+    _single_call = None      # (no single-call entry renders without compositing)
+
     def __init__(self, model_coarse, args, position_encoder, direction_encoder):
         super().__init__(model_coarse, model_coarse, args, position_encoder, direction_encoder)
-
-    def _single_call_ok(self, data) -> bool:
-        return False      # (no single-call entry renders without compositing)
-
-    def render_rays(self, data):
-        with torch.no_grad():
-            return self._forward_calls(data)
 
     def _forward_calls(self, data):
         ray_sample, ray_translation, _, _, warp, _ = data
@@ -501,6 +474,8 @@ class AppendSmplParamsPipeline(NerfPipeline):
     the fused kernel's `additional` input (weight columns in front of the position encoding) instead of
     being expanded to every sample."""
 
+    _pose_in_batch = 1
+
     def __init__(self, model_coarse, model_fine, args, position_encoder, direction_encoder, human_pose_encoder):
         super().__init__(model_coarse, model_fine, args, position_encoder, direction_encoder)
         self.human_pose_encoder = human_pose_encoder
@@ -508,86 +483,38 @@ class AppendSmplParamsPipeline(NerfPipeline):
     def _select(self, goal_pose):
         return goal_pose
 
-    def _single_call_ok(self, data) -> bool:
-        return super()._single_call_ok(data) and torch.is_tensor(data[4]) and data[4].is_cuda and data[4].dtype == torch.float32
+    def _net_desc(self, net):
+        return net.desc_for_encoders(self.position_encoder, self.direction_encoder, True)
+
+    def _pose_rows(self, goal_pose):
+        """The per-ray rows the nets read as additional inputs, [B, additional_input_dim] fp32 (:29-37)."""
+        goal_pose = self._select(goal_pose).contiguous()
+        pose = self.human_pose_encoder.encode(goal_pose) if self.args.human_pose_encoding else goal_pose
+        return pose.reshape(pose.shape[0], -1).contiguous().float()
 
     def _forward_calls(self, data):
-        ray_samples, ray_translation, ray_direction, z_vals, goal_pose, _ = data
-        args = self.args
-        B, Nc = z_vals.shape
-        wb = bool(args.white_background)
-        dev = ray_samples.device
-        goal_pose = self._select(goal_pose).contiguous()
-        pose = self.human_pose_encoder.encode(goal_pose) if args.human_pose_encoding else goal_pose   # :29-37
-        raw = self.model_coarse.forward_fused(ray_samples, ray_direction, Nc, self.position_encoder,
-                                              self.direction_encoder, additional=pose, add_first=True)   # :49-52
-        rgb, weights, densities = ops.composite(raw.view(B, Nc, 4), z_vals, ray_direction, wb,
-                                                self._noise((B, Nc), dev))                             # :55
-        if not args.run_fine:
-            return rgb, rgb, ray_samples, densities                                                    # :56-57
-        hs = ops.hierarchical_samples(ray_translation, ray_direction, z_vals, weights, args.number_fine_samples,
-                                      strict=bool(getattr(args, "strict_cumsum", 0)))
-        z_fine, ray_samples_fine = hs["z_fine"], hs["pts"]                                              # :60
-        if self.keep_fine:
-            self.last_fine = (z_fine, ray_samples_fine)
-        N = z_fine.shape[1]
-        raw_f = self.model_fine.forward_fused(ray_samples_fine, ray_direction, N, self.position_encoder,
-                                              self.direction_encoder, additional=pose, add_first=True)  # :77-81
-        rgb_fine, _, densities_fine = ops.composite(raw_f.view(B, N, 4), z_fine, ray_direction, wb,
-                                                    self._noise((B, N), dev), want_weights=False)       # :89
-        return rgb, rgb_fine, ray_samples_fine, densities_fine                                         # :91
+        ray_direction = data[2]
+        pose = self._pose_rows(data[4])
 
+        def stage(samples, n, fine):      # :49-52, :77-81
+            net = self.model_fine if fine else self.model_coarse
+            return net.forward_fused(samples, ray_direction, n, self.position_encoder, self.direction_encoder, additional=pose,
+                                     add_first=True), None, ()
 
-    def render_rays(self, data):
-        """forward(data) for inference through the single C-ABI call snerf_render_rays_add_f32 (include/smplnerf.h): the pose
-        rows as the nets' per-ray additional inputs, folded per ray inside the call in fp32.  Same outputs as forward()."""
-        from . import _lib
-        from ._lib import check, ptr, current_stream
-        if any(getattr(m, "_layered", False) for m in self.children()):      # (widths above the fused kernels': layered.py)
-            with torch.no_grad():
-                return self._forward_calls(data)
-        ray_samples, ray_translation, ray_direction, z_vals, goal_pose, _ = data
-        args = self.args
-        B, Nc = z_vals.shape
-        Nf = int(args.number_fine_samples) if args.run_fine else 0
-        N = Nc + Nf
-        dev = ray_samples.device
-        mc, mf = self.model_coarse, self.model_fine
-        if mc.precision != mf.precision:
-            raise RuntimeError("render_rays: both nets must use the same precision mode")
-        prec = {"fp32": 0, "bf16x3": 2, "bf16x6": 3, "f16x3": _lib.SPLIT_F16X3}[mc.precision]
-        if mc.width != 256 or mf.width != 256:
-            prec = 0
-        goal_pose = self._select(goal_pose).contiguous()
-        pose = self.human_pose_encoder.encode(goal_pose) if args.human_pose_encoding else goal_pose
-        pose = pose.reshape(B, -1).contiguous().float()
-        descs, packed = [], []
-        for m in (mc, mf):
-            d = m.desc_for_encoders(self.position_encoder, self.direction_encoder, True)
-            descs.append(d)
-            packed.append(None if prec == 0 else m.packed_weights_bf16(d, prec))
-        prec, packed = _infer_streams(prec, (mc, mf), descs, packed)
-        lib = _lib.load()
-        need = int(lib.snerf_render_rays_add_workspace_bytes(descs[0], descs[1], B, Nc, Nf))
-        if need < 0:
-            check(need, "snerf_render_rays_add_workspace_bytes")
-        ws = torch.empty(need, device=dev, dtype=torch.uint8)
-        rgb, rgb_fine, samples_fine, dens = _render_outputs(B, N, 1, dev)
-        u = ops.uniform_u(Nf, dev) if Nf else None
-        nc, nf = self._noise((B, Nc), dev), (self._noise((B, N), dev) if Nf else None)
-        x, o, d, z = (t.contiguous() for t in (ray_samples, ray_translation, ray_direction, z_vals))
-        with _on_device(dev), _lib.timed("render_rays_add"):
-            check(lib.snerf_render_rays_add_f32(descs[0], ptr(packed[0]), descs[1], ptr(packed[1]), _sampler_prec(prec, args), ptr(x), ptr(o), ptr(d),
-                                                ptr(z), ptr(pose), ptr(u), ptr(nc), ptr(nf), B, Nc, Nf,
-                                                1 if args.white_background else 0, ptr(ws), ptr(rgb), ptr(rgb_fine),
-                                                ptr(samples_fine), ptr(dens), current_stream()), "snerf_render_rays_add_f32")
-        if not Nf:
-            return rgb, rgb, ray_samples, dens      # (models/append_smpl_params_pipeline.py:56-57)
-        return rgb, rgb_fine, samples_fine, dens
+        return self._march(data, stage)      # :55-57, :60, :89-91
+
+    def _single_call(self, data):
+        """snerf_render_rays_add_f32: the pose rows as the nets' per-ray additional inputs, folded per ray inside the call in fp32."""
+        pose = self._pose_rows(data[4])
+        r = self._render_setup(data, (self.model_coarse, self.model_fine), "snerf_render_rays_add_workspace_bytes", True)
+        with _on_device(r.dev), _lib.timed("render_rays_add"):
+            check(r.lib.snerf_render_rays_add_f32(*r.head, *r.mid, ptr(pose), *r.tail, *map(ptr, r.outs), current_stream()),
+                  "snerf_render_rays_add_f32")
+        return self._render_result(data, r)
 
 
 class AppendToNerfPipeline(AppendSmplParamsPipeline):
     """models/append_to_nerf_pipeline.py:7-90 drop-in: the same with only joints 38 and 41 of the pose (:26)."""
 
     def _select(self, goal_pose):
-        return torch.stack([goal_pose[:, 38], goal_pose[:, 41]], axis=-1)
+        return joints_38_41(goal_pose)

@@ -505,21 +505,14 @@ class DataParallelTrainer:
                 v.copy_(p.grad)
 
     def _additional_rows(self, oc, batch):
-        pipe, args = self.pipeline, self.pipeline.args
-        if oc["verts"]:      # models/append_vertices_pipeline.py:30-58: estimator -> body model -> the vertex floats the nets read (Q7)
-            images, z_vals = batch[4], batch[3]
-            goal_poses, betas = pipe.smpl_estimator(images)
-            orient = torch.zeros([1, 3], device=z_vals.device).expand(z_vals.shape[0], -1)
-            vertices = pipe.smpl_model(betas=betas, return_verts=True, body_pose=goal_poses, global_orient=orient).vertices
-            return vertices.reshape(z_vals.shape[0], -1)[:, :oc["nets"][0].positions_dim].contiguous().float()
-        # models/append_smpl_params_pipeline.py:29-37 / append_to_nerf_pipeline.py:26: the pose rows the nets read
-        add = pipe._select(batch[4]).contiguous()
-        if args.human_pose_encoding:
-            add = pipe.human_pose_encoder.encode(add)
-        add = add.reshape(add.shape[0], -1).contiguous()
+        """The per-ray rows the nets read, as the pipeline builds them for its own launches."""
+        pipe = self.pipeline
+        if oc["verts"]:
+            return pipe._vertex_rows(batch[4], batch[3].shape[0], batch[3].device).contiguous().float()
+        add = pipe._pose_rows(batch[4])
         if add.shape[1] != oc["nets"][0].additional_input_dim:
             raise RuntimeError("DataParallelTrainer: the pose rows do not match the nets' additional_input_dim")
-        return add.float()
+        return add
 
     # -- marshalling for the call: one job each ---------------------------------------------------------------------------
     def _oc_unpack(self, oc, batch, add_graph):
@@ -541,7 +534,7 @@ class DataParallelTrainer:
         ig = oc["warp"] is not None
         descs, packed, packed_t, adam = [], [], [], (_lib.AdamNet * 2)()
         for k, m in enumerate((mc, mf)):
-            d = m.desc_for_rows() if oc["verts"] else m.desc_for_encoders(pipe.position_encoder, pipe.direction_encoder, bool(oc["posed"]))
+            d = pipe._net_desc(m)
             descs.append(d)
             if k == 1 and not Nf:          # run_fine = 0: the fine net takes no part (models/nerf_pipeline.py:43-44)
                 packed.append(None), packed_t.append(None)
@@ -563,8 +556,7 @@ class DataParallelTrainer:
         """The warp net's descriptor, its streams (the transposed one is kept in oc["warp"] until the forward stream is re-built: the
         weights changed behind the step) and the encoded pose rows."""
         lib, pipe, W, dev = oc["lib"], self.pipeline, oc["warp"], self._flat_p.device
-        mw, pe_ = W["net"], pipe.position_encoder
-        wdesc = _lib.WarpDesc(mw.width, pe_.number_frequencies, 1 if pe_.include_identity else 0, mw.direcions_dim)
+        mw, wdesc = W["net"], pipe._warp_desc()
         packed_w = mw._packed(wdesc, training=True)
         if W["packed_t"] is None or W["packed_t"][0] is not packed_w:
             sizes = [ctypes.c_int64() for _ in range(4)]
@@ -574,8 +566,7 @@ class DataParallelTrainer:
             with torch.cuda.device(dev):
                 _lib.check(lib.snerf_warp_pack_t_f32(wdesc, seg_w.data_ptr(), pt.data_ptr(), _lib.current_stream()), "snerf_warp_pack_t_f32")
             W["packed_t"] = (packed_w, pt)
-        two = torch.stack([goal_pose[:, 38], goal_pose[:, 41]], axis=-1).contiguous()          # models/smpl_nerf_pipeline.py:28
-        pose_enc = pipe.human_pose_encoder.encode(two).contiguous()                              # :30
+        pose_enc = pipe._joint_pose(goal_pose)[1]
         return SimpleNamespace(desc=wdesc, packed=packed_w, packed_t=W["packed_t"][1], pose_enc=pose_enc, off=W["seg"][0])
 
     def _oc_workspace(self, oc, nets, warp, B, Nc, Nf):

@@ -376,6 +376,26 @@ def test_like_training_and_the_knob_keep_the_training_forwards_bits(dev, tmp_pat
     assert np.array_equal(np.load(out), raw_train.cpu().numpy())
 
 
+def test_forward_rays_stays_on_the_regular_stream(dev):
+    """AppendVerticesNet.forward_rays (6 rays of 8 samples, the default net) does not run on the composed inference stream, though
+    the library has one for its descriptor: its no-grad output in eval() equals that in train() bit for bit - where forward_fused of
+    a RenderRayNet differs between the two (the test above).  Moving it to that stream is a change of its bits, to be made on
+    purpose."""
+    from smpl_nerf_amd import _lib
+    from smpl_nerf_amd.nets import AppendVerticesNet
+    torch.manual_seed(11)
+    net = AppendVerticesNet().to(dev)
+    assert _lib.load().snerf_mlp_packed_infer_floats(net.desc_for_rows()) > 0
+    rng = np.random.default_rng(12)
+    rows = torch.from_numpy(rng.uniform(-1, 1, (6, 60)).astype(F32)).to(dev)
+    d = torch.from_numpy(rng.normal(size=(6, 3)).astype(F32)).to(dev)
+    with torch.no_grad():
+        in_eval = net.eval().forward_rays(rows, d, 8, 48)
+        in_train = net.train().forward_rays(rows, d, 8, 48)
+    assert bool(torch.isfinite(in_eval).all()) and bool((in_eval != 0).any())
+    assert torch.equal(in_eval, in_train)
+
+
 # ------------------------------------------------------------------------------------------------ the render entries
 def _render_rays_spied(pipe, batch, entry, precision_arg):
     """pipe.render_rays(batch) under no_grad, and the precision codes it passed to `entry` of the library."""
