@@ -464,6 +464,36 @@ SNERF_API int snerf_vertex_warp_bwd_f32(const float *samples, const float *goal,
                               int64_t B, int S, int V, float radius, float temperature, float *d_samples, float *d_goal,
                               float *d_canon, snerf_stream_t stream);
 
+/* ---- The image-wise model: linear-attention warp with ONE body per image (solver/image_wise_solver.py:89-105) ----------------
+ * samples [B,S,3] (N = B S, flat), goal / canon [V,3] (the one body of the image, shared by every ray), ray_o [B,3] ->
+ *   x_sv = max(radius - |sample_s - goal_v|, 0)      D_s = sum_v x_sv + eps      warp_s = (sum_v x_sv (canon_v - goal_v)) / D_s
+ * warp [N,3], warped [N,3] = sample + warp, sdirs [N,3] = warped - ray_o[s / S]: the trio of snerf_vertex_warp_fwd_f32.
+ * No softmax, no temperature; nothing of size N V or B V exists.  fp32 in and out; the pairs inside the radius are evaluated in
+ * float64 (radius and eps are doubles for that reason) and warp is rounded once; warped and sdirs are the fp32 sums of the
+ * rounded warp.  stats [N,4] float64 = (D_s, warp_s unrounded) is what the backward reads; NULL when no backward follows.
+ * A sample with nothing in its radius has warp = 0 / eps = 0 (with eps = 0 it is the reference's 0 / 0).
+ * Any B >= 0 (0: no-op), S >= 1, V >= 1; radius > 0, eps >= 0 (else SNERF_E_BADARG; a bad scalar is an error whatever B is);
+ * stats 8-byte aligned (SNERF_E_ALIGN).  Two calls on the same inputs give the same bits. */
+SNERF_API int snerf_image_warp_fwd_f32(const float *samples, const float *goal, const float *canon, const float *ray_o,
+                              int64_t B, int S, int V, double radius, double eps, float *warp, float *warped, float *sdirs,
+                              double *stats, snerf_stream_t stream);
+/* Bytes of the backward's workspace for N = B S samples and V vertices: the per-slab partial sums [slabs, V, 6] in float64.  The
+ * slab count is a function of N alone (at most 64 slabs of at least 8 chunks of 64 samples), never of the device.  -1 on a bad
+ * argument. */
+SNERF_API int64_t snerf_image_warp_bwd_workspace_bytes(int64_t N, int V);
+/* Its backward: stats from the forward (eps travels in it); d_warp / d_warped / d_sdirs [N,3] are the gradients arriving at the
+ * three outputs (each nullable, not all: their sum is d loss / d warp) -> d_goal, d_canon [V,3], summed over all N samples, and,
+ * unless NULL, d_samples [N,3] = d loss / d samples: what flows through the attention plus d_warped + d_sdirs, the identity
+ * paths of the two derived outputs.  Every element is written (zeros where nothing is in radius) and every workspace word that is
+ * read was written by the same call; no atomics, slabs added in slab order, each output rounded to fp32 once: the same bits on
+ * every call and every device.  A workspace that is NULL or smaller than snerf_image_warp_bwd_workspace_bytes(B S, V) is
+ * SNERF_E_BADARG; stats and workspace 8-byte aligned (SNERF_E_ALIGN).
+ * torch's conventions: relu' (0) = 0, no gradient through a zero distance. */
+SNERF_API int snerf_image_warp_bwd_f32(const float *samples, const float *goal, const float *canon, const double *stats,
+                              const float *d_warp, const float *d_warped, const float *d_sdirs, int64_t B, int S, int V,
+                              double radius, void *workspace, int64_t workspace_bytes, float *d_samples, float *d_goal,
+                              float *d_canon, snerf_stream_t stream);
+
 /* ---- SmplNerfSolver's canonical-density loss: pdf of a Gaussian mixture (utils.py:72-111, solver/smpl_nerf_solver.py:39-41) ----
  * samples [n,3] (any leading shape, flattened), means [V,3] (one isotropic Gaussian of standard deviation std per canonical body
  * vertex, equal weights) ->

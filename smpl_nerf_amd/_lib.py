@@ -153,6 +153,10 @@ SIGNATURES = {
     # DynamicPipeline's vertex-attention warp (csrc/vertex_warp.hip)
     "snerf_vertex_warp_fwd_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P]),
     "snerf_vertex_warp_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
+    # the image-wise model's linear-attention warp, one body per image (csrc/image_warp.hip)
+    "snerf_image_warp_fwd_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_double, c_double, _P, _P, _P, _P, _P]),
+    "snerf_image_warp_bwd_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "snerf_image_warp_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_double, _P, c_int64, _P, _P, _P, _P]),
     # the canonical-density loss of SmplNerfSolver: Gaussian-mixture pdf and its sample gradient (csrc/gmm_pdf.hip)
     "snerf_gmm_pdf_f32": (c_int, [_P, _P, c_int64, c_int, c_float, _P, _P, _P]),
     # the SMPL body model: linear blend skinning (csrc/smpl_lbs.hip)

@@ -1,8 +1,8 @@
-// The skeleton of the brute-force "pair walk" kernels (vertex_warp.hip, vertex_sphere.hip, gmm_pdf.hip, ray_mesh.hip): every lane
+// The skeleton of the brute-force "pair walk" kernels (vertex_warp.hip, image_warp.hip, vertex_sphere.hip, gmm_pdf.hip, ray_mesh.hip): every lane
 // holds one sample or ray, a workgroup is one 64-lane chunk of them, and its waves split the other axis - the items: vertices,
 // means, faces - into consecutive slices which each wave reads at wave-uniform addresses (the compiler reads them through the scalar
 // cache: one load per wave, not per lane).  The per-wave partials meet in LDS as part[WAVES][Q][64] and wave 0 combines them in wave
-// order; how they combine is each kernel's own business.  Here: what at least two of the four files share.  (gmm_pdf.hip and
+// order; how they combine is each kernel's own business.  Here: what at least two of the five files share.  (gmm_pdf.hip and
 // vertex_sphere.hip write the loop of walk4 out themselves: their kernels measured slower with their bodies in functors.)
 #pragma once
 #include "snerf_common.h"
@@ -62,9 +62,37 @@ __device__ __forceinline__ void walk4(const float *base, int v0, int v1, Quad &&
     }
 }
 
+// f(v, gx, gy, gz, dx, dy, dz, d2) for the vertices [v0, v1) of g that can matter to the sample (px, py, pz) of a lane (vertex_warp.hip,
+// image_warp.hip): walk4 hands them over four at a time, the four squared distances share ONE test against r2, and f - which decides
+// per vertex - runs for all four when any is below it (WAVE_UNIFORM: when any lane's is) and for each of the last 0 .. 3 vertices.
+template <bool WAVE_UNIFORM, class F>
+__device__ __forceinline__ void radius_walk(const float *g, int v0, int v1, float px, float py, float pz, float r2, F &&f) {
+    walk4<3>(
+        g, v0, v1,
+        [&](int v, const float *t) {
+            float dx[4], dy[4], dz[4], d2[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                dx[j] = px - t[3 * j];
+                dy[j] = py - t[3 * j + 1];
+                dz[j] = pz - t[3 * j + 2];
+                d2[j] = dist2(dx[j], dy[j], dz[j]);
+            }
+            const bool any = fminf(fminf(d2[0], d2[1]), fminf(d2[2], d2[3])) < r2;
+            if (WAVE_UNIFORM ? __builtin_amdgcn_ballot_w64(any) != 0 : any) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) f(v + j, t[3 * j], t[3 * j + 1], t[3 * j + 2], dx[j], dy[j], dz[j], d2[j]);
+            }
+        },
+        [&](int v, const float *t) {
+            const float dx = px - t[0], dy = py - t[1], dz = pz - t[2];
+            f(v, t[0], t[1], t[2], dx, dy, dz, dist2(dx, dy, dz));
+        });
+}
+
 // a lane's partials x... into rows 0, 1, ... of its wave's part[wave]
-template <int Q, class... T>
-__device__ __forceinline__ void put_partials(float (&part)[Q][WAVE], int lane, T... x) {
+template <int Q, class E, class... T>
+__device__ __forceinline__ void put_partials(E (&part)[Q][WAVE], int lane, T... x) {
     static_assert(sizeof...(T) <= Q, "more partials than rows");
     int q = 0;
     ((part[q++][lane] = x), ...);

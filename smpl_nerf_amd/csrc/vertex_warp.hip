@@ -36,34 +36,6 @@ struct VwBwdArgs {
     float radius, temperature, r2_test;
 };
 
-// f(v, gx, gy, gz, dx, dy, dz, d2) for the vertices [v0, v1) of g that can matter to the sample (px, py, pz): walk4 hands them over
-// four at a time, the four squared distances share ONE test against r2, and f - which decides per vertex - runs for all four when
-// any is below it (WAVE_UNIFORM: when any lane's is) and for each of the last 0 .. 3 vertices.
-template <bool WAVE_UNIFORM, class F>
-__device__ __forceinline__ void vw_walk(const float *g, int v0, int v1, float px, float py, float pz, float r2, F &&f) {
-    walk4<3>(
-        g, v0, v1,
-        [&](int v, const float *t) {
-            float dx[4], dy[4], dz[4], d2[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                dx[j] = px - t[3 * j];
-                dy[j] = py - t[3 * j + 1];
-                dz[j] = pz - t[3 * j + 2];
-                d2[j] = dist2(dx[j], dy[j], dz[j]);
-            }
-            const bool any = fminf(fminf(d2[0], d2[1]), fminf(d2[2], d2[3])) < r2;
-            if (WAVE_UNIFORM ? __builtin_amdgcn_ballot_w64(any) != 0 : any) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) f(v + j, t[3 * j], t[3 * j + 1], t[3 * j + 2], dx[j], dy[j], dz[j], d2[j]);
-            }
-        },
-        [&](int v, const float *t) {
-            const float dx = px - t[0], dy = py - t[1], dz = pz - t[2];
-            f(v, t[0], t[1], t[2], dx, dy, dz, dist2(dx, dy, dz));
-        });
-}
-
 __global__ __launch_bounds__(VW_WAVES * 64) void vertex_warp_fwd_kernel(VwArgs A) {
     __shared__ float part[VW_WAVES][6][WAVE];   // m, sum, hits, numerator xyz of every wave's vertex slice
     const int lane = lane_id(), wave = wave_index();
@@ -76,7 +48,7 @@ __global__ __launch_bounds__(VW_WAVES * 64) void vertex_warp_fwd_kernel(VwArgs A
     const float *g = A.goal + ray * A.V * 3, *c = A.canon + ray * A.V * 3;
     const Slice sl = wave_slice(A.V, VW_WAVES, wave);
     float m = 0.f, sum = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f, hits = 0.f;
-    vw_walk<false>(g, sl.lo, sl.hi, px, py, pz, A.r2_test, [&](int v, float gx, float gy, float gz, float, float, float, float d2) {
+    radius_walk<false>(g, sl.lo, sl.hi, px, py, pz, A.r2_test, [&](int v, float gx, float gy, float gz, float, float, float, float d2) {
         if (d2 < A.r2_test) {   // (r2_test is a little above r^2: the exact decision is the one below)
             const float xr = A.radius - sqrtf(d2);
             if (xr > 0.f) {
@@ -176,7 +148,7 @@ __global__ __launch_bounds__(VW_BWD_WAVES * 64) void vertex_warp_bwd_vertices_ke
         const int s = chunk * WAVE + lane;
         const bool valid = s < A.S;
         const VwSample q = vw_load_sample(A, ray * A.S + tail_index(s, A.S, valid));
-        vw_walk<true>(g, 0, nv, q.px, q.py, q.pz, A.r2_test, [&](int vi, float gx, float gy, float gz, float dx, float dy, float dz, float d2) {
+        radius_walk<true>(g, 0, nv, q.px, q.py, q.pz, A.r2_test, [&](int vi, float gx, float gy, float gz, float dx, float dy, float dz, float d2) {
             const bool near = valid && d2 < A.r2_test;
             if (__builtin_amdgcn_ballot_w64(near) == 0) return;   // wave-uniform
             float a = 0.f, k = 0.f;
@@ -226,7 +198,7 @@ __global__ __launch_bounds__(VW_WAVES * 64) void vertex_warp_bwd_samples_kernel(
     const float *g = A.goal + ray * A.V * 3, *c = A.canon + ray * A.V * 3;
     const Slice sl = wave_slice(A.V, VW_WAVES, wave);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    vw_walk<false>(g, sl.lo, sl.hi, q.px, q.py, q.pz, A.r2_test, [&](int v, float gx, float gy, float gz, float dx, float dy, float dz, float d2) {
+    radius_walk<false>(g, sl.lo, sl.hi, q.px, q.py, q.pz, A.r2_test, [&](int v, float gx, float gy, float gz, float dx, float dy, float dz, float d2) {
         if (d2 < A.r2_test) {
             const float d = sqrtf(d2), xr = A.radius - d;
             if (xr > 0.f && d > 0.f) {

@@ -498,6 +498,88 @@ def vertex_attention_warp(ray_samples, goal_vertices, canonical_vertices, ray_tr
 
 
 # ------------------------------------------------------------------------------------------------
+# The image-wise model's linear-attention warp, one body per image (solver/image_wise_solver.py:89-105)
+# ------------------------------------------------------------------------------------------------
+def _image_warp_launch(samples, goal, canon, ray_o, radius, eps, want_stats):
+    B, S, _ = samples.shape
+    V = goal.shape[-2]
+    dev = samples.device
+    warp, warped, sdirs = (torch.empty((B * S, 3), device=dev, dtype=torch.float32) for _ in range(3))
+    stats = torch.empty((B * S, 4), device=dev, dtype=torch.float64) if want_stats else None      # D and the unrounded warp
+    lib = _lib.load()
+    with torch.cuda.device(dev), _lib.timed(f"image_warp_fwd[V={V}]"):
+        check(lib.snerf_image_warp_fwd_f32(ptr(samples), ptr(goal), ptr(canon), ptr(ray_o), B, S, V, radius, eps,
+                                           ptr(warp), ptr(warped), ptr(sdirs), ptr(stats), current_stream()),
+              "snerf_image_warp_fwd_f32")
+    return warp, warped, sdirs, stats
+
+
+class _ImageWarpFn(torch.autograd.Function):
+    """snerf_image_warp_fwd_f32 / snerf_image_warp_bwd_f32 under autograd: _VertexWarpFn with one body for all rays.  The three
+    incoming gradients add up to d loss / d warp; the samples also receive d warped + d sdirs directly (inside the kernel, which
+    rounds their gradient once) and the ray origins -sum_s d sdirs.  The vertex gradients are sums over every sample of the batch,
+    taken on the device in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, samples, goal, canon, ray_o, radius, eps):
+        warp, warped, sdirs, stats = _image_warp_launch(samples, goal, canon, ray_o, radius, eps, True)
+        ctx.save_for_backward(samples, goal, canon, stats)
+        ctx.radius = radius
+        ctx.set_materialize_grads(False)
+        return warp, warped, sdirs
+
+    @staticmethod
+    def backward(ctx, d_warp, d_warped, d_sdirs):
+        if d_warp is None and d_warped is None and d_sdirs is None:
+            return (None,) * 6
+        samples, goal, canon, stats = ctx.saved_tensors
+        B, S, _ = samples.shape
+        V = goal.shape[-2]
+        d_warp, d_warped, d_sdirs = (None if g is None else g.contiguous().float() for g in (d_warp, d_warped, d_sdirs))
+        want_samples, want_o = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        d_samples = torch.empty_like(samples) if want_samples else None
+        d_goal, d_canon = torch.empty_like(goal), torch.empty_like(canon)
+        lib = _lib.load()
+        nbytes = lib.snerf_image_warp_bwd_workspace_bytes(B * S, V)
+        if nbytes < 0:
+            check(-1, "snerf_image_warp_bwd_workspace_bytes")
+        ws = torch.empty((nbytes // 8,), device=samples.device, dtype=torch.float64)
+        with torch.cuda.device(samples.device), _lib.timed(f"image_warp_bwd[V={V}]"):
+            check(lib.snerf_image_warp_bwd_f32(ptr(samples), ptr(goal), ptr(canon), ptr(stats), ptr(d_warp), ptr(d_warped),
+                                               ptr(d_sdirs), B, S, V, ctx.radius, ptr(ws), nbytes, ptr(d_samples), ptr(d_goal),
+                                               ptr(d_canon), current_stream()), "snerf_image_warp_bwd_f32")
+        d_o = -d_sdirs.view(B, S, 3).sum(1) if want_o and d_sdirs is not None else None
+        return d_samples, d_goal, d_canon, d_o, None, None
+
+
+def image_wise_warp(ray_samples, goal_vertices, canonical_vertices, ray_translation, radius, eps=1e-5):
+    """solver/image_wise_solver.py:89-105 in one launch: every sample moves by the attention-weighted sum of canonical - goal over
+    the vertices of the image's ONE body within `radius`, with the linear attention relu(radius - distance) / (its sum over the
+    vertices + eps) - no softmax, no temperature.  ray_samples [B,S,3], goal_vertices / canonical_vertices [V,3] or [1,V,3] (what
+    the body model returns for one pose), ray_translation [B,3] -> (warp, warped, sdirs), each [B*S, 3] like
+    vertex_attention_warp.  Differentiable with respect to both vertex tensors (the gradients are summed over all B*S samples on
+    the device, in a fixed order) and, where they require grad, the samples and the ray origins; with autograd off the call
+    keeps nothing for a backward.  No [B,S,V] and no [B,V,3] tensor is built."""
+    for nm, t in (("ray_samples", ray_samples), ("goal_vertices", goal_vertices), ("canonical_vertices", canonical_vertices),
+                  ("ray_translation", ray_translation)):
+        _need_cuda(nm, t)
+    if ray_samples.dim() != 3 or ray_samples.shape[-1] != 3:
+        raise RuntimeError(f"image_wise_warp: ray_samples must be [B, S, 3], got {tuple(ray_samples.shape)}")
+    B, S = ray_samples.shape[:2]
+    gs = tuple(goal_vertices.shape)
+    if not (len(gs) in (2, 3) and gs[-1] == 3 and (len(gs) == 2 or gs[0] == 1)) or canonical_vertices.shape != goal_vertices.shape \
+            or tuple(ray_translation.shape) != (B, 3):
+        raise RuntimeError(f"image_wise_warp: goal {gs} and canonical {tuple(canonical_vertices.shape)} must be one body, [V, 3] or "
+                           f"[1, V, 3], and ray_translation {tuple(ray_translation.shape)} must match ray_samples [B={B}, S={S}, 3]")
+    if S < 1 or gs[-2] < 1:
+        raise RuntimeError("image_wise_warp: needs at least one sample per ray and one vertex")
+    x, g, c, o = (t.contiguous() for t in (ray_samples, goal_vertices, canonical_vertices, ray_translation))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, g, c, o)):
+        return _ImageWarpFn.apply(x, g, c, o, float(radius), float(eps))
+    return _image_warp_launch(x, g, c, o, float(radius), float(eps), False)[:3]
+
+
+# ------------------------------------------------------------------------------------------------
 # GaussianMixture.pdf (utils.py:72-111): the canonical-density term of SmplNerfSolver's loss
 # ------------------------------------------------------------------------------------------------
 def _gmm_launch(samples, means, std, want_grad):

@@ -422,6 +422,53 @@ class DynamicPipeline(NerfPipeline):
         return self._march(data, stage, coarse_only=True)      # :81, :83
 
 
+class ImageWisePipeline(NerfPipeline):
+    """The forward of solver/image_wise_solver.py:73-116 (--model_type image_wise_dynamic; the reference has no pipeline class for
+    it, its solver carries the forward) with DynamicPipeline's return tuple.  ONE body per image: pose_image() asks the estimator
+    for the image's pose - `smpl_estimator(1)` returns (goal_pose [1, 69], betas) - and poses the body model in the zero pose and
+    in the goal pose, without a global_orient as the reference does (:77-79); the two [1, V, 3] vertex tensors stay with the
+    pipeline and every ray batch of that image is warped with them, autograd graph included: the trainer's
+    backward(retain_graph=True) of every batch flows through the same, by then stale, vertices into the estimator (:121).
+    forward(data), data = [ray_samples, ray_translation, ray_direction, z_vals, rgb_truth]: every sample moves by the
+    linear-attention sum of canonical - goal over the goal vertices within args.warp_radius (ops.image_wise_warp: :89-101 in one
+    launch, no [B, S, V] and no [B, V, 3] tensor), then the coarse net on the warped samples with per-sample view directions and
+    the compositing that scales distances by |x' - o| (:103-116) - coarse only.  z_vals may be [S]: the reference hands ONE row of
+    depths to raw2outputs for the whole batch (datasets/image_wise_dataset.py:154).  Returns (rgb, rgb, warp [B,S,3],
+    ray_samples, warped [B,S,3], densities)."""
+
+    _single_call = None      # (the body comes from torch modules in front of the warp: no single-call entry)
+    warp_eps = 1e-5          # image_wise_solver.py:96
+
+    def __init__(self, model_coarse, model_fine, smpl_estimator, smpl_model, args, position_encoder, direction_encoder):
+        super().__init__(model_coarse, model_fine, args, position_encoder, direction_encoder)
+        self.smpl_estimator = smpl_estimator
+        self.smpl_model = smpl_model
+        self.goal_vertices = self.canonical_vertices = None
+
+    def pose_image(self):
+        """Poses the body for the next image (:73-81) under the caller's grad mode; returns (goal, canonical), each [1, V, 3]."""
+        goal_pose, betas = self.smpl_estimator(1)                                                  # :73
+        canonical = self.smpl_model(betas=betas, return_verts=True, body_pose=torch.zeros_like(goal_pose)).vertices   # :29, :77
+        goal = self.smpl_model(betas=betas, return_verts=True, body_pose=goal_pose).vertices       # :79
+        self.goal_vertices, self.canonical_vertices = goal, canonical
+        return goal, canonical
+
+    def _forward_calls(self, data):
+        ray_samples, ray_translation, _, z_vals, _ = data
+        if self.goal_vertices is None:
+            raise RuntimeError("ImageWisePipeline: pose_image() has to be called once per image before its ray batches")
+        B, S = ray_samples.shape[:2]
+        if z_vals.dim() == 1:
+            z_vals = z_vals[None, :].expand(B, S).contiguous()
+        warp, warped, sdirs = ops.image_wise_warp(ray_samples, self.goal_vertices, self.canonical_vertices, ray_translation,
+                                                  self.args.warp_radius, self.warp_eps)            # :89-105
+
+        def stage(samples, n, fine):      # :103-115
+            return self.model_coarse.forward_fused(warped, sdirs, n, self.position_encoder, self.direction_encoder), sdirs, (warp, warped)
+
+        return self._march([ray_samples, ray_translation, data[2], z_vals], stage, coarse_only=True)      # :116
+
+
 class VertexSpherePipeline(NerfPipeline):
     """models/vertex_sphere_pipeline.py:7-50 drop-in: the deterministic-warp ("true warp") model.  The warp is not learned and
     not computed here: it arrives with the batch, data = [ray_samples, ray_translation, ray_direction, z_vals, warp, rgb_truth]

@@ -1,6 +1,7 @@
 """Stand-ins for the SMPL assets the reference needs but does not ship (SMPL .pkl, smplx): a linear
 "body model" with the call contract AppendVerticesPipeline uses (models/append_vertices_pipeline.py:38-40)
-and the index-based pose estimator (models/dummy_smpl_estimator_model.py:6-27).  Torch modules, device
+and the index-based pose estimator (models/dummy_smpl_estimator_model.py:6-27), and the arm-angle estimator of
+the image-wise model (models/dummy_image_wise_estimator.py).  Torch modules, device
 agnostic; used by the golden generator, the tests and the synthetic benchmarks."""
 from __future__ import annotations
 
@@ -40,6 +41,27 @@ class IndexPoseEstimator(torch.nn.Module):
 
     def forward(self, x):
         return self.goal_poses[x], self.betas.expand(len(x), -1)
+
+
+class ArmAngleEstimator(torch.nn.Module):
+    """The estimator of the image-wise model (models/dummy_image_wise_estimator.py, as train.py:88-95 builds it): ONE pose for the
+    image, fixed but for the two arm angles - entries 38 and 41 of the 69 body-pose parameters -, which are trained through the
+    warp.  forward(x) ignores x and returns (pose [1, 69], betas [1, NB]).  The attribute names the solver's pose loss reads are
+    the reference's: arm_angle_l, arm_angle_r ([1, 1] parameters) and ground_truth_pose [1, 69]."""
+
+    def __init__(self, arm_angle_l: float, arm_angle_r: float, betas=None, ground_truth_pose=None, rest_pose=None):
+        super().__init__()
+        rest = torch.zeros(1, 69) if rest_pose is None else torch.as_tensor(rest_pose, dtype=torch.float32).reshape(1, 69)
+        self.register_buffer("rest_pose", rest.clone())
+        self.arm_angle_l = torch.nn.Parameter(torch.tensor([[float(arm_angle_l)]]))
+        self.arm_angle_r = torch.nn.Parameter(torch.tensor([[float(arm_angle_r)]]))
+        self.betas = torch.nn.Parameter(torch.zeros(1, 10) if betas is None else betas.data.clone().reshape(1, -1), requires_grad=False)
+        gt = torch.zeros(1, 69) if ground_truth_pose is None else torch.as_tensor(ground_truth_pose, dtype=torch.float32).reshape(1, 69)
+        self.ground_truth_pose = torch.nn.Parameter(gt.clone(), requires_grad=False)
+
+    def forward(self, x=None):
+        r = self.rest_pose
+        return torch.cat([r[:, :38], self.arm_angle_l, r[:, 39:41], self.arm_angle_r, r[:, 42:]], dim=-1), self.betas
 
 
 # SMPL's kinematic tree (kintree_table[0] of the published model files, root = -1)

@@ -883,6 +883,120 @@ class SmplNerfTrainer(DataParallelTrainer):
         return loss + term                                                                                       # :41
 
 
+class ImageWiseTrainer(DataParallelTrainer):
+    """ImageWiseSolver.train (solver/image_wise_solver.py:41-139) on the trainer, for pipelines.ImageWisePipeline: per image the
+    body is posed ONCE (pipeline.pose_image(), :73-82), then per ray batch of that image forward, MSE of the coarse colour (:119: one
+    term, not the two of NerfSolver), backward(retain_graph=True) - every batch of the image sends its gradient through the same
+    posed body into the estimator - and a step (:121-122).  Two parameter groups as in :32-36, each on the library's Adam kernel
+    (one HipAdam per group: a group is a learning rate): the coarse net at `lr`, the estimator's trainable parameters (the arm
+    angles) at `lr_pose`.  The pose loss of :125-129 is kept beside the training loss (last_pose_loss, the history of fit()).
+    Single process: the estimator's gradient is not part of the flat buffer the data-parallel all-reduce covers."""
+
+    def __init__(self, pipeline, lr: float = 5e-4, lr_pose: float = 0.1, weight_decay: float = 0.0, loss_func=None, fused=None):
+        super().__init__(pipeline, [pipeline.model_coarse], lr=lr, weight_decay=weight_decay, loss_func=loss_func, fused=fused,
+                         one_call=False)
+        if self.world > 1:
+            raise RuntimeError("ImageWiseTrainer: single process only (the estimator's gradient is not all-reduced)")
+        self.pose_params = [p for p in pipeline.smpl_estimator.parameters() if p.requires_grad]
+        args = dict(self.default_adam_args, lr=lr_pose, weight_decay=weight_decay)
+        if isinstance(self.optim, HipAdam):
+            flat_p, flat_g, _, order = flatten_parameters_([torch.nn.ParameterList(self.pose_params)])
+            views, off = [], 0
+            for p in order:
+                views.append(flat_g[off:off + p.numel()].view(p.shape))
+                off += p.numel()
+            self.pose_optim = HipAdam(order, flat_p, flat_g, views, **args)
+        else:
+            self.pose_optim = torch.optim.Adam(self.pose_params, **args)
+        self.last_pose_loss = None
+
+    def batch_loss(self, out, batch):
+        return self.loss_func(out[0], batch[-1])                                                   # :119
+
+    def pose_loss(self):
+        """(arm_angle_l - truth[38])^2 + (arm_angle_r - truth[41])^2 of the estimator (:125-129), a 0-d tensor."""
+        est = self.pipeline.smpl_estimator
+        with torch.no_grad():
+            gt = est.ground_truth_pose
+            return (est.arm_angle_l.reshape(-1)[0] - gt[0, 38]) ** 2 + (est.arm_angle_r.reshape(-1)[0] - gt[0, 41]) ** 2
+
+    def step(self, batch):
+        """One ray batch of the image pose_image() was last called for (:84-129).  Returns the loss tensor."""
+        self.optim.zero_grad(set_to_none=True)
+        self.pose_optim.zero_grad(set_to_none=True)
+        self._arm_grad_sinks()
+        out = self.pipeline(batch)
+        loss = self.batch_loss(out, batch)
+        loss.backward(retain_graph=True)                                                           # :121
+        self.last_outputs = (out[0].detach(), out[1].detach())
+        self.optim.step()
+        self.pose_optim.step()
+        for m in self.models:
+            if hasattr(m, "mark_weights_changed"):
+                m.mark_weights_changed()
+        self.last_pose_loss = self.pose_loss()
+        return loss.detach()
+
+    @staticmethod
+    def ray_batches(image, batch_size: int, generator=None):
+        """The ray batches of one image = [ray_samples [R,S,3], ray_translation [R,3], ray_direction [R,3], z_vals [S] or [R,S],
+        rgb [R,3]] (image_wise.ImageWiseRays.image()): `batch_size` rays each, the last one short, shuffled with `generator` (the
+        reference's DataLoader(shuffle=True) over SubDataset, :69-70) or in ray order without one.  A z_vals row [S] goes to every
+        batch whole."""
+        samples, ray_o, ray_d, z, rgb = image
+        R = samples.shape[0]
+        order = torch.arange(R, device=samples.device) if generator is None else torch.randperm(R, device=samples.device, generator=generator)
+        for r0 in range(0, R, batch_size):
+            idx = order[r0:r0 + batch_size]
+            yield [samples[idx], ray_o[idx], ray_d[idx], z if z.dim() == 1 else z[idx], rgb[idx]]
+
+    def train_image(self, image, batch_size: int, generator=None):
+        """pose_image() once, then a step per ray batch (:73-129).  Returns (losses, pose losses), one 0-d tensor per batch each."""
+        self.pipeline.pose_image()
+        losses, pose = [], []
+        for batch in self.ray_batches(image, batch_size, generator):
+            losses.append(self.step(batch))
+            pose.append(self.last_pose_loss)
+        return losses, pose
+
+    @torch.no_grad()
+    def validate_image(self, image, batch_size: int):
+        """The validation pass of :150-208 for one image under no_grad, through the same pipeline: (mean loss, rgb [R,3] in ray order)."""
+        self.pipeline.pose_image()
+        losses, renders = [], []
+        for batch in self.ray_batches(image, batch_size):
+            out = self.pipeline(batch)
+            losses.append(self.batch_loss(out, batch))
+            renders.append(out[0])
+        return float(torch.stack(losses).mean()), torch.cat(renders)
+
+    def fit(self, train_images, val_images=(), num_epochs: int = 1, batch_size: int = 4096, seed: int = 0, log=print):
+        """ImageWiseSolver.train: per epoch every image of `train_images` (an iterable of image lists, re-iterated per epoch - an
+        image_wise.ImageWiseRays re-samples with the estimator's current pose) through train_image(), then the validation images.
+        Returns the history: per epoch the mean training loss, the mean pose loss and the mean validation loss."""
+        dev = self.params[0].device
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        hist = {"train_loss": [], "pose_loss": [], "val_loss": []}
+        for epoch in range(num_epochs):
+            self.pipeline.model_coarse.train()
+            self.pipeline.smpl_estimator.train()
+            losses, pose = [], []
+            for image in train_images:
+                a, b = self.train_image([e.to(dev) for e in image], batch_size, gen)
+                losses += a
+                pose += b
+            self.pipeline.model_coarse.eval()
+            self.pipeline.smpl_estimator.eval()
+            val = [self.validate_image([e.to(dev) for e in image], batch_size)[0] for image in val_images]
+            hist["train_loss"].append(float(torch.stack(losses).mean()) if losses else 0.0)
+            hist["pose_loss"].append(float(torch.stack(pose).mean()) if pose else 0.0)
+            hist["val_loss"].append(sum(val) / (len(val) or 1))
+            log("[Epoch %d] Average loss of Epoch: %.7f Pose Loss: %.7f | VAL loss: %.7f" %
+                (epoch + 1, hist["train_loss"][-1], hist["pose_loss"][-1], hist["val_loss"][-1]))
+        return hist
+
+
 class RayBatchLoader:
     """The shuffled DataLoader over RaysFromImagesDataset (train.py:96-100) with the rays generated on the device
     (raygen.RayGenerator).  Data-parallel runs shard the data set BY IMAGE (1200 images -> 150 per GPU): build
