@@ -157,6 +157,8 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     const int enc_pos_off = A.add_first ? A.add_dim : 0, enc_add_off = A.add_first ? 0 : A.pos_dim;
     const int enc_dir_off = A.enc_stride - A.dir_dim;  // directions = x[..., -dir_dim:] (:43)
     const bool composed = !TRAIN && A.composed != 0;
+    // the 8-wave inference kernels of width 256 (two waves per SIMD, 55 VGPRs to spare) prefetch two A pairs ahead: kblock_deep()
+    constexpr bool DEEP = WIDTH == 256 && NWAVES == 8 && !TRAIN;
 
     // Persistent workgroups: one per CU (the 99 / 132 KiB ring allows no more), each walking the sample tiles blockIdx.x,
     // blockIdx.x + gridDim.x, ...  The weight ring keeps rolling from one tile into the next (the stream wraps around),
@@ -216,7 +218,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     f4 in[T], acc[T];
 
     // extra input segments [PE(x) | add] of layer 0 and of the skip layers
-    auto pe_segment = [&](LayerRun<T, NT, Pipe> &run, bool first) {
+    auto pe_segment = [&](LayerRun<T, NT, Pipe, DEEP> &run, bool first) {
         for (int kb = 0; kb < A.pos_nkb; ++kb) {
             const f4 b = pe_operand<ENCODED>(c, false, A.pos_L, A.pos_id, kb, enc_pos_off);
             if (TRAIN && first && valid) store_tile(A.act, A.act_pe + kb, A.n, sample, c.g, b);
@@ -224,7 +226,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
         }
     };
     int fold_slot = 0;
-    auto add_segment = [&](LayerRun<T, NT, Pipe> &run, bool first) {
+    auto add_segment = [&](LayerRun<T, NT, Pipe, DEEP> &run, bool first) {
         if (FOLD) {
             for (int kb = 0; kb < A.add_nkb; ++kb) run.skip();
             const f4 *row = reinterpret_cast<const f4 *>(A.fold + ((sc / A.spr) * A.fold_slots + fold_slot) * WIDTH) + c.g;
@@ -252,14 +254,14 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
         }
     };
     // extra input segments of layer 0 and of the skip layers, in the column order of the weight matrix
-    auto pos_segments = [&](LayerRun<T, NT, Pipe> &run, bool first) {
+    auto pos_segments = [&](LayerRun<T, NT, Pipe, DEEP> &run, bool first) {
         if (A.add_first) add_segment(run, first);
         pe_segment(run, first);
         if (!A.add_first) add_segment(run, first);
     };
 
     {  // positions_pose_input + relu (models/render_ray_net.py:45)
-        LayerRun<T, NT, Pipe> run(pipe, lane);
+        LayerRun<T, NT, Pipe, DEEP> run(pipe, lane);
         run.init(acc);
         pos_segments(run, true);
         run.finish();
@@ -270,7 +272,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
         }
     }
     for (int i = 0; i < A.n_hidden; ++i) {  // positional_net[i] + relu (:46-50)
-        LayerRun<T, NT, Pipe> run(pipe, lane);
+        LayerRun<T, NT, Pipe, DEEP> run(pipe, lane);
         run.init(acc);
 #pragma unroll
         for (int kb = 0; kb < T; ++kb) run.step(in[kb], acc);
@@ -285,7 +287,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     // Inference on the composed stream (mlp_plan.h: make_plan_infer; uniform over the launch): additional_linear_layer and
     // directional_net[0] are not in the stream - sigma' and dir-net' (with the ReLU of directional_net[0]) read the trunk's output
     if (!composed) {  // additional_linear_layer, no activation (:51)
-        LayerRun<T, NT, Pipe> run(pipe, lane);
+        LayerRun<T, NT, Pipe, DEEP> run(pipe, lane);
         run.init(acc);
 #pragma unroll
         for (int kb = 0; kb < T; ++kb) run.step(in[kb], acc);
@@ -303,7 +305,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
     }
     f4 ind[TD], accd[TD];
     {  // directional_input, no activation (:54-57)
-        LayerRun<TD, NT, Pipe> run(pipe, lane);
+        LayerRun<TD, NT, Pipe, DEEP> run(pipe, lane);
         run.init(accd);
 #pragma unroll
         for (int kb = 0; kb < T; ++kb) run.step(in[kb], accd);
@@ -320,7 +322,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs &A) {
         if (PREFETCH) load_raw(tile + gridDim.x < A.n_tiles ? tile + gridDim.x : tile);
     }
     if (!composed) {  // directional_net[0] + relu (:58-59)
-        LayerRun<TD, NT, Pipe> run(pipe, lane);
+        LayerRun<TD, NT, Pipe, DEEP> run(pipe, lane);
         run.init(accd);
 #pragma unroll
         for (int kb = 0; kb < TD; ++kb) run.step(ind[kb], accd);

@@ -536,6 +536,10 @@ __device__ __forceinline__ f4 add_operand(const SampleCtx &c, int add_dim, int k
 // next slab) is read during the last pair - so a wave never waits on an LDS read between MFMAs.  Tiles are
 // walked in pairs so that consecutive MFMAs never share an accumulator (dependent latency of 16x16x4 is 40
 // cycles vs 32 issue).  (pa0, pa1) carry the prefetched first pair from k-block to k-block.
+// The hazard of this placement: the read at the top of a pair may be given the accumulator quad that the previous pair's last
+// MFMA still reads as SrcC (hipcc renames the result into dead A registers), and then stands behind 7 - 8 wait states of `s_nop`
+// that no MFMA covers.  The 8-wave inference kernels of width 256, where that cost 1.6 % of the frame, go through kblock_deep()
+// below, which avoids it (tests/test_mfma_gap_isa.py holds them to it); every other kernel keeps this form, unchanged.
 // mid(): called once between two tile pairs early in the block (LayerRun: the staging of the slab after next, so that its LDS
 // writes and global loads issue between MFMAs instead of behind the slab's last one)
 struct NoMid {
@@ -590,20 +594,91 @@ __device__ __forceinline__ void kblock(const float *a_kb, const float *a_next, f
     }
 }
 
+// kblock() with the prefetch TWO tile pairs ahead and pinned behind the pair's 2nd MFMA (T_OUT >= 8; the 8-wave inference kernels
+// of width 256: LayerRun<.., DEEP>).  Why: hipcc lets the last MFMA of an accumulation chain - and many a pair's last MFMA in the
+// middle of one - write its result into the A-operand registers that just died and hands the old accumulator quad to the next
+// ds_read_b128.  With the reads at the top of the next pair (kblock()) that read stands right behind the MFMA that still reads
+// those registers as SrcC, and the hazard recognizer separates the two with `s_nop 6` / `s_nop 7`: 28 - 32 clocks that no MFMA
+// covers, in 1 gap of 20.  Two MFMAs further on the quad has been read and the `s_nop` is gone or short enough (<= 6 wait
+// states = 24 clocks + the MFMA's own 8) to fit beside the MFMA in front of it.  Reading one pair ahead from there would make every
+// wait a full `lgkmcnt(0)` (nothing younger in flight at the top of a pair); two pairs ahead, a third A pair (8 VGPRs), the wait
+// at the top of pair p+1 leaves the reads of pair p+2 in flight (`lgkmcnt(2)`) and every read has 14 MFMAs to land.
+// (pa0, pa1) = the next pair as in kblock(); (pb0, pb1) = the pair behind it (LayerRun primes it per layer).  The MFMA order of
+// every accumulator is kblock()'s.  tests/test_mfma_gap_isa.py holds the compiled kernels to this; tests/test_weight_ring_isa.py
+// to the counted waits.
+template <int T_OUT, class Mid = NoMid>
+__device__ __forceinline__ void kblock_deep(const float *a_kb, const float *a_next, f4 b, f4 (&acc)[T_OUT], f4 &pa0, f4 &pa1,
+                                            f4 &pb0, f4 &pb1, int lane, Mid mid = Mid{}) {
+    static_assert(T_OUT >= 8 && T_OUT % 2 == 0, "two pairs ahead stay inside this k-block and the next one");
+    const f4 *ap = reinterpret_cast<const f4 *>(a_kb) + lane;
+    const f4 *np = reinterpret_cast<const f4 *>(a_next) + lane;
+    f4 a0 = pa0, a1 = pa1, b0 = pb0, b1 = pb1;
+#pragma unroll
+    for (int to = 0; to < T_OUT; to += 2) {
+        f4 n0, n1;
+        if (to + 4 < T_OUT) {
+            n0 = ap[(to + 4) * 64];
+            n1 = ap[(to + 5) * 64];
+        } else {   // the first two pairs of the next k-block (`a_next`: possibly in the next slab, or the next layer's first)
+            n0 = np[(to + 4 - T_OUT) * 64];
+            n1 = np[(to + 5 - T_OUT) * 64];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            acc[to] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[r], b[r], acc[to], 0, 0, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            acc[to + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[r], b[r], acc[to + 1], 0, 0, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            if (r == 0) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // the 2 DS reads of pair to/2 + 2, behind the 2nd MFMA
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (to == 2) {
+            mid();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        a0 = b0;
+        a1 = b1;
+        b0 = n0;
+        b1 = n1;
+    }
+    pa0 = a0;
+    pa1 = a1;
+    pb0 = b0;
+    pb1 = b1;
+}
+
 // Walks the k-blocks of one layer through the slab pipe (either one: PIPE).  A slab is released (the next slab staged - SlabPipe: the
 // registers written to LDS and the next global loads issued; SlabPipeDma: the DMA pieces of slab p+3 issued -, workgroup barrier)
 // as soon as its last k-block has been issued; the first A pair of the following slab was read before that barrier - legal
 // because slab p+1 has been resident and visible since the barrier that ended slab p-1 (the 3-slot ring holds p, p+1 and the slot
 // being filled with p+2; the 4-slot ring p, p+1, p+2 landing and the slot of p+3).
-template <int T_OUT, int NT, class PIPE>
-struct LayerRun {
+// DEEP (T_OUT >= 8): the k-blocks go through kblock_deep(); the second prefetched pair lives here, per layer - primed from the
+// layer's first k-block (resident: the layer starts in `slab`), dropped at the layer's end (the last pair's read of the block
+// behind the layer stays inside that slab's A region: tiles 2 and 3).
+template <bool DEEP>
+struct DeepPair {};
+template <>
+struct DeepPair<true> {
+    f4 pb0, pb1;   // the A-operand pair behind (pipe.pa0, pipe.pa1)
+};
+template <int T_OUT, int NT, class PIPE, bool DEEP = false>
+struct LayerRun : DeepPair<DEEP> {
     static constexpr int KPS = SLAB_TILES / T_OUT;
+    static_assert(!DEEP || T_OUT >= 8, "kblock_deep");
     PIPE &pipe;
     const float *slab;
     int kbl;  // k-block index inside the current slab
     int lane;
 
-    __device__ __forceinline__ LayerRun(PIPE &p, int lane_) : pipe(p), slab(p.acquire()), kbl(0), lane(lane_) {}
+    __device__ __forceinline__ LayerRun(PIPE &p, int lane_) : pipe(p), slab(p.acquire()), kbl(0), lane(lane_) {
+        if constexpr (DEEP) prime(slab);
+    }
+    // DEEP: (pb0, pb1) = tiles 2 and 3 of the k-block at `kb` - whose tiles 0 and 1 are in (pipe.pa0, pipe.pa1)
+    __device__ __forceinline__ void prime(const float *kb) {
+        const f4 *p = reinterpret_cast<const f4 *>(kb) + lane;
+        this->pb0 = p[2 * 64];
+        this->pb1 = p[3 * 64];
+    }
     // bias -> accumulator init (aux block of the layer's first slab: bias[16*to + 4*g + r])
     __device__ __forceinline__ void init(f4 (&acc)[T_OUT]) {
         const f4 *aux = reinterpret_cast<const f4 *>(slab + SLAB_A_FLOATS) + (lane >> 4);
@@ -620,9 +695,11 @@ struct LayerRun {
         const float *nxt = (kbl + 1 < KPS) ? cur + T_OUT * 256 : pipe.peek_next();
         if constexpr (T_OUT >= 8) {
             const bool last = kbl + 1 == KPS;     // the slab's last k-block carries the staging between its MFMAs
-            kblock<T_OUT>(cur, nxt, b, acc, pipe.pa0, pipe.pa1, lane, [&]() __attribute__((always_inline)) {
+            auto mid = [&]() __attribute__((always_inline)) {
                 if (last) pipe.stage();
-            });
+            };
+            if constexpr (DEEP) kblock_deep<T_OUT>(cur, nxt, b, acc, pipe.pa0, pipe.pa1, this->pb0, this->pb1, lane, mid);
+            else kblock<T_OUT>(cur, nxt, b, acc, pipe.pa0, pipe.pa1, lane, mid);
             if (++kbl == KPS) {
                 pipe.advance();
                 slab = pipe.acquire();
@@ -644,6 +721,10 @@ struct LayerRun {
         const f4 *np = reinterpret_cast<const f4 *>((kbl + 1 < KPS) ? cur + T_OUT * 256 : pipe.peek_next()) + lane;
         pipe.pa0 = np[0];
         pipe.pa1 = np[64];
+        if constexpr (DEEP) {
+            this->pb0 = np[2 * 64];
+            this->pb1 = np[3 * 64];
+        }
         if (++kbl == KPS) {
             pipe.release();
             slab = pipe.acquire();
