@@ -17,7 +17,11 @@ parameter gradient, every input-row gradient - and a pre-activation of exactly 0
     conditions that keep an exact comparison from passing vacuously;
   * assert_exact(): the comparison, naming tensor, first mismatching index, its 16 x 16 tile, got / want;
   * the cases of tests/test_gpu_mlp_exact.py, so that tests/test_exact_net_host.py checks on the CPU what the GPU tests take for
-    granted.  `python tests/exact_net_ref.py` rewrites profiles/mlp_exact_cases.txt.
+    granted.  `python tests/exact_net_ref.py` rewrites profiles/mlp_exact_cases.txt;
+  * the inference cases of tests/test_gpu_mlp_infer_exact.py (second half of this file): the same networks through the no-grad
+    entries - infer_data() / infer_reference() / infer_preconditions(), the composed maps of the inference stream restated
+    (composed_maps()), big_rows() for large calls, the launch rule of the latency kernels (launch_form()) and the operand split of the
+    split-precision kernels (split_parts()) restated; their record is profiles/mlp_infer_exact_cases.txt.
 """
 import functools
 import os
@@ -38,8 +42,9 @@ INT_LIMIT = 2 ** 24           # integers below it are exact in fp32
 
 
 # ------------------------------------------------------------------------------------------------ the generator
-def _sparse_rows(rng, n_out, n_in, r, p_plus):
-    """[n_out, n_in] fp32: k = max(r, ceil(n_in / n_out)) entries of +-1 per row (+1 with probability p_plus), no empty column"""
+def _sparse_rows(rng, n_out, n_in, r, p_plus, fill_tiles=0):
+    """[n_out, n_in] fp32: k = max(r, ceil(n_in / n_out)) entries of +-1 per row (+1 with probability p_plus), no empty column;
+    fill_tiles: no origin-aligned 16 x 16 tile without an entry either (_fill_tiles)"""
     k = min(n_in, max(r, -(-n_in // n_out)))
     cols = np.stack([rng.choice(n_in, k, replace=False) for _ in range(n_out)])
     count = np.bincount(cols.ravel(), minlength=n_in)
@@ -49,10 +54,49 @@ def _sparse_rows(rng, n_out, n_in, r, p_plus):
         count[cols[i, j]] -= 1
         cols[i, j] = c
         count[c] = 1
+    extra = _fill_tiles(rng, cols, n_in) if fill_tiles else []
     w = np.zeros((n_out, n_in), F32)
-    w[np.arange(n_out)[:, None], cols] = np.where(rng.random((n_out, k)) < p_plus, 1.0, -1.0)
-    assert ((w != 0).sum(1) == k).all() and (w != 0).any(0).all()
+    signs = np.where(rng.random((n_out, k)) < p_plus, 1.0, -1.0)
+    if fill_tiles and k > 1:
+        # as many +1 as -1 in every row (one more of either where k is odd), whatever p_plus: the outputs of a ReLU layer share a positive
+        # mean, and a row that does not cancel it is active on nearly every sample (one sign only: on every sample or on none)
+        plus = k // 2 + (rng.random(n_out) < 0.5) * (k % 2)
+        signs = np.where(rng.permuted(np.tile(np.arange(k), (n_out, 1)), axis=1) < plus[:, None], 1.0, -1.0)
+    w[np.arange(n_out)[:, None], cols] = signs
+    for i, c in extra:
+        w[i, c] = 1.0 if rng.random() < p_plus else -1.0
+    assert ((w != 0).sum(1) == k + np.bincount([i for i, _ in extra], minlength=n_out)).all() and (w != 0).any(0).all()
     return w
+
+
+def _fill_tiles(rng, cols, n_in):
+    """cols [n_out, k] (column indices, distinct per row), in place: every origin-aligned 16 x 16 tile of the [n_out, n_in] matrix
+    gets an entry - into an empty tile moves an entry of one of its rows that sits in a tile with a second entry and in a column
+    with a second entry (so no tile and no column is emptied), to a column of the empty tile drawn at random.  Where a tile-row has
+    no such entry (the last two rows of a 50-row matrix: 8 entries for 8 tiles) the tile gets an entry MORE: returns those (row, column)"""
+    extra = []
+    n_out, tc = cols.shape[0], -(-n_in // 16)
+    tiles = np.zeros((-(-n_out // 16), tc), np.int64)
+    np.add.at(tiles, (np.arange(n_out)[:, None] // 16, cols // 16), 1)
+    count = np.bincount(cols.ravel(), minlength=n_in)
+    for ti, tj in np.argwhere(tiles == 0):
+        rows = np.arange(16 * ti, min(n_out, 16 * ti + 16))
+        spare = np.argwhere((tiles[ti][cols[rows] // 16] > 1) & (count[cols[rows]] > 1))
+        c = int(rng.integers(16 * tj, min(n_in, 16 * tj + 16)))          # (no entry of the tile-row is in this tile: it is empty)
+        if not len(spare):
+            extra.append((int(rows[rng.integers(len(rows))]), c))
+            tiles[ti, tj] += 1
+            count[c] += 1
+            continue
+        i, j = spare[rng.integers(len(spare))]
+        i = rows[i]
+        tiles[ti, cols[i, j] // 16] -= 1
+        count[cols[i, j]] -= 1
+        cols[i, j] = c
+        tiles[ti, tj] += 1
+        count[c] += 1
+    assert (tiles > 0).all() and (count > 0).all()
+    return extra
 
 
 def _dense_rows(rng, n_out, n_in, p_plus):
@@ -71,7 +115,7 @@ def render_net_shapes(n_layers, width, positions_dim, directions_dim, additional
 
 
 NetCase = namedtuple("NetCase", "name n_layers width positions_dim directions_dim additional_input_dim skips use_directional_input "
-                                "n r p_plus seed")
+                                "n r p_plus seed fill_tiles", defaults=(0,))
 WarpCase = namedtuple("WarpCase", "name width row_len n spr r p_plus seed")
 
 
@@ -81,10 +125,11 @@ def net_kw(case):
                 use_directional_input=case.use_directional_input)
 
 
-def _state(rng, shapes, r, p_plus):
+def _state(rng, shapes, r, p_plus, fill_tiles=0):
     state = {}
     for name, n_out, n_in in shapes:
-        state[name + ".weight"] = _dense_rows(rng, n_out, n_in, p_plus) if n_out <= 3 else _sparse_rows(rng, n_out, n_in, r, p_plus)
+        state[name + ".weight"] = _dense_rows(rng, n_out, n_in, p_plus) if n_out <= 3 else \
+            _sparse_rows(rng, n_out, n_in, r, p_plus, fill_tiles)
         state[name + ".bias"] = rng.integers(0, 3, n_out).astype(F32)
     return state
 
@@ -92,9 +137,11 @@ def _state(rng, shapes, r, p_plus):
 def render_net_data(case):
     """(state dict, encoded rows [n, positions + additional + directions], d_raw [n, 4]) as fp32 arrays of integers"""
     rng = np.random.default_rng([case.seed, case.width, case.n_layers, case.n])
-    state = _state(rng, render_net_shapes(*case[1:8]), case.r, case.p_plus)
+    state = _state(rng, render_net_shapes(*case[1:8]), case.r, case.p_plus, case.fill_tiles)
     rows = rng.integers(-2, 3, (case.n, case.positions_dim + case.additional_input_dim + case.directions_dim)).astype(F32)
     d_raw = rng.integers(-2, 3, (case.n, 4)).astype(F32)
+    if case.fill_tiles:
+        _make_two_sided(case, state, rows, rng)
     return state, rows, d_raw
 
 
@@ -244,6 +291,27 @@ def reference(case):
     return render_net_reference(case) if isinstance(case, NetCase) else warp_net_reference(case)
 
 
+def _make_two_sided(case, state, rows, rng):
+    """The inference cases, n >= 77: a hidden feature of a ReLU layer that the float64 forward finds active on every row or on none
+    gets its signs (as many +1 as -1, on the same columns) and its bias (0 .. 2) drawn again, up to 32 times, until it is active on
+    some row and inactive on another; layer by layer from the input, each on the inputs the layers before it now give.  In place."""
+    if case.n < 77:
+        return
+    x, zero = rows.astype(np.float64), np.zeros((case.n, 4))
+    for name in ["positions_pose_input"] + [f"positional_net.{i}" for i in range(case.n_layers - 1)] + ["directional_net.0"]:
+        l = next(l for l in _render_layers(case, _f64(state), x, zero)[1] if l.name == name)
+        on = l.z > 0
+        for f in np.nonzero(on.all(0) | ~on.any(0))[0]:
+            nz = np.nonzero(state[name + ".weight"][f])[0]
+            for _ in range(32):
+                signs = np.where(rng.permutation(len(nz)) < len(nz) // 2 + (rng.random() < 0.5) * (len(nz) % 2), 1.0, -1.0)
+                bias = float(rng.integers(0, 3))
+                z = l.a[:, nz] @ signs + bias
+                if (z > 0).any() and (z <= 0).any():
+                    state[name + ".weight"][f, nz], state[name + ".bias"][f] = signs, bias
+                    break
+
+
 # ------------------------------------------------------------------------------------------------ preconditions
 def _tiles_without_nonzero(g):
     g = np.atleast_2d(g) != 0
@@ -322,9 +390,9 @@ def assert_exact(what, got, want64):
 
 # ------------------------------------------------------------------------------------------------ the cases
 def _net(name, n, n_layers=8, width=256, positions_dim=60, additional_input_dim=0, skips=(4,), use_directional_input=1, r=4,
-         p_plus=0.5, seed=1):
-    return NetCase(name, n_layers, width, positions_dim, 24, additional_input_dim, tuple(skips), use_directional_input, n, r, p_plus,
-                   seed)
+         p_plus=0.5, seed=1, directions_dim=24, fill_tiles=0):
+    return NetCase(name, n_layers, width, positions_dim, directions_dim, additional_input_dim, tuple(skips), use_directional_input, n, r,
+                   p_plus, seed, fill_tiles)
 
 
 # r, sign balance and seeds: 4 entries per row, signs balanced, seed 1 unless the float64 reference alone misses a condition of
@@ -395,7 +463,376 @@ def profile_text():
     return PROFILE_HEAD + "".join(describe(c) + "\n" for c in ALL_CASES)
 
 
+# ================================================================================================ inference
+# The cases of tests/test_gpu_mlp_infer_exact.py: the same integer networks through the no-grad entries.  Only forward sums count
+# here (no sum crosses samples), so the bound has two orders of magnitude of headroom and the coverage conditions are about the
+# forward: every 16 x 16 tile of every weight matrix holds an entry (fill_tiles: a skipped or mis-addressed tile changes an integer),
+# every ReLU feature is seen on both sides, the outputs vary.  An InferCase names a net (a NetCase), the entry and the call's form:
+#   entry "encoded": RenderRayNet.forward(rows), rows = render_net_data(net)[1];
+#   entry "fused":   RenderRayNet.forward_fused with PositionalEncoder(0, True) twice (positions_dim = directions_dim = 3): integer
+#                    positions, directions s * e_i (s in +-1, +-2, +-4: the kernels' sqrtf of an fp32 sum of squares and __fdiv_rn give
+#                    exactly +-e_i, direction_premise()), per ray (spr samples each) or per sample, per-ray additional inputs in front
+#                    of (add_first) or behind the position columns; mult: a multiplier on positions and additional inputs.
+InferCase = namedtuple("InferCase", "name net entry spr per_sample add_first mult", defaults=(1, 0, 0, 1))
+
+
+def _as_infer(base, **kw):
+    """the shape and generator parameters of a case of the training tests, every weight tile occupied"""
+    return base._replace(name="infer-" + base.name[len("net-"):], fill_tiles=1, **kw)
+
+
+def _enc(net):
+    return InferCase(net.name, net, "encoded")
+
+
+def _fused(name, n, spr=1, per_sample=0, add_first=0, mult=1, **kw):
+    net = _net("fused-" + name, n, positions_dim=3, directions_dim=3, fill_tiles=1, **kw)
+    assert n % spr == 0
+    return InferCase(net.name, net, "fused", spr, per_sample, add_first, mult)
+
+
+INFER_DEFAULT = {n: _enc(_as_infer(NET_DEFAULT[n])) for n in (1, 77, 333, 1100)}
+INFER_WIDTHS = [_enc(_as_infer(c)) for c in NET_WIDTHS] + [
+    _enc(_net("infer-200x3-skip1", 333, n_layers=3, width=200, skips=(1,), fill_tiles=1)),          # padded inside 256
+    _enc(_net("infer-384x2", 333, n_layers=2, width=384, skips=(), fill_tiles=1)),                   # one wave per SIMD: 320, 384,
+    _enc(_net("infer-448x2-skip0", 333, n_layers=2, width=448, skips=(0,), fill_tiles=1)),           # 448, 512
+    _enc(_net("infer-576x2-skip0-layered", 333, n_layers=2, width=576, skips=(0,), fill_tiles=1))]   # smpl_nerf_amd/layered.py
+INFER_INPUTS = [_enc(_as_infer(c)) for c in NET_INPUTS]
+INFER_CASES = [INFER_DEFAULT[n] for n in (1, 77, 333, 1100)] + INFER_WIDTHS + INFER_INPUTS
+LAYERED = INFER_WIDTHS[-1]
+
+FUSED_POOL = _fused("256x8-n1100", 1100)                          # the pool of rows of the launch forms (big_rows)
+FUSED_RAYS = [_fused("256x8-ray4", 332, spr=4), _fused("256x8-ray24", 336, spr=24), _fused("256x8-sample4", 332, spr=4, per_sample=1)]
+# the four forms of tests/test_gpu_infer_compose.NETS with per-ray additional inputs: 24 samples per ray fold, 4 do not
+FUSED_ADD = [_fused("add69-first-fold", 336, spr=24, add_first=1, additional_input_dim=69),
+             _fused("add69-last-fold", 336, spr=24, additional_input_dim=69),
+             _fused("add69-first-nofold", 332, spr=4, add_first=1, additional_input_dim=69),
+             _fused("add69-last-nofold", 332, spr=4, additional_input_dim=69)]
+# the structures of tests/test_gpu_infer_compose.NETS (composed stream: widths up to 256) and the narrow widths of the throughput form
+FUSED_NETS = [_fused("256x1", 333, n_layers=1, skips=()), _fused("256x2", 333, n_layers=2, skips=()),
+              _fused("256x4-skip1", 333, n_layers=4, skips=(1,)), _fused("256x10-skips257", 333, n_layers=10, skips=(2, 5, 7)),
+              _fused("256x8-nodir", 333, use_directional_input=0), _fused("64x8", 333, width=64), _fused("200x8", 333, width=200),
+              _fused("128x4-skip1", 333, n_layers=4, width=128, skips=(1,))]
+# (no fused cases above width 256: those kernels want at least 17 input columns in every layer - csrc/mlp_plan.h refuses the 3 of an
+# identity-only encoder - so the widths 320 .. 512 are reached through the encoded entry, INFER_WIDTHS)
+FUSED_CASES = [FUSED_POOL] + FUSED_RAYS + FUSED_ADD + FUSED_NETS
+# split-precision inference (snerf_mlp_fwd_bf16_f32, width 256): per mode a case whose every layer input is at most 255 - its own first
+# part in every mode - and one whose largest layer inputs need the mode's last part (split_premise(); the multiplier is the knob:
+# 31 keeps every input inside two bf16 parts = 16 bits, 301 takes them past one fp16 part = 11 bits and keeps them inside two, 3001
+# takes some past 2^16 and keeps every sum of absolute terms below 2^24)
+SPLIT_FIRST = _fused("256x4-skip1-r3-first-part", 333, n_layers=4, skips=(1,), r=3)
+SPLIT_LAST = {"bf16x3": _fused("256x8-x31", 333, mult=31), "bf16x6": _fused("256x8-x3001", 333, mult=3001),
+              "f16x3": _fused("256x8-x301", 333, mult=301)}
+SPLIT_MODES = {"bf16x3": (2, "bf16"), "bf16x6": (3, "bf16"), "f16x3": (2, "f16")}           # parts per operand, format
+ALL_INFER_CASES = INFER_CASES + FUSED_CASES + [SPLIT_FIRST, SPLIT_LAST["bf16x3"], SPLIT_LAST["bf16x6"]]
+# the warp net's no-grad entries: WARP_CASES through forward(rows); forward_fused at 4 samples per ray (no fold: the per-ray pose
+# fold of csrc/warp.hip: warp_fold_bytes applies from 8 samples per ray) and at 8 (fold)
+WARP_FUSED_FOLD = _warp(256, 43, 336, spr=8)
+WARP_INFER_FUSED = [WARP_FUSED, WARP_FUSED_FOLD]
+
+
+def direction_premise(d):
+    """fp32, on the CPU, operation by operation as the kernels do it (csrc/mlp.hip: mlp_fwd_body; no fast-math anywhere in build.py):
+    nrm = sqrtf((ux ux + uy uy) + uz uz), d / nrm.  Returns the normalised directions; for s * e_i they are exactly sign(s) e_i."""
+    d = np.asarray(d, F32)
+    nrm = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]).astype(F32) + d[:, 2] * d[:, 2], dtype=F32)
+    return (d / nrm[:, None]).astype(F32)
+
+
+def infer_data(case):
+    """(state dict, inputs, rows): inputs = {"rows"} (encoded) or {"x" [n, 3], "d" [n or n / spr, 3], "add" [n / spr, A] or None};
+    rows [n, positions + additional + directions] are the encoded rows the float64 reference evaluates"""
+    net = case.net
+    if case.entry == "encoded":
+        state, rows, _ = render_net_data(net)
+        return state, {"rows": rows}, rows
+    rng = np.random.default_rng([net.seed, net.width, net.n_layers, net.n, case.spr, case.per_sample, case.add_first, 17])
+    state = _state(rng, render_net_shapes(*net[1:8]), net.r, net.p_plus, net.fill_tiles)
+    n, rays = net.n, net.n // case.spr
+    x = (case.mult * rng.integers(-2, 3, (n, 3))).astype(F32)
+    nd = n if case.per_sample else rays
+    d = np.zeros((nd, 3), F32)
+    d[np.arange(nd), rng.integers(0, 3, nd)] = rng.choice([-4.0, -2.0, -1.0, 1.0, 2.0, 4.0], nd)
+    add = (case.mult * rng.integers(-2, 3, (rays, net.additional_input_dim))).astype(F32) if net.additional_input_dim else None
+    per_sample = lambda v: v if len(v) == n else np.repeat(v, case.spr, 0)
+    cols = [x] if add is None else [per_sample(add), x] if case.add_first else [x, per_sample(add)]
+    rows = np.concatenate(cols + [per_sample(np.sign(d))], 1).astype(F32)
+    _make_two_sided(net, state, rows, rng)
+    return state, {"x": x, "d": d, "add": add}, rows
+
+
+Composed = namedtuple("Composed", "sigma dnet rgb raw own_abs_sum entries")
+InferRef = namedtuple("InferRef", "out layers composed")
+
+
+def composed_maps(net, P):
+    """mlp_compose_mid_kernel / mlp_compose_out_kernel (csrc/mlp.hip) restated in float64 numpy: sigma' = w_s W_a with bias
+    w_s b_a + b_s; dir-net' = W_n [W_d[:, :W] W_a | W_d[:, W:]] with bias W_n (W_d[:, :W] b_a + b_d) + b_n.  Returns
+    (sigma' weight, bias, dir-net' weight, bias, the largest sum of absolute terms of the composition's own sums)."""
+    W, A = net.width, np.abs
+    Wa, ba = P["additional_linear_layer.weight"], P["additional_linear_layer.bias"]
+    ws, bs = P["sigma_out_layer.weight"], P["sigma_out_layer.bias"]
+    Wd, bd = P["directional_input.weight"], P["directional_input.bias"]
+    Wn, bn = P["directional_net.0.weight"], P["directional_net.0.bias"]
+    Wd1, Wd2 = Wd[:, :W], Wd[:, W:]
+    mid_w, mid_b = Wd1 @ Wa, Wd1 @ ba + bd
+    own = [A(ws) @ A(Wa), A(ws) @ A(ba) + A(bs), A(Wd1) @ A(Wa), A(Wd1) @ A(ba) + A(bd), A(Wn) @ A(mid_w), A(Wn) @ A(Wd2),
+           A(Wn) @ A(mid_b) + A(bn)]
+    return (ws @ Wa, ws @ ba + bs, np.concatenate([Wn @ mid_w, Wn @ Wd2], 1), Wn @ mid_b + bn,
+            max(float(v.max()) for v in own if v.size))
+
+
+@functools.lru_cache(maxsize=None)
+def infer_reference(case):
+    """float64: raw of the UNCOMPOSED network on the case's rows (the numpy layers, checked against torch_ref.render_ray_net), every
+    layer, and for widths up to 256 the same rows through the composed maps - which must give the same raw"""
+    net = case.net
+    state, _, rows = infer_data(case)
+    P, x = _f64(state), rows.astype(np.float64)
+    raw, layers, _, _ = _render_layers(net, P, x, np.zeros((net.n, 4)))
+    with torch.no_grad():
+        want = R.render_ray_net({k: torch.from_numpy(v) for k, v in P.items()}, torch.from_numpy(x),
+                                **{k: (tuple(v) if k == "skips" else v) for k, v in net_kw(net).items() if k != "width"})
+    assert np.array_equal(raw, want.numpy())
+    composed = None
+    if net.width <= 256:
+        sw, sb, dw, db, own = composed_maps(net, P)
+        h, dd = layers[net.n_layers - 1].out, x[:, x.shape[1] - net.directions_dim:]
+        sigma = Layer("sigma'", h, sw, sb, False)
+        dnet = Layer("dir-net'", np.concatenate([h, dd], 1) if net.use_directional_input else h, dw, db, True)
+        rgb = Layer("rgb_out_layer", dnet.out, P["rgb_out_layer.weight"], P["rgb_out_layer.bias"], False)
+        composed = Composed(sigma, dnet, rgb, np.concatenate([rgb.out, sigma.out], 1), own, [sw, sb, dw, db])
+        assert np.array_equal(composed.raw, raw)
+    return InferRef(raw, layers, composed)
+
+
+def infer_preconditions(case):
+    """Measured on the float64 reference alone:
+      max_abs_sum:   the largest sum of absolute terms over every forward pre-activation, through the composed maps too, and over the
+                     composition's own sums - below 2^24 every order is exact in fp32;
+      composed_ok:   every composed entry and bias is an integer that fp32 holds;
+      zero_preacts, relu_min, relu_max: as preconditions();
+      one_sided:     hidden features of a ReLU layer that are active on every row or on none;
+      empty_tiles:   origin-aligned 16 x 16 tiles without a non-zero over every weight matrix, the composed maps included;
+      min_distinct:  the smallest number of distinct values one of the four output columns takes over the rows."""
+    ref = infer_reference(case)
+    m = dict(max_abs_sum=0.0, composed_ok=True, zero_preacts=0, relu_min=1.0, relu_max=0.0, one_sided=0, empty_tiles=0,
+             min_distinct=min(len(np.unique(ref.out[:, j])) for j in range(4)), max_act=0.0)
+    for l in ref.layers + (list(ref.composed[:3]) if ref.composed else []):
+        m["max_abs_sum"] = max(m["max_abs_sum"], float(l.abs_fwd.max()))
+        m["max_act"] = max(m["max_act"], float(np.abs(l.a).max()))
+        m["empty_tiles"] += _tiles_without_nonzero(l.w)
+    for l in ref.layers:
+        if l.relu:
+            on = l.z > 0
+            m["relu_min"], m["relu_max"] = min(m["relu_min"], float(on.mean())), max(m["relu_max"], float(on.mean()))
+            m["zero_preacts"] += int((l.z == 0).sum())
+            m["one_sided"] += int((on.all(0) | ~on.any(0)).sum())
+    if ref.composed:
+        m["max_abs_sum"] = max(m["max_abs_sum"], ref.composed.own_abs_sum)
+        m["composed_ok"] = all(np.array_equal(v, np.rint(v)) and np.abs(v).max() < INT_LIMIT for v in ref.composed.entries)
+    return m
+
+
+def assert_infer_preconditions(case):
+    m, n = infer_preconditions(case), case.net.n
+    assert m["max_abs_sum"] < INT_LIMIT and m["composed_ok"] and m["empty_tiles"] == 0 and m["zero_preacts"] >= 1, (case.name, m)
+    assert n < 16 or (0.25 <= m["relu_min"] and m["relu_max"] <= 0.75), (case.name, m)
+    assert n < 77 or (m["one_sided"] == 0 and m["min_distinct"] >= 8), (case.name, m)
+    return m
+
+
+def describe_infer(case):
+    m = infer_preconditions(case)
+    form = case.entry if case.entry == "encoded" else \
+        f"fused spr {case.spr} {'per-sample' if case.per_sample else 'per-ray'} dirs" + (" add first" if case.add_first else "")
+    return (f"{case.name:34s} {form:34s} max|act| {m['max_act']:8.0f}  largest sum of |terms| {m['max_abs_sum']:9.0f} "
+            f"({m['max_abs_sum'] / INT_LIMIT:.5f} of 2^24)  composed {'integers' if infer_reference(case).composed else 'none':8s}  "
+            f"empty tiles {m['empty_tiles']}  ReLU active {m['relu_min']:.3f} .. {m['relu_max']:.3f}  zero pre-activations "
+            f"{m['zero_preacts']}  one-sided features {m['one_sided']}  distinct outputs >= {m['min_distinct']}")
+
+
+def big_rows(case, n, seed):
+    """A call of n samples made of the case's own rows (the pool): whole rays drawn with replacement.  Returns (inputs as
+    infer_data gives them, index [n] into the pool's samples); no forward sum crosses samples, so the expected output is
+    infer_reference(case).out[index]."""
+    _, inputs, _ = infer_data(case)
+    assert n % case.spr == 0
+    pool_rays = case.net.n // case.spr
+    ray = np.arange(pool_rays) if n == case.net.n else np.random.default_rng([seed, n]).integers(0, pool_rays, n // case.spr)
+    idx = (ray[:, None] * case.spr + np.arange(case.spr)).ravel()
+    if case.entry == "encoded":
+        return {"rows": inputs["rows"][idx]}, idx
+    return {"x": inputs["x"][idx], "d": inputs["d"][idx if case.per_sample else ray],
+            "add": None if inputs["add"] is None else inputs["add"][ray]}, idx
+
+
+# ---- which kernels a fused fp32 inference call of a width-256 net runs on (csrc/mlp_lat.hip: lat_lds, lat_split, lat_cost, lat_choose;
+# csrc/mlp.hip: launch_fwd), restated the way wgrad_splits() restates the wgrad rule
+def encoder_kblocks(freqs, identity):
+    per_lane = (3 * identity + 3 * freqs + 3) // 4
+    return (2 * per_lane + 3) // 4
+
+
+def lat_limits(pos_nkb=1, dir_nkb=1, add_nkb=0):
+    """(s_max, pair_s): the most 16-sample tiles per pass whose LDS fits 160 KiB, and the most of which two workgroups fit a CU"""
+    pad = lambda k: -(-k // 4) * 4
+    lds = lambda s: s * (2 * 16384 + (pad(pos_nkb + add_nkb) + pad(16 + dir_nkb) - 16) * 1024)
+    s_max = max([s for s in (1, 2, 3, 4) if lds(s) <= 160 * 1024], default=0)
+    return s_max, max([h for h in (1, 2) if 2 * lds(h) <= 160 * 1024], default=0)
+
+
+def lat_split(n16, n_cu, s_max, pair_s=0, mixed_ok=False):
+    """the launches of n16 tiles: dicts of kind ("single": one workgroup per CU; "paired": two of S tiles per CU; "mixed": a two-tile
+    and a one-tile workgroup per CU), S, grid, passes, tile_off, tile_end"""
+    out, done = [], 0
+    S = min(s_max, -(-n16 // n_cu))
+    per_round = S * n_cu
+    passes = n16 // per_round
+
+    def mixed(first, tiles):
+        n_a = min(n_cu, tiles // 2)
+        return dict(kind="mixed", S=3, grid=n_a + tiles - 2 * n_a, passes=1, tile_off=first, tile_end=first + tiles)
+    if passes > 0:
+        if passes == 1 and S % 2 == 0 and S // 2 <= pair_s:
+            out.append(dict(kind="paired", S=S // 2, grid=2 * n_cu, passes=1, tile_off=0, tile_end=per_round))
+        elif passes == 1 and S == 3 and mixed_ok and pair_s >= 2:
+            out.append(mixed(0, per_round))
+        else:
+            out.append(dict(kind="single", S=S, grid=n_cu, passes=passes, tile_off=0, tile_end=per_round * passes))
+        done = per_round * passes
+    r = n16 - done
+    if r > 0:
+        S2 = min(s_max, -(-r // n_cu))
+        if S2 == 3 and mixed_ok and pair_s >= 2:
+            return out + [mixed(done, r)]
+        kind = "single"
+        if S2 % 2 == 0 and S2 // 2 <= pair_s:
+            S2, kind = S2 // 2, "paired"
+        out.append(dict(kind=kind, S=S2, grid=-(-r // S2), passes=1, tile_off=done, tile_end=n16))
+    return out
+
+
+def lat_cost(n16, n_cu, s_max, fixed=21.0, per_tile=41.0):
+    return sum(fixed + q["passes"] * (4.0 + per_tile * q["S"]) for q in lat_split(n16, n_cu, s_max))
+
+
+def lat_choose_infer(n, n_cu, s_max=4):
+    """(mode, n_main) of lat_choose for inference: 0 the throughput kernel alone, 1 the latency kernels alone, 2 the throughput kernel
+    on the first n_main samples - whole rounds of 128 samples per CU - and the latency kernels on the rest"""
+    n16, per_round = (n + 15) // 16, 128 * n_cu
+    t_best = 178.0 if n <= 64 * n_cu else -(-n // per_round) * 295.0
+    best = (0, 0)
+    if n16 <= 64 * n_cu:
+        t = lat_cost(n16, n_cu, s_max)
+        if t < t_best:
+            t_best, best = t, (1, 0)
+    rounds = n // per_round
+    rem = n - rounds * per_round
+    if 1 <= rounds <= 64 and rem > 0 and rounds * 295.0 + lat_cost((rem + 15) // 16, n_cu, s_max) < 0.98 * t_best:
+        best = (2, rounds * per_round)
+    return best
+
+
+def launch_form(n, n_cu, lat=True):
+    """what a fused fp32 inference call of n samples of a width-256 net with identity encoders and no additional inputs runs as:
+    (mode, the kinds of the latency launches in order, throughput tile of 64 or 128 samples or 0)"""
+    s_max, pair_s = lat_limits()
+    mode, n_main = lat_choose_infer(n, n_cu, s_max) if lat else (0, 0)
+    kinds = [q["kind"] for q in lat_split((n + 15) // 16 - n_main // 16, n_cu, s_max, pair_s, True)] if mode else []
+    return mode, kinds, 0 if mode == 1 else 128 if mode == 2 or n > 64 * n_cu else 64
+
+
+def lat_sizes(n_cu):
+    """sizes that reach each branch of lat_split on n_cu compute units, derived from the count: [(label, n, kinds wanted)]"""
+    c = n_cu
+    return [("single", 1, ["single"]), ("single", 77, ["single"]), ("single", min(1100, 16 * c - 4), ["single"]),
+            ("paired", 16 * 2 * c, ["paired"]), ("mixed", 16 * 3 * c, ["mixed"]),
+            ("paired + remainder", 16 * (4 * c + 5), ["paired", "single"]), ("ragged mixed remainder", 16 * (2 * c + 3) - 5, ["mixed"])]
+
+
+def hybrid_size(n_cu):
+    return 128 * n_cu + 16 * n_cu - 7          # one throughput round and a ragged latency remainder of n_cu tiles
+
+
+def throughput_sizes(n_cu):
+    """[(label, n)] of the SNERF_LAT=0 child: 64-sample tiles, one 128-sample tile per workgroup, and a call in which every workgroup
+    wraps its weight stream and the last tile is ragged"""
+    return [("a ragged tile", 333), ("a ragged tile", 1100), ("one tile per workgroup", 128 * n_cu),
+            ("wrapped, ragged", (2 * n_cu + 1) * 128 - 37)]
+
+
+# ---- the operand split of the split-precision kernels (csrc/mlp_bf16_device.h: split_pair_into), restated
+def _bf16_rne(v):
+    b = np.asarray(v, F32).view(np.uint32).astype(np.uint64)
+    return ((b + 0x7fff + ((b >> 16) & 1)) & 0xffff0000).astype(np.uint32).view(F32)
+
+
+def _f16_rtz(v):
+    """fp16 by truncation (v_cvt_pkrtz_f16_f32): 11 significant bits, none below 2^-24; |v| < 2^16"""
+    a = np.abs(np.asarray(v, np.float64))
+    assert (a < 65536).all()
+    e = np.floor(np.log2(np.where(a > 0, a, 1.0)))
+    q = 2.0 ** np.maximum(e - 10, -24)
+    return (np.sign(v) * np.floor(a / q) * q).astype(F32)
+
+
+def split_parts(a, mode):
+    """the parts of the B operand a [n, k] (float64 integers) as the mode's kernels form them, as float64 in a's own scale.
+    bf16x3 / bf16x6: 2 / 3 bf16 parts, each the round-to-nearest-even bf16 of what the ones before leave (split_pair_into).  f16x3: the
+    sample's row scaled by a power of two that takes its largest |value| - at least 1 where encoder or additional columns enter, as
+    here in every layer that has any - into [2^14, 2^15) (operand_scale16, kx_pos), then 2 fp16 parts by truncation."""
+    ns, fmt = SPLIT_MODES[mode]
+    a = np.asarray(a, np.float64)
+    scale = np.ones((a.shape[0], 1))
+    if fmt == "f16":
+        top = np.maximum(np.abs(a).max(1, keepdims=True), 1.0)
+        scale = 2.0 ** (14 - np.floor(np.log2(top)))
+    rest, parts = (a * scale).astype(F32), []
+    assert np.array_equal(rest.astype(np.float64), a * scale)
+    for _ in range(ns):
+        p = _bf16_rne(rest) if fmt == "bf16" else _f16_rtz(rest)
+        parts.append(p.astype(np.float64) / scale)
+        rest = (rest - p).astype(F32)
+    return parts
+
+
+def split_premise(case, mode):
+    """On the reference alone: does every layer input recombine exactly from the parts the mode keeps (weights of +-1 are their own
+    first part, so every product weight x part is one of the cross terms the kernels form - mlp_bf16_device.h: Terms<2>, Terms<3>
+    hold (A 0, B s) for every s); the share of non-zero layer inputs with a non-zero LAST part; the largest sum of absolute terms
+    when each input enters as its parts"""
+    ref = infer_reference(case)
+    exact, last, total, abs_sum = True, 0, 0, 0.0
+    for l in ref.layers:
+        parts = split_parts(l.a, mode)
+        exact = exact and np.array_equal(sum(parts), l.a)
+        last += int((parts[-1] != 0).sum())
+        total += int((l.a != 0).sum())
+        abs_sum = max(abs_sum, float((sum(np.abs(p) for p in parts) @ np.abs(l.w).T + np.abs(l.b)).max()))
+    return dict(exact=bool(exact), last_share=last / total, max_abs_sum=abs_sum)
+
+
+INFER_PROFILE = os.path.join(ROOT, "profiles", "mlp_infer_exact_cases.txt")
+INFER_PROFILE_HEAD = ("# tests/exact_net_ref.py: what the float64 reference of every case of tests/test_gpu_mlp_infer_exact.py measures (CPU;\n"
+                      "# rewritten by `python tests/exact_net_ref.py`, compared by tests/test_exact_net_host.py).  Forward sums only.\n")
+
+
+def _describe_split(mode, case):
+    m, p = infer_preconditions(case), split_premise(case, mode)
+    return (f"split {mode:7s} {case.name:34s} max|layer input| {m['max_act']:8.0f}  recombines exactly {p['exact']}  non-zero last part "
+            f"{p['last_share']:.5f}  largest sum of |terms| over the parts {p['max_abs_sum']:9.0f}")
+
+
+def infer_profile_text():
+    return (INFER_PROFILE_HEAD + "".join(describe_infer(c) + "\n" for c in ALL_INFER_CASES) +
+            "".join(_describe_split(mode, c) + "\n" for mode in SPLIT_MODES for c in (SPLIT_FIRST, SPLIT_LAST[mode])) +
+            describe(WARP_FUSED_FOLD) + "\n")
+
+
 if __name__ == "__main__":
     with open(PROFILE, "w") as f:
         f.write(profile_text())
-    print(profile_text())
+    with open(INFER_PROFILE, "w") as f:
+        f.write(infer_profile_text())
+    print(profile_text() + infer_profile_text())

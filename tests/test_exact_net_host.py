@@ -40,7 +40,7 @@ def test_render_net_in_float32_on_the_cpu_equals_float64(case):
         _same(k, v.grad, ref.grads[k])
 
 
-@pytest.mark.parametrize("case", E.WARP_CASES + [E.WARP_FUSED], ids=IDS)
+@pytest.mark.parametrize("case", E.WARP_CASES + E.WARP_INFER_FUSED, ids=IDS)
 def test_warp_net_in_float32_on_the_cpu_equals_float64(case):
     state, rows, d_out = E.warp_net_data(case)
     ref = E.warp_net_reference(case)
@@ -140,6 +140,159 @@ def test_preconditions_see_what_they_are_for():
         E.assert_preconditions(thin)
     with pytest.raises(AssertionError):
         E.assert_preconditions(E.NET_DEFAULT[333], max_operand=255)
+
+
+# ---- the inference cases of tests/test_gpu_mlp_infer_exact.py --------------------------------------------------------------------------
+@pytest.mark.parametrize("case", E.ALL_INFER_CASES, ids=IDS)
+def test_inference_preconditions_hold_on_the_float64_reference(case):
+    """the forward bound (through the composed maps and over the composition's own sums too), integer composed entries, a zero
+    pre-activation, the ReLU shares, every feature seen active and inactive, no weight tile without an entry, varied outputs"""
+    m = E.assert_infer_preconditions(case)
+    print(E.describe_infer(case))
+    assert m["max_abs_sum"] < 2 ** 24 and m["empty_tiles"] == 0 and m["composed_ok"]
+    assert (E.infer_reference(case).composed is not None) == (case.net.width <= 256)
+
+
+def _forward32(case, composed):
+    """raw of the case in float32 torch on the CPU: the network as it stands, or its trunk followed by the composed maps"""
+    net, ref = case.net, E.infer_reference(case)
+    state, _, rows = E.infer_data(case)
+    P, x = {k: torch.from_numpy(v) for k, v in state.items()}, torch.from_numpy(rows)
+    kw = {k: v for k, v in E.net_kw(net).items() if k != "width"}
+    if not composed:
+        return R.render_ray_net(P, x, **kw)
+    lin = torch.nn.functional.linear
+    pp, dd = x[:, :net.positions_dim + net.additional_input_dim], x[:, x.shape[1] - net.directions_dim:]
+    h = torch.relu(lin(pp, P["positions_pose_input.weight"], P["positions_pose_input.bias"]))
+    for i in range(net.n_layers - 1):
+        h = torch.relu(lin(torch.cat([h, pp], 1) if i in net.skips else h, P[f"positional_net.{i}.weight"], P[f"positional_net.{i}.bias"]))
+    sw, sb, dw, db = (torch.from_numpy(v.astype(np.float32)) for v in ref.composed.entries)
+    e = torch.relu(lin(torch.cat([h, dd], 1) if net.use_directional_input else h, dw, db))
+    return torch.cat([lin(e, P["rgb_out_layer.weight"], P["rgb_out_layer.bias"]), lin(h, sw, sb)], 1)
+
+
+@pytest.mark.parametrize("case", E.ALL_INFER_CASES, ids=IDS)
+def test_inference_net_in_float32_on_the_cpu_equals_float64(case):
+    """the uncomposed network, and (widths up to 256) the trunk followed by the composed maps, both against the UNCOMPOSED float64"""
+    ref = E.infer_reference(case)
+    _same("raw", _forward32(case, False), ref.out)
+    if ref.composed is not None:
+        _same("raw through the composed maps", _forward32(case, True), ref.out)
+
+
+def test_direction_normalisation_gives_unit_axes_exactly():
+    """sqrtf((ux ux + uy uy) + uz uz) and the division, in fp32 operation by operation: s e_i -> sign(s) e_i for every s the cases use;
+    a direction off the axes (1, 1, 0) does not normalise to integers, so the premise is not vacuous"""
+    for s in (-4.0, -2.0, -1.0, 1.0, 2.0, 4.0):
+        d = s * np.eye(3, dtype=np.float32)
+        got = E.direction_premise(d)
+        assert got.dtype == np.float32 and np.array_equal(got, np.sign(d))
+    assert not np.array_equal(E.direction_premise(np.array([[1.0, 1.0, 0.0]])), np.array([[1.0, 1.0, 0.0]], np.float32))
+    for case in E.FUSED_CASES + [E.SPLIT_FIRST] + list(E.SPLIT_LAST.values()):
+        _, inputs, rows = E.infer_data(case)
+        d = inputs["d"]
+        assert d.shape[0] == (case.net.n if case.per_sample else case.net.n // case.spr)
+        assert ((d != 0).sum(1) == 1).all() and set(np.unique(np.abs(d))) <= {0.0, 1.0, 2.0, 4.0}
+        dn = E.direction_premise(d)
+        assert np.array_equal(dn, np.sign(d))
+        assert np.array_equal(rows[:, -3:], dn if len(dn) == case.net.n else np.repeat(dn, case.spr, 0))
+        assert np.abs(inputs["x"]).max() == 2 * case.mult and np.array_equal(inputs["x"], np.rint(inputs["x"]))
+        assert {tuple(abs(v) for v in r) for r in np.unique(np.sign(d), axis=0)} == {(1, 0, 0), (0, 1, 0), (0, 0, 1)}
+
+
+def test_fused_rows_are_what_the_kernel_assembles():
+    """rows = [positions | additional of the ray] or [additional | positions], then the direction of the ray or of the sample"""
+    for case in E.FUSED_ADD + E.FUSED_RAYS:
+        _, inp, rows = E.infer_data(case)
+        n, spr, a = case.net.n, case.spr, case.net.additional_input_dim
+        ray = np.arange(n) // spr
+        assert inp["x"].shape == (n, 3) and rows.shape == (n, 3 + a + 3)
+        x0 = a if case.add_first else 0
+        assert np.array_equal(rows[:, x0:x0 + 3], inp["x"])
+        if a:
+            a0 = 0 if case.add_first else 3
+            assert inp["add"].shape == (n // spr, a) and np.array_equal(rows[:, a0:a0 + a], inp["add"][ray])
+        assert np.array_equal(rows[:, -3:], np.sign(inp["d"][np.arange(n) if case.per_sample else ray]))
+    assert [(c.spr, c.per_sample) for c in E.FUSED_RAYS] == [(4, 0), (24, 0), (4, 1)]
+    assert [(c.spr, c.add_first) for c in E.FUSED_ADD] == [(24, 1), (24, 0), (4, 1), (4, 0)]
+
+
+def test_big_rows_are_rows_of_the_pool():
+    for case, n in ((E.FUSED_POOL, 8192 + 5), (E.FUSED_ADD[0], 24 * 100), (E.INFER_DEFAULT[333], 1000), (E.FUSED_RAYS[2], 4 * 77)):
+        _, pool, _ = E.infer_data(case)
+        inp, idx = E.big_rows(case, n, 3)
+        assert idx.shape == (n,) and idx.min() >= 0 and idx.max() < case.net.n and len(np.unique(idx)) > min(n, case.net.n) // 3
+        again, idx2 = E.big_rows(case, n, 3)
+        assert np.array_equal(idx, idx2) and all(np.array_equal(inp[k], again[k]) for k in inp if inp[k] is not None)
+        if case.entry == "encoded":
+            assert np.array_equal(inp["rows"], pool["rows"][idx])
+            continue
+        assert np.array_equal(inp["x"], pool["x"][idx])
+        ray = idx[::case.spr] // case.spr
+        assert np.array_equal(idx, (ray[:, None] * case.spr + np.arange(case.spr)).ravel())         # whole rays
+        assert np.array_equal(inp["d"], pool["d"][idx if case.per_sample else ray])
+        if pool["add"] is not None:
+            assert np.array_equal(inp["add"], pool["add"][ray])
+    inp, idx = E.big_rows(E.FUSED_POOL, E.FUSED_POOL.net.n, 0)
+    assert np.array_equal(idx, np.arange(E.FUSED_POOL.net.n))                                       # the pool itself, every row once
+
+
+@pytest.mark.parametrize("n_cu", [256, 304, 64])
+def test_launch_forms_of_the_sizes_derived_from_the_compute_unit_count(n_cu):
+    """the restated lat_choose / lat_split (csrc/mlp_lat.hip) on the sizes the GPU test derives from the device's CU count: every
+    branch of lat_split is reached - one workgroup per CU, two paired ones, the mixed launch, a remainder launch, a ragged size - the
+    hybrid size is whole throughput rounds plus a latency remainder, and with SNERF_LAT=0 the sizes are 64- and 128-sample tiles"""
+    assert E.lat_limits() == (4, 2) and E.encoder_kblocks(0, 1) == 1 and E.encoder_kblocks(10, 0) == 4 and E.encoder_kblocks(4, 0) == 2
+    seen = set()
+    for label, n, kinds in E.lat_sizes(n_cu):
+        mode, got, tile = E.launch_form(n, n_cu)
+        assert (mode, got, tile) == (1, kinds, 0), (label, n, mode, got)
+        seen |= set(got) | ({"remainder"} if len(got) == 2 else set()) | ({"ragged"} if n % 16 else set())
+    assert seen == {"single", "paired", "mixed", "remainder", "ragged"}
+    n = E.hybrid_size(n_cu)
+    assert E.launch_form(n, n_cu) == (2, ["single"], 128) and E.lat_choose_infer(n, n_cu) == (2, 128 * n_cu)
+    sizes = E.throughput_sizes(n_cu)
+    assert [E.launch_form(n, n_cu, lat=False)[2] for _, n in sizes] == [64 if n <= 64 * n_cu else 128 for _, n in sizes]
+    assert sizes[2][1] == 128 * n_cu and sizes[3][1] > 2 * 128 * n_cu and sizes[3][1] % 128
+    if n_cu == 256:          # the figures of the comments in csrc/mlp_lat.hip: 4096 samples latency, 32 768 and 153 600 not alone
+        assert E.lat_choose_infer(4096, 256)[0] == 1 and E.lat_choose_infer(32768, 256)[0] == 0
+        assert [q["kind"] for q in E.lat_split(512, 256, 4, 2, True)] == ["paired"]
+        assert E.lat_split(1029, 256, 4, 2, True)[1] == dict(kind="single", S=1, grid=5, passes=1, tile_off=1024, tile_end=1029)
+
+
+@pytest.mark.parametrize("mode", sorted(E.SPLIT_MODES))
+def test_split_precision_premises(mode):
+    """first-part case: every layer input at most 255, so its own first part in every mode (no second part anywhere); last-part case:
+    every layer input recombines exactly from the parts the mode keeps, a non-zero share of them has a non-zero last part, and the
+    sums of absolute terms stay below 2^24 with the inputs entering as their parts"""
+    first, last = E.split_premise(E.SPLIT_FIRST, mode), E.split_premise(E.SPLIT_LAST[mode], mode)
+    assert E.infer_preconditions(E.SPLIT_FIRST)["max_act"] <= E.SPLIT_MAX_OPERAND
+    assert first["exact"] and first["last_share"] == 0 and first["max_abs_sum"] < 2 ** 24
+    ref = E.infer_reference(E.SPLIT_FIRST)
+    assert all(np.array_equal(E.split_parts(l.a, mode)[0], l.a) for l in ref.layers)
+    assert last["exact"] and last["last_share"] > 0 and last["max_abs_sum"] < 2 ** 24
+    # the split can fail: one part too few loses the inputs of the last-part case
+    big = E.infer_reference(E.SPLIT_LAST[mode]).layers[-2].a
+    assert not np.array_equal(sum(E.split_parts(big, mode)[:-1]), big)
+    assert np.array_equal(E._bf16_rne(np.array([257.0, 255.0, -3.0], np.float32)), np.array([256.0, 255.0, -3.0], np.float32))
+    assert np.array_equal(E._f16_rtz(np.array([2049.0, 4095.0, -4095.0, 2.0 ** -25], np.float32)),
+                          np.array([2048.0, 4094.0, -4094.0, 0.0], np.float32))
+
+
+def test_fused_warp_case_with_the_fold_meets_the_preconditions():
+    case = E.WARP_FUSED_FOLD
+    m = E.assert_preconditions(case)
+    assert case.spr == 8 and case.n % case.spr == 0 and case.row_len == E.WARP_FUSED.row_len and m["max_act"] <= E.SPLIT_MAX_OPERAND
+    assert E.preconditions(E.WARP_FUSED)["max_act"] <= E.SPLIT_MAX_OPERAND          # (every input its own first bf16 part)
+
+
+def test_inference_profile_is_the_record_of_these_cases():
+    """profiles/mlp_infer_exact_cases.txt holds what this run measures (rewrite it with `python tests/exact_net_ref.py`)"""
+    with open(E.INFER_PROFILE) as f:
+        assert f.read() == E.infer_profile_text()
+    names = [c.name for c in E.ALL_INFER_CASES]
+    assert len(set(names)) == len(names)
+    assert sorted({c.net.width for c in E.INFER_CASES}) == [64, 100, 128, 200, 256, 320, 384, 448, 512, 576]
 
 
 def test_profile_is_the_record_of_these_cases():
