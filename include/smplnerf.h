@@ -642,6 +642,46 @@ SNERF_API int snerf_ssim_bwd_f32(const float *x, const float *y, int64_t N, int6
                               int64_t sh, int64_t sw, const float *win, int k, float c1, float c2, const float *g_ssim,
                               const float *g_cs, float *dx, void *workspace, int64_t workspace_bytes, snerf_stream_t stream);
 
+/* ---- SmplEstimator, inference: the fused convolution block and the whole network (models/smpl_estimator.py:6-47, eval mode) ----
+ * One block, one launch, contiguous NCHW fp32:
+ *   y = [maxpool2x2](relu(scale[co] * conv3x3_pad1(x, w)[co] + shift[co]))
+ *   x [N,Ci,H,W], w [Co,Ci,3,3], scale, shift [Co] -> y [N,Co,H,W], or [N,Co,H/2,W/2] with pool != 0.  relu and pool are separate
+ *   flags.  With pooling an odd H or W floors as nn.MaxPool2d(2, 2) does: the last row or column takes part in no window.
+ * Arithmetic: exact fp32 on the matrix cores.  Every output element is one fused-multiply-add chain over k = ci 9 + ky 3 + kx in
+ *   ascending order (zero products stand in for the padding); then one multiplication by scale, one addition of shift.  The chain
+ *   depends on Ci alone, so a pixel's value does not depend on N, on the grid or on where it lies in a tile; no atomics; two calls
+ *   give the same bits.  Every element of y is written.
+ * 1 <= Ci, Co <= 256; H, W >= 1 (with pooling >= 2); N >= 0 (0: SNERF_OK whatever the pointers are); N Ci H W and N Co H W below
+ *   2^31; with N > 0 no null pointer - else SNERF_E_BADARG on the host, before anything touches a device, with a message naming the
+ *   value; a bad scalar is an error whatever N is. */
+SNERF_API int snerf_conv3x3_block_f32(const float *x, int64_t N, int Ci, int64_t H, int64_t W, const float *w, const float *scale,
+                              const float *shift, int Co, int relu, int pool, float *y, snerf_stream_t stream);
+/* The network.  Device pointers to the tensors of the reference's state_dict, as they are stored: */
+typedef struct snerf_conv_bn {
+    const float *weight, *bias;                                         /* convN.weight [Co,Ci,3,3], convN.bias [Co] */
+    const float *bn_weight, *bn_bias, *running_mean, *running_var;      /* bnN.* [Co] */
+    double eps;                                                         /* bnN.eps */
+} snerf_conv_bn;
+typedef struct snerf_smpl_estimator {
+    snerf_conv_bn block[5];                                             /* channels 3 -> 16 -> 32 -> 64 -> 64 -> 128 */
+    const float *fc1_weight, *fc1_bias, *fc2_weight, *fc2_bias;         /* [500,8192], [500], [human_size,500], [human_size] */
+    int32_t human_size;
+} snerf_smpl_estimator;
+/* images [N,3,128,128] -> out [N,human_size], eval mode (running statistics, no dropout), in one call of eight launches on `stream`:
+ *   the fold of each block's BatchNorm and bias, scale = gamma / sqrt(var + eps), shift = beta + (b - mean) scale, computed on the
+ *   device in float64 from the pointers above and rounded once (so a parameter changed in place is seen by the next call);
+ *   the five blocks (pooling after blocks 2 .. 5) between two activation buffers; fc1 with ReLU and fc2 on snerf_linear_fwd_f32's
+ *   kernel.  Block 5 writes contiguous [N,128,8,8]: the rows of the reference's view(-1, 8 * 8 * 128).
+ * workspace: snerf_smpl_estimator_workspace_bytes(N, human_size) bytes (-1 on a bad argument), 16-byte aligned: the fold and the
+ *   two buffers.  Nothing is allocated and nothing synchronises: the call can be captured into a graph.  Same inputs, same bits; an
+ *   image's row does not depend on the rest of the batch.
+ * SNERF_E_BADARG on the host: a null net; human_size < 1; N negative or above 8191 (2^31 activations); an eps that is negative or
+ *   not finite; with N > 0 a null pointer in the net, null images or out, a workspace that is null or too small.  SNERF_E_ALIGN: a
+ *   workspace that is not 16-byte aligned.  N = 0: SNERF_OK. */
+SNERF_API int64_t snerf_smpl_estimator_workspace_bytes(int64_t N, int human_size);
+SNERF_API int snerf_smpl_estimator_fwd_f32(const snerf_smpl_estimator *net, const float *images, int64_t N, float *out, void *workspace,
+                              int64_t workspace_bytes, snerf_stream_t stream);
+
 /* ---- 8(f)-1: on-device ray generation + stratified coarse sampling --------------------------------------
  * Replaces get_rays (utils.py:50-54) + CoarseSampling (datasets/transforms.py:80-89) + ToTensor (:13-21) for a
  * batch of rays.  poses: fp64 [n_frames, 4, 4] camera-to-world; ray_index int64 [B] = frame*H*W + row*W + col;

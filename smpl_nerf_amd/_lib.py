@@ -54,6 +54,18 @@ class SmplModel(ctypes.Structure):
                 ("J_dirs", _P), ("weights", _P), ("parents", POINTER(c_int32))]
 
 
+class ConvBn(ctypes.Structure):
+    """struct snerf_conv_bn - one Conv2d + BatchNorm2d of SmplEstimator: device pointers to the state_dict's tensors, and bn.eps."""
+    _fields_ = [("weight", _P), ("bias", _P), ("bn_weight", _P), ("bn_bias", _P), ("running_mean", _P), ("running_var", _P),
+                ("eps", c_double)]
+
+
+class SmplEstimatorNet(ctypes.Structure):
+    """struct snerf_smpl_estimator - models/smpl_estimator.py:14-30."""
+    _fields_ = [("block", ConvBn * 5), ("fc1_weight", _P), ("fc1_bias", _P), ("fc2_weight", _P), ("fc2_bias", _P),
+                ("human_size", c_int32)]
+
+
 class AdamState(ctypes.Structure):
     """struct snerf_adam_state - torch.optim.Adam over one flat fp32 buffer (solver/nerf_solver.py:11-14, 31-33)."""
     _fields_ = [("params", _P), ("grads", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("n_params", c_int64),
@@ -174,6 +186,10 @@ SIGNATURES = {
                                    c_float, _P, _P, _P, _P, c_int64, _P]),
     "snerf_ssim_bwd_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int, c_float,
                                    c_float, _P, _P, _P, _P, c_int64, _P]),
+    # SmplEstimator, inference: the fused conv-BN-ReLU-pool block and the whole network (csrc/conv_block.hip)
+    "snerf_conv3x3_block_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "snerf_smpl_estimator_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "snerf_smpl_estimator_fwd_f32": (c_int, [POINTER(SmplEstimatorNet), _P, c_int64, _P, _P, c_int64, _P]),
     "snerf_raygen_f64": (c_int, [_P, c_int64, c_int, c_int, c_double, _P, _P, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "snerf_mlp_fwd_encoded_f32": (c_int, [POINTER(MlpDesc), _P, _P, c_int64, c_int64, _P, _P]),
     "snerf_render_rays_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),

@@ -1,0 +1,156 @@
+"""SmplEstimator (models/smpl_estimator.py:6-47): image [N,3,128,128] -> pose [N,human_size].
+
+The module has the reference's parameter and buffer names, so a model_smpl_estimator.pt written by the reference's save_run loads
+with io.load_run, and the other way round.  On the GPU, in eval() mode with grad disabled, forward is ONE call of the library
+(snerf_smpl_estimator_fwd_f32: the BatchNorm fold, five fused conv-BN-ReLU-pool launches, fc1, fc2).  Everywhere else - training
+mode, grad enabled, CPU tensors - it is the reference's expression in torch ops: the training kernels of the convolution block
+(batch-statistics BatchNorm, dropout, weight gradient, pool / ReLU / BN backward) do not exist yet.
+
+validate() is the validation half of SmplEstimatorSolver.train (solver/smpl_estimator_solver.py:70-84); normalize_image restates
+the data set's transform (datasets/transforms.py NormalizeRGBImage, smpl_estimator_dataset.py:78-80).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from ._lib import check, current_stream, ptr
+
+CHANNELS = (3, 16, 32, 64, 64, 128)      # features in front of and behind each of the five blocks
+POOL = (False, True, True, True, True)    # which blocks end in the 2 x 2 max pool
+SIDE = 128                                # image extent: five blocks and four pools leave 8 x 8 x 128 = FLAT features
+FLAT, HIDDEN = 8 * 8 * CHANNELS[-1], 500
+
+
+def fold_bn(conv_bias, bn_weight, bn_bias, running_mean, running_var, eps):
+    """(scale, shift) of ops.conv3x3_block for an eval-mode BatchNorm2d behind a convolution with bias, as the one-call entry folds
+    them: float64, rounded once.  scale = gamma / sqrt(var + eps), shift = beta + (b - mean) scale."""
+    scale = bn_weight.detach().double() / torch.sqrt(running_var.detach().double() + eps)
+    shift = bn_bias.detach().double() + (conv_bias.detach().double() - running_mean.detach().double()) * scale
+    return scale.float(), shift.float()
+
+
+class SmplEstimator(nn.Module):
+
+    def __init__(self, human_size=69):
+        super().__init__()
+        self.pool = nn.MaxPool2d(2, 2)
+        for i in range(5):
+            setattr(self, f"conv{i + 1}", nn.Conv2d(CHANNELS[i], CHANNELS[i + 1], 3, padding=1))
+            setattr(self, f"bn{i + 1}", nn.BatchNorm2d(CHANNELS[i + 1]))
+        self.fc1 = nn.Linear(FLAT, HIDDEN)
+        self.dropout = nn.Dropout(0.25)
+        self.fc2 = nn.Linear(HIDDEN, human_size)
+        self.human_size = human_size
+        self._workspaces = {}      # (device, N) -> uint8 workspace of the one-call forward
+
+    def _blocks(self):
+        return [(getattr(self, f"conv{i}"), getattr(self, f"bn{i}")) for i in range(1, 6)]
+
+    def _forward_torch(self, images):
+        """The network in torch ops, for every case the device path does not take.  In training mode BatchNorm2d normalises with the
+        batch statistics and moves the running ones, and the dropout acts on the flattened features and on fc1's output."""
+        h = images
+        for (conv, bn), pooled in zip(self._blocks(), POOL):
+            h = torch.relu(bn(conv(h)))
+            if pooled:
+                h = self.pool(h)
+        h = self.dropout(h.reshape(-1, FLAT))      # [N, 128, 8, 8] -> [N, 8192], channel-major
+        h = self.dropout(torch.relu(self.fc1(h)))
+        return self.fc2(h)
+
+    def _net(self):
+        """struct snerf_smpl_estimator of the parameters as they lie now (pointers only: the fold happens on the device, per call)."""
+        net = _lib.SmplEstimatorNet()
+        for i, (conv, bn) in enumerate(self._blocks()):
+            tensors = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+            for t in tensors:
+                if t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise RuntimeError("SmplEstimator: the device path needs contiguous fp32 GPU parameters and BatchNorm2d with "
+                                       "affine weights and running statistics")
+            net.block[i] = _lib.ConvBn(*(ptr(t) for t in tensors), float(bn.eps))
+        for t in (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("SmplEstimator: the device path needs contiguous fp32 GPU parameters")
+        net.fc1_weight, net.fc1_bias, net.fc2_weight, net.fc2_bias = (ptr(t) for t in (self.fc1.weight, self.fc1.bias, self.fc2.weight,
+                                                                                       self.fc2.bias))
+        net.human_size = self.fc2.out_features
+        return net
+
+    def _forward_device(self, x):
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, SIDE, SIDE) or x.dtype != torch.float32:
+            raise RuntimeError(f"SmplEstimator: the device path takes fp32 images [N,3,{SIDE},{SIDE}], got {x.dtype} {tuple(x.shape)}")
+        x = x.contiguous()
+        N, hs = x.shape[0], self.fc2.out_features
+        lib = _lib.load()
+        key = (x.device, N)
+        if key not in self._workspaces:
+            nbytes = lib.snerf_smpl_estimator_workspace_bytes(N, hs)
+            if nbytes < 0:
+                check(-1, "snerf_smpl_estimator_workspace_bytes")
+            self._workspaces[key] = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
+        ws = self._workspaces[key]
+        out = torch.empty((N, hs), device=x.device, dtype=torch.float32)
+        net = self._net()
+        with torch.cuda.device(x.device), _lib.timed(f"smpl_estimator_fwd[{N}]"):
+            check(lib.snerf_smpl_estimator_fwd_f32(net, ptr(x), N, ptr(out), ptr(ws), ws.numel(), current_stream()),
+                  "snerf_smpl_estimator_fwd_f32")
+        return out
+
+    def forward(self, x):
+        if x.is_cuda and not self.training and not torch.is_grad_enabled():
+            return self._forward_device(x)
+        return self._forward_torch(x)
+
+    @property
+    def is_cuda(self):
+        """True when the parameters live on a GPU (the attribute the reference's solvers ask a model for)."""
+        return self.fc2.weight.is_cuda
+
+    def save(self, path):
+        """Pickles the WHOLE module to `path`, as the reference's models do in their save(); io.save_run writes the state_dict."""
+        print(f"SmplEstimator: writing the module to {path}")
+        torch.save(self, path)
+
+    def __getstate__(self):      # (the cached workspaces are not part of a saved model)
+        state = self.__dict__.copy()
+        state["_workspaces"] = {}
+        return state
+
+
+def normalize_image(frames):
+    """The data set's transform for this model: 8-bit frames [H,W,3] or [F,H,W,3] (io.load_dataset's BGR frames; the channel order
+    stays, as in the reference) -> float32 tensor [3,H,W] or [F,3,H,W] with values in [0, 1].  The quotient by 255 is taken in
+    float64 and rounded once, which is what the reference's numpy expression does."""
+    frames = np.asarray(frames)
+    if frames.ndim not in (3, 4) or frames.shape[-1] != 3:
+        raise ValueError(f"normalize_image: expected [H,W,3] or [F,H,W,3], got {frames.shape}")
+    unit = np.true_divide(frames, 255.0, dtype=np.float64).astype(np.float32)
+    return torch.from_numpy(np.ascontiguousarray(np.moveaxis(unit, -1, -3)))
+
+
+def validate(model, loader, loss_func=None):
+    """The validation loop of SmplEstimatorSolver.train (:70-84): the mean over the loader's batches of loss_func(model(images), truth)
+    under no_grad, on the model's device.  The model is put into eval() mode for the loop and back afterwards (the reference never
+    leaves training mode, so its validation draws dropout masks and moves the running statistics; a validation loss should do
+    neither), so on the GPU every batch is one library call.  A model with two outputs is scored against columns 38 and 41 of the
+    69-vector truth (:79).  Returns a float (0.0 for an empty loader)."""
+    criterion = nn.MSELoss() if loss_func is None else loss_func
+    device = model.fc2.weight.device
+    two_angles = model.fc2.out_features == 2
+    total, batches, was_training = 0.0, 0, model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for images, truth in loader:
+                images, truth = images.to(device), truth.to(device)
+                if two_angles:
+                    truth = truth[:, [38, 41]]
+                total += float(criterion(model(images), truth))
+                batches += 1
+    finally:
+        model.train(was_training)
+    return total / max(batches, 1)

@@ -12,6 +12,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     ray_mesh_hits / vertex_sphere_warp   datasets/vertex_sphere_dataset.py:84-116 (trimesh's intersector) and :128-159 (the true warp)
     ray_mesh_first_hit                   render.py:222-319 (get_warp: the depth and the true warp of the single-sample model)
     ssim / image_scores util/scores.py:88-173 (ssim) and :11-48 (img2mse, img2psnr): the scores of print_scores, on the device
+    conv3x3_block       models/smpl_estimator.py:35-39: one conv - BatchNorm (eval) - ReLU - pool block of SmplEstimator, inference only
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -1029,3 +1030,31 @@ def image_scores(renders, truths, channels_first: bool = False, **ssim_kwargs):
         val = {'mean': torch.mean, 'sum': torch.sum}[reduction](val, dim=0)
     mse = sqerr.double().sum() / x.numel()
     return {"mse": mse, "psnr": -10. * torch.log(mse) / math.log(10.), "ssim": val}
+
+
+# ------------------------------------------------------------------------------------------------
+# SmplEstimator's convolution block (csrc/conv_block.hip); the network itself: estimator.py
+# ------------------------------------------------------------------------------------------------
+def conv3x3_block(x, weight, scale, shift, relu: bool = True, pool: bool = False):
+    """y = [maxpool2x2](relu(scale[co] * conv3x3_pad1(x, weight)[co] + shift[co])) in one launch: x [N,Ci,H,W], weight [Co,Ci,3,3],
+    scale, shift [Co] (an eval-mode BatchNorm2d and the convolution's bias folded: estimator.fold_bn) -> [N,Co,H,W], or
+    [N,Co,H//2,W//2] with pool (odd extents floor as nn.MaxPool2d(2, 2)).  fp32 GPU tensors, made contiguous.  Forward only: while
+    grad mode is enabled an input that requires grad is refused (no graph could be recorded through this op); under torch.no_grad()
+    such a tensor passes, so a module hands its Parameters over as they are."""
+    for nm, t in (("x", x), ("weight", weight), ("scale", scale), ("shift", shift)):
+        _need_cuda(nm, t)
+        if t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"conv3x3_block: `{nm}` requires grad, but this op is inference only: the training kernels of the "
+                               "convolution block (weight gradient, pool / ReLU / BatchNorm backward) do not exist yet")
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[1:]) != (x.shape[1], 3, 3):
+        raise RuntimeError(f"conv3x3_block: x must be [N,Ci,H,W] and weight [Co,Ci,3,3], got {tuple(x.shape)} and {tuple(weight.shape)}")
+    N, Ci, H, W = x.shape
+    Co = weight.shape[0]
+    if tuple(scale.shape) != (Co,) or tuple(shift.shape) != (Co,):
+        raise RuntimeError(f"conv3x3_block: scale and shift must be [{Co}], got {tuple(scale.shape)} and {tuple(shift.shape)}")
+    x, weight, scale, shift = (t.detach().contiguous() for t in (x, weight, scale, shift))
+    y = torch.empty((N, Co, H // 2, W // 2) if pool else (N, Co, H, W), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device), _lib.timed(f"conv3x3_block[{Ci}->{Co},{H}x{W}]"):
+        check(_lib.load().snerf_conv3x3_block_f32(ptr(x), N, Ci, H, W, ptr(weight), ptr(scale), ptr(shift), Co, int(bool(relu)),
+                                                  int(bool(pool)), ptr(y), current_stream()), "snerf_conv3x3_block_f32")
+    return y
