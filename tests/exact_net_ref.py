@@ -21,7 +21,11 @@ parameter gradient, every input-row gradient - and a pre-activation of exactly 0
   * the inference cases of tests/test_gpu_mlp_infer_exact.py (second half of this file): the same networks through the no-grad
     entries - infer_data() / infer_reference() / infer_preconditions(), the composed maps of the inference stream restated
     (composed_maps()), big_rows() for large calls, the launch rule of the latency kernels (launch_form()) and the operand split of the
-    split-precision kernels (split_parts()) restated; their record is profiles/mlp_infer_exact_cases.txt.
+    split-precision kernels (split_parts()) restated; their record is profiles/mlp_infer_exact_cases.txt;
+  * the cases of tests/test_gpu_mlp_split_exact.py (third part of this file): nets with a "rich" layer whose weights need the further
+    parts of a split mode - rich_data() / rich_reference(), the weight split and the wgrad scales restated (weight_parts(),
+    operand_parts()), split_emulate(): the sum over a mode's terms of the restated parts for every GEMM of a training step, and
+    rich_premises(): the conditions under which that sum is the float64 sum; their record is profiles/mlp_split_exact_cases.txt.
 """
 import functools
 import os
@@ -830,9 +834,507 @@ def infer_profile_text():
             describe(WARP_FUSED_FOLD) + "\n")
 
 
+# ================================================================================================ split precision: the low parts
+# The cases of tests/test_gpu_mlp_split_exact.py.  In every case above a weight is +-1 - its own first part - so weight parts 1 and 2 of
+# every stream are zeros, and in the training cases every operand is.  Here one layer l* of a net is "rich": its non-zero weights are
+# +-q, q a constant that needs the mode's further parts (RICH_Q), and inputs / output gradients may be multiples of a two-part constant
+# (TWO_PART_Q).  Every other layer is a signed selection - one +-1 per row, every input column used by about as many rows as any other
+# (the 1- and 3-row heads: HEAD_ENTRIES per row) - so values do not grow on the way forward or back.  A weight gradient sums over the
+# samples: with a q of 18 bits (or 257 x 257) it is q times a sum that has to stay below 2^24 / q = 127 (254), so in those families
+# only every g_every-th sample has a non-zero output gradient.  Every sum of absolute part-products then stays below 2^24
+# (rich_premises()).  Width 256, the fused entry with PositionalEncoder(0, True) twice, as SPLIT_FIRST / SPLIT_LAST.
+#
+# Restated from the kernels (smpl_nerf_amd/csrc), not guessed:
+#   TERMS                  mlp_bf16_device.h: Terms<2>, Terms<3> - (A part, B part) of the products a mode forms.  Forward and dgrad
+#                          (mlp_bf16.hip, mlp_train_bf16.hip: mlp_bwd_bf16_kernel): A = the weights, B = the layer input / d Y;
+#                          wgrad (mlp_wgrad_bf16_kernel, mlp_wgrad_f16_kernel, mlp_wgrad_direct_f16_kernel): A = d Y, B = X;
+#   weight_parts()         mlp_pack_bf16_kernel / mlp_pack_t_bf16_kernel: bf16 parts by round-to-nearest-even; f16x3: the whole layer
+#                          times 2^we, we = min(14 - exponent of its largest |w|, 50) (layer_weight_exp), then two fp16 parts, both by
+#                          round-to-nearest-even (the pack kernels cast; only the OPERANDS are truncated);
+#   split_parts(a, mode)   forward and dgrad operands: per sample, operand_scale16(sample_exp16(..)) with the cap where input columns
+#                          enter (kx_pos, KX_PE) - on integers min(14 - e, cap) is 14 - exponent of max(largest |value| of the row, 1)
+#                          in the forward (cap 64) and in the dgrad (cap 40) alike;
+#   split_parts(a, mode, stat_exp)   wgrad operands: bf16 parts of X and d Y as they are; f16x3: times 2^(14 - stat_exp), stat_exp
+#                          the exponent of the largest value over ALL samples (wgrad_f16_scales; wgrad_stat_exps(): the hidden input
+#                          of the layer, max(1, largest |position|) for position columns - layer 0 has no hidden input and reads that
+#                          one too - 0 for direction columns, the largest |d Y_l|), clamped to +-100;
+#   wgrad_is_wide()        mlp_wgrad_jobs.h: wgrad_wide - at least 8 output tiles and 16 input k-blocks of 16 columns.  In the bf16 modes
+#                          the narrow jobs run the fp32 kernels (launch_wgrad), in f16x3 the two-part direct kernel; nothing is folded;
+#   the sigma head's share of d o is an fp32 product of fp32 values in every mode (mlp_bwd_bf16_kernel: the aux block).
+TERMS = {2: ((1, 0), (0, 1), (0, 0)), 3: ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0))}
+# q of the rich layer.  Three bf16 parts: 131329 = 2^17 + 2^8 + 1 is the smallest integer that has three under round-to-nearest-even.
+# 65793 = 2^16 + 2^8 + 1 - the constant first proposed for these cases - has two, 66048 - 255 (the remainder 257 is above half a unit of
+# 512; below 2^17 at most 256 is left behind the first part, which fits 8 bits): it is kept as a family of its own, W65793, whose second
+# part is negative.
+RICH_Q = {"bf16x3": 257, "bf16x6": 131329, "f16x3": 2049}         # 256 + 1; 131072 + 256 + 1; 2048 + 1
+TWO_PART_Q = {"bf16x3": 257, "bf16x6": 257, "f16x3": 2049}
+HEAD_ENTRIES = 16
+RichCase = namedtuple("RichCase", "name mode family net rich q x_mult g_mult g_every")
+RichWarpCase = namedtuple("RichWarpCase", "name mode family warp rich q x_mult")
+
+
+def _selection(rng, n_out, n_in, width, k):
+    """[n_out, k] column indices, distinct within a row: consecutive runs of k of a cyclic order of the columns - the columns behind
+    the hidden ones (the input columns of a skip layer, the directions) first, then the hidden ones at random - dealt to the rows at random"""
+    hidden = min(width, n_in)
+    pool = np.resize(np.concatenate([np.arange(hidden, n_in), rng.permutation(hidden)]), n_out * k).reshape(n_out, k)
+    return pool[rng.permutation(n_out)]
+
+
+def _rich_layer(rng, name, n_out, a, width, q, relu):
+    """(weight, bias) of one layer for the input a [n, n_in] (float64) it will see.
+      a selection layer: one +-1 per row; where a ReLU follows, the pre-activation is a - min(a) or max(a) - a over the rows of the
+        selected column a: exactly zero (inactive) where a is at that end and active elsewhere, so a feature is two-sided wherever its
+        column varies, values do not grow, and a multiple of a two- or three-part constant stays one; elsewhere the bias is in 0 .. 2;
+      a head (1 or 3 rows): HEAD_ENTRIES entries per row;
+      the rich layer (q > 1): two entries per row, (+q, -q) with a bias in 0 .. 2 where a ReLU follows - a feature that is active on
+        every row or on none gets its two columns drawn again, up to 256 times - the heads HEAD_ENTRIES entries +-q."""
+    n_in, head = a.shape[1], n_out <= 3
+    k = min(n_in, HEAD_ENTRIES if head else 2 if q > 1 else 1)
+    cols = _selection(rng, n_out, n_in, width, k)
+    signs = np.where(rng.random((n_out, k)) < 0.5, 1.0, -1.0)
+    bias = rng.integers(0, 3, n_out).astype(np.float64)
+    if relu and q > 1:
+        signs = np.tile([1.0, -1.0], (n_out, 1))
+        for f in range(n_out):
+            for _ in range(256):
+                z = q * (a[:, cols[f, 0]] - a[:, cols[f, 1]]) + bias[f]
+                if (z > 0).any() and (z <= 0).any():
+                    break
+                cols[f] = rng.choice(n_in, 2, replace=False)
+    elif relu:
+        sel = a[:, cols[:, 0]]
+        bias = -signs[:, 0] * np.where(signs[:, 0] > 0, sel.min(0), sel.max(0))
+    w = np.zeros((n_out, n_in), F32)
+    w[np.arange(n_out)[:, None], cols] = signs * q
+    return w, bias.astype(F32)
+
+
+def _rich_state(rng, net, rich, q, rows):
+    """the layers in forward order, each made for the input the ones before it give on `rows` (float64)"""
+    W, nh = net.width, net.n_layers - 1
+    pp, dd = rows[:, :3], rows[:, 3:]
+    state, out = {}, {}
+
+    def make(name, n_out, a, relu):
+        w, b = _rich_layer(rng, name, n_out, a, W, q if name == rich else 1, relu)
+        state[name + ".weight"], state[name + ".bias"] = w, b
+        z = a @ w.astype(np.float64).T + b
+        return np.maximum(z, 0.0) if relu else z
+    h = make("positions_pose_input", W, pp, True)
+    for i in range(nh):
+        h = make(f"positional_net.{i}", W, np.concatenate([h, pp], 1) if i in net.skips else h, True)
+    o = make("additional_linear_layer", W, h, False)
+    make("sigma_out_layer", 1, o, False)
+    h1 = make("directional_input", W // 2, np.concatenate([o, dd], 1), False)
+    h2 = make("directional_net.0", W // 2, h1, True)
+    make("rgb_out_layer", 3, h2, False)
+    return {k + s: state[k + s] for k, _, _ in render_net_shapes(*net[1:8]) for s in (".weight", ".bias")}
+
+
+@functools.lru_cache(maxsize=None)
+def rich_data(case):
+    """(state dict, inputs {"x" [n, 3], "d" [n, 3], "add": None}, rows [n, 6], d_raw [n, 4]): positions in -1 .. 1 times x_mult,
+    directions s e_i (one ray per sample), output gradients in -1 .. 1 times g_mult on every g_every-th sample and zero on the others"""
+    net = case.net
+    shapes = render_net_shapes(*net[1:8])
+    rich = [n for n, _, _ in shapes].index(case.rich) if case.rich else 99
+    rng = np.random.default_rng([net.seed, net.n_layers, net.n, rich, case.q, case.x_mult, case.g_mult, case.g_every, 23])
+    n = net.n
+    x = (case.x_mult * rng.integers(-1, 2, (n, 3))).astype(F32)
+    d = np.zeros((n, 3), F32)
+    d[np.arange(n), rng.integers(0, 3, n)] = rng.choice([-4.0, -2.0, -1.0, 1.0, 2.0, 4.0], n)
+    rows = np.concatenate([x, np.sign(d)], 1).astype(F32)
+    d_raw = (case.g_mult * rng.integers(-1, 2, (n, 4))).astype(F32)
+    d_raw[np.arange(n) % case.g_every != case.g_every // 2] = 0
+    state = _rich_state(rng, net, case.rich, case.q, rows.astype(np.float64))
+    return state, {"x": x, "d": d, "add": None}, rows, d_raw
+
+
+@functools.lru_cache(maxsize=None)
+def rich_reference(case):
+    """float64: raw, parameter gradients of loss = sum(raw * d_raw) from torch_ref.render_ray_net under autograd, and the layers"""
+    net = case.net
+    state, _, rows, d_raw = rich_data(case)
+    P = {k: torch.from_numpy(v).double().requires_grad_() for k, v in state.items()}
+    x = torch.from_numpy(rows).double()
+    raw = R.render_ray_net(P, x, **{k: (tuple(v) if k == "skips" else v) for k, v in net_kw(net).items() if k != "width"})
+    (raw * torch.from_numpy(d_raw).double()).sum().backward()
+    grads = {k: v.grad.numpy() for k, v in P.items()}
+    raw_np, layers, d_rows, abs_rows = _render_layers(net, _f64(state), rows.astype(np.float64), d_raw.astype(np.float64))
+    assert np.array_equal(raw_np, raw.detach().numpy())
+    for l in layers:
+        assert np.array_equal(l.dw, grads[l.name + ".weight"]) and np.array_equal(l.db, grads[l.name + ".bias"]), l.name
+    return Reference(raw.detach().numpy(), grads, d_rows, layers, {})
+
+
+def _exponent(v):
+    """floor(log2 v) of the largest |entry| of v, or None if v is all zeros"""
+    top = float(np.abs(v).max()) if np.size(v) else 0.0
+    return int(np.frexp(top)[1]) - 1 if top > 0 else None
+
+
+def weight_parts(w, mode):
+    """the parts of a whole layer's weights w [n_out, n_in] as the pack kernels form them, float64 in w's own scale"""
+    ns, fmt = SPLIT_MODES[mode]
+    w = np.asarray(w, np.float64)
+    rest = w.astype(F32)
+    assert np.array_equal(rest.astype(np.float64), w)
+    if fmt == "bf16":
+        parts = []
+        for _ in range(ns):
+            p = _bf16_rne(rest)
+            parts.append(p.astype(np.float64))
+            rest = (rest - p).astype(F32)
+        return parts
+    e = _exponent(w)
+    we = 0 if e is None else min(14 - e, 50)
+    ws = (w * 2.0 ** we).astype(F32)
+    assert np.array_equal(ws.astype(np.float64), w * 2.0 ** we) and np.abs(ws).max() < 65520
+    h0 = ws.astype(np.float16).astype(F32)                   # (numpy casts to fp16 by round-to-nearest-even, as the pack kernels do)
+    h1 = (ws - h0).astype(F32).astype(np.float16).astype(F32)
+    return [h0.astype(np.float64) / 2.0 ** we, h1.astype(np.float64) / 2.0 ** we]
+
+
+def operand_parts(a, mode, stat_exp=None):
+    """split_parts() with the wgrad's scale: f16x3 and stat_exp given - the exponent of the job's largest value over all samples, None
+    if there is none (the statistic is then never raised: clamped to -100) - one scale 2^(14 - stat_exp) for every sample"""
+    ns, fmt = SPLIT_MODES[mode]
+    if fmt == "bf16" or stat_exp is None:
+        return split_parts(a, mode)
+    a = np.asarray(a, np.float64)
+    scale = 2.0 ** (14 - min(max(stat_exp, -100), 100))
+    rest, parts = (a * scale).astype(F32), []
+    assert np.array_equal(rest.astype(np.float64), a * scale)
+    for _ in range(ns):
+        p = _f16_rtz(rest)
+        parts.append(p.astype(np.float64) / scale)
+        rest = (rest - p).astype(F32)
+    return parts
+
+
+def wgrad_is_wide(n_out, n_cols):
+    return -(-n_out // 16) >= 8 and -(-n_cols // 16) >= 16
+
+
+class _Emulation:
+    """the GEMMs of one forward + backward in float64, each the sum over the mode's terms of the restated parts; drop = (kind, term)
+    leaves that term out of every GEMM of that kind ("fwd", "dgrad", "wgrad").  self.gemms records every GEMM for premises()."""
+
+    def __init__(self, mode, drop=None):
+        self.mode, self.ns, self.drop, self.gemms = mode, SPLIT_MODES[mode][0], drop, []
+
+    def split(self, kind, layer, A, B, Ap, Bp, bias=None, job=None):
+        """sum over the terms of A_i B_j^T, A [m, k] (weights; d Y^T in the wgrad), B [p, k] -> [m, p]"""
+        out = sum(Ap[i] @ Bp[j].T for i, j in TERMS[self.ns] if self.drop != (kind, (i, j)))
+        self.gemms.append(dict(kind=kind, layer=layer, job=job, split=True, A=A, B=B, Ap=Ap, Bp=Bp, bias=bias))
+        return out if not np.isscalar(out) else np.zeros((A.shape[0], B.shape[0]))
+
+    def fp32(self, kind, layer, A, B, bias=None, job=None):
+        """a GEMM the mode leaves to fp32 arithmetic: one product per term"""
+        self.gemms.append(dict(kind=kind, layer=layer, job=job, split=False, A=A, B=B, Ap=[A], Bp=[B], bias=bias))
+        return A @ B.T
+
+
+def _as_fp32(what, v):
+    assert np.array_equal(v.astype(F32).astype(np.float64), v) and np.abs(v).max(initial=0) < INT_LIMIT, f"{what}: not an fp32 integer"
+    return v
+
+
+def split_emulate(case, mode, drop=None):
+    """What the split kernels of `mode` compute on the case, if the restatement above is theirs: (raw, parameter gradients by
+    state-dict name, the emulation with its GEMMs).  Every accumulator is checked to be an integer fp32 holds."""
+    net = case.net
+    state, _, rows, d_raw = rich_data(case)
+    P, x, g_raw = _f64(state), rows.astype(np.float64), d_raw.astype(np.float64)
+    W, nh, fmt = net.width, net.n_layers - 1, SPLIT_MODES[mode][1]
+    pp, dd = x[:, :3], x[:, 3:]
+    E = _Emulation(mode, drop)
+    wp = {name: weight_parts(P[name + ".weight"], mode) for name, _, _ in render_net_shapes(*net[1:8])}
+    relu = lambda z: np.maximum(z, 0.0)
+    saved = {}                                               # name -> (layer input, pre-activation)
+
+    def fwd(name, a):
+        z = _as_fp32(name, E.split("fwd", name, P[name + ".weight"], a, wp[name], split_parts(a, mode), P[name + ".bias"]).T +
+                     P[name + ".bias"])
+        saved[name] = (a, z)
+        return z
+    h = relu(fwd("positions_pose_input", pp))
+    for i in range(nh):
+        h = relu(fwd(f"positional_net.{i}", np.concatenate([h, pp], 1) if i in net.skips else h))
+    o = fwd("additional_linear_layer", h)
+    sigma = fwd("sigma_out_layer", o)
+    h1 = fwd("directional_input", np.concatenate([o, dd], 1))
+    h2 = relu(fwd("directional_net.0", h1))
+    raw = np.concatenate([fwd("rgb_out_layer", h2), sigma], 1)
+
+    def dgrad(name, dz):                                     # d (hidden input) = d Y W[:, :W]
+        Wt = P[name + ".weight"][:, :W].T
+        return _as_fp32("d " + name, E.split("dgrad", name, Wt, dz, [p[:, :W].T for p in wp[name]], split_parts(dz, mode)).T)
+    dY = {"rgb_out_layer": g_raw[:, :3], "sigma_out_layer": g_raw[:, 3:]}
+    dY["directional_net.0"] = np.where(saved["directional_net.0"][1] > 0, dgrad("rgb_out_layer", dY["rgb_out_layer"]), 0.0)
+    dY["directional_input"] = dgrad("directional_net.0", dY["directional_net.0"])
+    dY["additional_linear_layer"] = _as_fp32("d o", dgrad("directional_input", dY["directional_input"]) + E.fp32(
+        "dgrad", "sigma_out_layer", P["sigma_out_layer.weight"].T, dY["sigma_out_layer"]).T)
+    g = dgrad("additional_linear_layer", dY["additional_linear_layer"])
+    for i in range(nh - 1, -1, -1):
+        dY[f"positional_net.{i}"] = np.where(saved[f"positional_net.{i}"][1] > 0, g, 0.0)
+        g = dgrad(f"positional_net.{i}", dY[f"positional_net.{i}"])
+    dY["positions_pose_input"] = np.where(saved["positions_pose_input"][1] > 0, g, 0.0)
+
+    grads = {}
+    for name, n_out, n_in in render_net_shapes(*net[1:8]):
+        a, dz = saved[name][0], dY[name]
+        dw = np.zeros((n_out, n_in))
+        if name == "positions_pose_input":
+            segs = [(0, n_in, "pos")]
+        elif n_in > W:                                       # a skip layer, directional_input: the input columns are a pair of their own
+            segs = [(0, W, "hidden"), (W, n_in, "dir" if name == "directional_input" else "pos")]
+        else:
+            segs = [(0, n_in, "hidden")]
+        for c0, c1, typ in segs:
+            job = "wide" if wgrad_is_wide(n_out, c1 - c0) else "narrow"
+            if fmt == "bf16" and job == "narrow":
+                dw[:, c0:c1] = E.fp32("wgrad", name, dz.T, a[:, c0:c1].T, job=job)
+                continue
+            ex = {"hidden": _exponent(a[:, c0:c1]), "pos": _exponent(np.maximum(np.abs(pp), 1.0)), "dir": 0}[typ]
+            ex, ey = (-100 if ex is None else ex), (-100 if _exponent(dz) is None else _exponent(dz))
+            dw[:, c0:c1] = E.split("wgrad", name, dz.T, a[:, c0:c1].T, [p.T for p in operand_parts(dz, mode, ey)],
+                                   [p.T for p in operand_parts(a[:, c0:c1], mode, ex)], job=job)
+        E.fp32("bias", name, np.ones((1, dz.shape[0])), dz.T)
+        grads[name + ".weight"], grads[name + ".bias"] = _as_fp32("d " + name + ".weight", dw), _as_fp32("d " + name + ".bias", dz.sum(0))
+    return raw, grads, E
+
+
+def _gemm_figures(gemms, ns, rich):
+    """(a), (b), (c) over recorded GEMMs: figures as rich_premises() returns them"""
+    m = dict(max_operand=0.0, max_abs_sum=0.0, last_a=[0, 0], last_b=[0, 0], covered=set(), exact=True, outside=0)
+    for g in gemms:
+        A, B, Ap, Bp = g["A"], g["B"], g["Ap"], g["Bp"]
+        m["max_operand"] = max(m["max_operand"], float(np.abs(A).max(initial=0)), float(np.abs(B).max(initial=0)))
+        total = np.abs(g["bias"])[:, None] if g["bias"] is not None else 0.0
+        if not g["split"]:
+            m["max_abs_sum"] = max(m["max_abs_sum"], float((np.abs(A) @ np.abs(B).T + total).max()))
+            continue
+        m["exact"] = m["exact"] and np.array_equal(sum(Ap), A) and np.array_equal(sum(Bp), B) and \
+            all(np.array_equal(p, np.rint(p)) for p in Ap + Bp)
+        for key, parts, full in (("last_a", Ap, A), ("last_b", Bp, B)):
+            m[key][0] += int((parts[-1] != 0).sum())
+            m[key][1] += int((full != 0).sum())
+        any_a, any_b = [p.any() for p in Ap], [p.any() for p in Bp]
+        where = "l*" if g["layer"] == rich else "elsewhere"
+        for i in range(ns):
+            for j in range(ns):
+                if not (any_a[i] and any_b[j]):
+                    continue
+                prod = np.abs(Ap[i]) @ np.abs(Bp[j]).T
+                if not prod.any():
+                    continue
+                if (i, j) in TERMS[ns]:
+                    total = total + prod
+                    m["covered"].add((g["kind"], g["job"], where, (i, j)))
+                else:
+                    m["outside"] += 1
+        m["max_abs_sum"] = max(m["max_abs_sum"], float(np.max(total)))
+    m["last_a"], m["last_b"] = (v[0] / max(v[1], 1) for v in (m["last_a"], m["last_b"]))
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def rich_premises(case, mode=None):
+    """Conditions (a) - (e) of the split-precision cases, on the float64 reference alone: the emulation's GEMMs are evaluated with no
+    term dropped, and every operand of every GEMM must be the reference's own (so nothing below depends on an emulated value).
+      (a) every operand of a split GEMM recombines exactly from the parts the mode keeps, and every part is an integer;
+      (b) every product (A part i) x (B part j) outside the mode's term table is zero;
+      (c) the sum of the absolute part-products (and the bias) of every output element is below 2^24 - the parts are integers, so
+          the lowest set bit among the terms is at least 1 and this is the stricter form of the bound;
+      (e) a ReLU pre-activation is exactly zero somewhere, and every feature of a rich ReLU layer is active on some row and inactive
+          on another.
+    Returns the figures: largest operand, share of non-zero last parts on either side over the split GEMMs, the largest sum of (c), the
+    terms with a non-zero product as (kind, wgrad job, at the rich layer or elsewhere, term), and whether the sum over the kept terms of the
+    restated parts is the float64 reference (the first half of (f))."""
+    mode = mode or case.mode
+    if isinstance(case, RichWarpCase):
+        raw, E, ref = warp_split_emulate(case)
+        m = _gemm_figures(E.gemms, 3, case.rich)
+        z1 = ref["z1"]
+        m["zero_preacts"] = int((z1 == 0).sum())
+        m["one_sided"] = int(((z1 > 0).all(0) | ~(z1 > 0).any(0)).sum()) if case.rich == "linear1" else 0
+        m["emulation_is_float64"] = bool(all(np.array_equal(raw[k], ref[k]) for k in raw))
+        m["max_abs_sum"] = max(m["max_abs_sum"], ref["abs_sdirs"])
+        return m
+    ref = rich_reference(case)
+    raw, grads, E = split_emulate(case, mode)
+    by_name, W = {l.name: l for l in ref.layers}, case.net.width
+    for g in E.gemms:
+        l, A, B = by_name[g["layer"]], g["A"], g["B"]
+        if g["kind"] == "fwd":
+            assert np.array_equal(A, l.w) and np.array_equal(B, l.a), (case.name, g["layer"], "forward operands")
+        elif g["kind"] == "dgrad":
+            assert np.array_equal(A, l.w[:, :W].T) and np.array_equal(B, l.dz), (case.name, g["layer"], "dgrad operands")
+        else:
+            assert np.array_equal(A if g["kind"] == "wgrad" else B, l.dz.T), (case.name, g["layer"], "wgrad operands")
+    m = _gemm_figures(E.gemms, SPLIT_MODES[mode][0], case.rich)
+    m["zero_preacts"], m["one_sided"] = 0, 0
+    for l in ref.layers:
+        if l.relu:
+            m["zero_preacts"] += int((l.z == 0).sum())
+            if l.name == case.rich:
+                on = l.z > 0
+                m["one_sided"] = int((on.all(0) | ~on.any(0)).sum())
+    m["emulation_is_float64"] = bool(np.array_equal(raw, ref.out) and all(np.array_equal(grads[k], ref.grads[k]) for k in ref.grads))
+    return m
+
+
+# ---- the warp net's split forward (warp_bf16.hip: always three bf16 parts, no scaling): linear1 on [x | pose of the ray], linear2
+@functools.lru_cache(maxsize=None)
+def rich_warp_data(case):
+    """(state dict, (x [n, 3], pose [rays, row_len - 3], o [rays, 3])): integers in -1 .. 1, x and pose times x_mult"""
+    wc = case.warp
+    rich = {"linear1": 1, "linear2": 2}[case.rich]
+    rng = np.random.default_rng([wc.seed, wc.row_len, wc.n, rich, case.q, case.x_mult, 29])
+    rays = wc.n // wc.spr
+    x = (case.x_mult * rng.integers(-1, 2, (wc.n, 3))).astype(F32)
+    pose = (case.x_mult * rng.integers(-1, 2, (rays, wc.row_len - 3))).astype(F32)
+    o = rng.integers(-1, 2, (rays, 3)).astype(F32)
+    rows = np.concatenate([x, np.repeat(pose, wc.spr, 0)], 1).astype(np.float64)
+    w1, b1 = _rich_layer(rng, "linear1", wc.width, rows, wc.row_len, case.q if rich == 1 else 1, True)
+    h = np.maximum(rows @ w1.astype(np.float64).T + b1, 0.0)
+    w2, b2 = _rich_layer(rng, "linear2", 3, h, wc.width, case.q if rich == 2 else 1, False)
+    return {"linear1.weight": w1, "linear1.bias": b1, "linear2.weight": w2, "linear2.bias": b2}, (x, pose, o)
+
+
+def warp_split_emulate(case, ns=3, drop=None):
+    """({warp, warped, sdirs} of the emulation with ns bf16 parts, the emulation, the float64 reference with z1 and abs_sdirs)"""
+    wc, mode = case.warp, {3: "bf16x6", 2: "bf16x3"}[ns]
+    state, (x, pose, o) = rich_warp_data(case)
+    P = _f64(state)
+    x64, o64 = x.astype(np.float64), np.repeat(o, wc.spr, 0).astype(np.float64)
+    rows = np.concatenate([x64, np.repeat(pose, wc.spr, 0).astype(np.float64)], 1)
+    E = _Emulation(mode, drop)
+    out = {}
+    a = rows
+    for name in ("linear1", "linear2"):
+        z = _as_fp32(name, E.split("fwd", name, P[name + ".weight"], a, weight_parts(P[name + ".weight"], mode), split_parts(a, mode),
+                                   P[name + ".bias"]).T + P[name + ".bias"])
+        a = np.maximum(z, 0.0)
+    out["warp"] = z
+    out["warped"] = _as_fp32("warped", x64 + z)
+    out["sdirs"] = _as_fp32("sdirs", out["warped"] - o64)
+    z1 = rows @ P["linear1.weight"].T + P["linear1.bias"]
+    warp = np.maximum(z1, 0.0) @ P["linear2.weight"].T + P["linear2.bias"]
+    ref = dict(warp=warp, warped=x64 + warp, sdirs=x64 + warp - o64, z1=z1,
+               abs_sdirs=float((np.abs(x64) + np.abs(np.maximum(z1, 0.0)) @ np.abs(P["linear2.weight"]).T + np.abs(P["linear2.bias"]) +
+                                np.abs(o64)).max()))
+    return out, E, ref
+
+
+def assert_rich_premises(case):
+    m = rich_premises(case)
+    assert m["exact"], (case.name, "(a): an operand does not recombine from the parts the mode keeps")
+    assert m["outside"] == 0, (case.name, "(b): a product outside the mode's term table is non-zero", m["outside"])
+    assert m["max_abs_sum"] < INT_LIMIT, (case.name, "(c)", m["max_abs_sum"])
+    assert m["zero_preacts"] >= 1 and m["one_sided"] == 0, (case.name, "(e)", m["zero_preacts"], m["one_sided"])
+    assert m["emulation_is_float64"], (case.name, "(f): the sum over the kept terms is not the float64 reference")
+    return m
+
+
+# (d) the terms a family is named for.  RICH_AT_LSTAR: non-zero in the GEMM of the rich layer itself, in every case of the family
+# (positions_pose_input has no dgrad: no input gradients here).  rich_over_sweep(): non-zero in some case of the family's sweep, as
+# (kind, wgrad job, term); the narrow wgrad jobs are split in f16x3 only (in the bf16 modes they run the fp32 kernels).
+RICH_AT_LSTAR = {"W3": {"fwd": ((1, 0), (2, 0)), "dgrad": ((1, 0), (2, 0))}, "W65793": {"fwd": ((1, 0),), "dgrad": ((1, 0),)}, "W2X2": {"fwd": ((1, 1),)}, "W2G2": {"dgrad": ((1, 1),)},
+                 "W2": {"fwd": ((1, 0),), "dgrad": ((1, 0),)}}
+
+
+def rich_over_sweep(mode, family):
+    narrow = lambda *terms: [("wgrad", "narrow", t) for t in terms] if mode == "f16x3" else []
+    return {"W3": [("fwd", None, (0, 2)), ("dgrad", None, (0, 2)), ("wgrad", "wide", (1, 0)), ("wgrad", "wide", (2, 0)), ("wgrad", "wide", (0, 2))],
+            "W65793": [("fwd", None, (0, 1)), ("dgrad", None, (0, 1)), ("wgrad", "wide", (1, 0)), ("wgrad", "wide", (0, 1))],
+            "W2X2": [("wgrad", "wide", (1, 1))], "W2G2": [("wgrad", "wide", (1, 1))],
+            "G2X2": [("fwd", None, (0, 1)), ("dgrad", None, (0, 1)), ("wgrad", "wide", (1, 1))],
+            "W2": [("wgrad", "wide", (1, 0))] + narrow((1, 0)),
+            "X2": [("fwd", None, (0, 1)), ("wgrad", "wide", (0, 1))] + narrow((0, 1)),
+            "G2": [("dgrad", None, (0, 1)), ("wgrad", "wide", (1, 0))] + narrow((1, 0))}[family]
+
+
+# (f) the family in which the emulation must leave the float64 reference when (kind, term) is dropped from it
+RICH_SENSITIVE = {3: {("fwd", (1, 1)): "W2X2", ("dgrad", (1, 1)): "W2G2", ("wgrad", (1, 1)): "G2X2", ("fwd", (0, 1)): "G2X2",
+                      ("dgrad", (0, 1)): "G2X2", ("wgrad", (0, 1)): "G2X2"},
+                  2: {("fwd", (1, 0)): "W2", ("dgrad", (1, 0)): "W2", ("wgrad", (1, 0)): "G2", ("fwd", (0, 1)): "X2", ("dgrad", (0, 1)): "G2",
+                      ("wgrad", (0, 1)): "X2", ("fwd", (0, 0)): "W2", ("dgrad", (0, 0)): "W2", ("wgrad", (0, 0)): "W2"}}
+RICH_SENSITIVE[3].update({(kind, t): "W3" for kind in ("fwd", "dgrad", "wgrad") for t in ((2, 0), (1, 0), (0, 2), (0, 0))})
+
+
+def emulation_is_reference(case, mode, drop=None):
+    ref = rich_reference(case)
+    raw, grads, _ = split_emulate(case, mode, drop)
+    return bool(np.array_equal(raw, ref.out) and all(np.array_equal(grads[k], ref.grads[k]) for k in ref.grads))
+
+
+def _rich_net(n, n_layers=8, skips=(4,)):
+    return _net(f"rich-256x{n_layers}-n{n}", n, n_layers=n_layers, positions_dim=3, directions_dim=3, skips=skips)
+
+
+# l* over layers that land in different kernels or jobs: input columns (a narrow wgrad job), a hidden layer before the skip and the
+# skip layer (wide jobs, the concatenated operand), additional_linear_layer, directional_input (the hidden columns ride with the
+# direction columns and, in the dgrad, with the sigma head's row), directional_net.0 (the 128 x 128 narrow job), rgb_out_layer; n = 333
+# and 77 in turn.  And a 4-layer net with skip 1 whose rich layer is the skip layer.
+RICH_SWEEP = [("positions_pose_input", 333, 8), ("positional_net.1", 77, 8), ("positional_net.4", 333, 8),
+              ("additional_linear_layer", 77, 8), ("directional_input", 333, 8), ("directional_net.0", 77, 8), ("rgb_out_layer", 333, 8),
+              ("positional_net.1", 77, 4)]
+
+
+def _rich_case(mode, family, rich, n, n_layers, q=1, x_mult=1, g_mult=1, g_every=1):
+    net = _rich_net(n, n_layers, (4,) if n_layers == 8 else (1,))
+    name = f"{mode}-{family}-{rich or 'none'}-x{n_layers}-n{n}"
+    return RichCase(name, mode, family, net, rich, q if rich else 1, x_mult, g_mult, g_every)
+
+
+def _family(mode, family, sweep=RICH_SWEEP, **kw):
+    return [_rich_case(mode, family, rich, n, depth, **kw) for rich, n, depth in sweep]
+
+
+_NO_RICH = [(None, 77, 8), (None, 333, 8)]
+_SHORT = [RICH_SWEEP[1], RICH_SWEEP[4], RICH_SWEEP[5]]
+RICH_CASES = {
+    "bf16x6": _family("bf16x6", "W3", q=131329, g_every=16) + _family("bf16x6", "W65793", q=65793, g_every=16) + _family("bf16x6", "W2X2", q=257, x_mult=257, g_every=4) +
+    _family("bf16x6", "W2G2", _SHORT, q=257, g_mult=257, g_every=8) + _family("bf16x6", "G2X2", _NO_RICH, x_mult=257, g_mult=257, g_every=4),
+    "bf16x3": _family("bf16x3", "W2", q=257) + _family("bf16x3", "X2", _NO_RICH, x_mult=257) + _family("bf16x3", "G2", _NO_RICH, g_mult=257),
+    "f16x3": _family("f16x3", "W2", q=2049) + _family("f16x3", "X2", _NO_RICH, x_mult=2049) + _family("f16x3", "G2", _NO_RICH, g_mult=2049)}
+ALL_RICH_CASES = [c for mode in ("bf16x6", "bf16x3", "f16x3") for c in RICH_CASES[mode]]
+# teeth: these bf16x6 cases run with two parts lose the terms they are named for
+RICH_TEETH = [c for c in RICH_CASES["bf16x6"] if c.family in ("W3", "W2X2") and c.rich in ("positional_net.1", "directional_input")
+              and c.net.n_layers == 8]
+
+
+_RICH_WARP = _warp(256, 43, 332, spr=4)
+RICH_WARP_CASES = [RichWarpCase(f"warp-{family}-{rich}-n332-spr4", "bf16x6", family, _RICH_WARP, rich, q, x_mult)
+                   for family, q, x_mult in (("W3", 131329, 1), ("W2X2", 257, 257)) for rich in ("linear1", "linear2")]
+
+
+def describe_rich(case):
+    m = rich_premises(case)
+    cov = sorted({f"{k}{'/' + j if j else ''}@{w}:A{t[0]}B{t[1]}" for k, j, w, t in m["covered"] if t != (0, 0)})
+    return (f"{case.name:52s} max|operand| {m['max_operand']:9.0f}  non-zero last part A {m['last_a']:.5f} B {m['last_b']:.5f}  "
+            f"largest sum of |part products| {m['max_abs_sum']:9.0f} ({m['max_abs_sum'] / INT_LIMIT:.5f} of 2^24)  "
+            f"zero pre-activations {m['zero_preacts']}  terms: {' '.join(cov)}")
+
+
+SPLIT_PROFILE = os.path.join(ROOT, "profiles", "mlp_split_exact_cases.txt")
+SPLIT_PROFILE_HEAD = ("# tests/exact_net_ref.py: what the float64 reference of every case of tests/test_gpu_mlp_split_exact.py measures (CPU;\n"
+                      "# rewritten by `python tests/exact_net_ref.py`, compared by tests/test_exact_net_host.py).  terms: GEMM kind / wgrad job @\n"
+                      "# the rich layer l* or elsewhere : (A part, B part) with a non-zero product, part 0 x part 0 left out.\n")
+
+
+def split_profile_text():
+    return SPLIT_PROFILE_HEAD + "".join(describe_rich(c) + "\n" for c in ALL_RICH_CASES + RICH_WARP_CASES)
+
+
 if __name__ == "__main__":
     with open(PROFILE, "w") as f:
         f.write(profile_text())
     with open(INFER_PROFILE, "w") as f:
         f.write(infer_profile_text())
-    print(profile_text() + infer_profile_text())
+    with open(SPLIT_PROFILE, "w") as f:
+        f.write(split_profile_text())
+    print(profile_text() + infer_profile_text() + split_profile_text())

@@ -1,7 +1,9 @@
 """What tests/test_gpu_mlp_exact.py takes for granted, checked on the CPU (tests/exact_net_ref.py): every case meets the exactness bound
 and the coverage conditions on its float64 reference alone, a float32 torch run of the same network on the same data equals that
 reference entry for entry (an independent proof that the data is exact in fp32), the generator makes what it says, and the
-comparison names what the builder needs.  profiles/mlp_exact_cases.txt is the record of every case's headroom."""
+comparison names what the builder needs.  profiles/mlp_exact_cases.txt is the record of every case's headroom.  Likewise for the
+inference cases (tests/test_gpu_mlp_infer_exact.py) and for the split-precision cases whose low operand parts are not zero
+(tests/test_gpu_mlp_split_exact.py: premises (a) - (f) on the three training GEMMs, profiles/mlp_split_exact_cases.txt)."""
 import numpy as np
 import pytest
 import torch
@@ -293,6 +295,118 @@ def test_inference_profile_is_the_record_of_these_cases():
     names = [c.name for c in E.ALL_INFER_CASES]
     assert len(set(names)) == len(names)
     assert sorted({c.net.width for c in E.INFER_CASES}) == [64, 100, 128, 200, 256, 320, 384, 448, 512, 576]
+
+
+# ---- the split-precision cases with non-zero low parts of tests/test_gpu_mlp_split_exact.py -----------------------------------------------
+@pytest.mark.parametrize("case", E.ALL_RICH_CASES + E.RICH_WARP_CASES, ids=IDS)
+def test_low_part_premises_hold_on_the_float64_reference(case):
+    """(a) every operand of every split GEMM - forward, dgrad, wgrad per layer - recombines exactly from the parts the mode keeps;
+    (b) every product outside the mode's term table is zero; (c) every sum of absolute part-products is below 2^24; (e) a
+    pre-activation is exactly zero and every ReLU feature of the rich layer is two-sided; (f, first half) the sum over the kept terms
+    of the restated parts is the float64 reference; (d, per case) the terms the family is named for are non-zero in the rich layer's
+    own GEMMs.  No family had to be dropped for any l*."""
+    m = E.assert_rich_premises(case)
+    print(E.describe_rich(case))
+    for kind, terms in E.RICH_AT_LSTAR.get(case.family, {}).items():
+        if case.rich is None or (kind == "dgrad" and case.rich in ("positions_pose_input", "linear1", "linear2")):
+            continue
+        for t in terms:
+            assert (kind, None, "l*", t) in m["covered"], (case.name, kind, t)
+    if case.family in ("X2", "G2"):          # (two-part modes: the last part is the second)
+        assert m["last_a" if case.g_mult > 1 else "last_b"] > 0.25
+
+
+@pytest.mark.parametrize("mode", sorted(E.RICH_CASES))
+def test_low_part_families_reach_every_kind_of_gemm(mode):
+    """(d, over the sweep): forward, dgrad, wide wgrad jobs and - f16x3, where they are split - narrow wgrad jobs each see the term a family
+    is named for with a non-zero product; at least one wide-job and one narrow-job l* per family with a rich layer; n = 77 and 333"""
+    families = sorted({c.family for c in E.RICH_CASES[mode]})
+    assert families == {"bf16x6": ["G2X2", "W2G2", "W2X2", "W3", "W65793"]}.get(mode, ["G2", "W2", "X2"])
+    for family in families:
+        cases = [c for c in E.RICH_CASES[mode] if c.family == family]
+        covered = set().union(*[{(k, j, t) for k, j, _, t in E.rich_premises(c)["covered"]} for c in cases])
+        for want in E.rich_over_sweep(mode, family):
+            assert want in covered, (mode, family, want)
+        assert {c.net.n for c in cases} == {77, 333}
+        rich = {c.rich for c in cases}
+        assert rich == {None} or (rich & {"positional_net.1", "positional_net.4", "additional_linear_layer", "directional_input"} and
+                                  rich & {"positions_pose_input", "directional_net.0", "rgb_out_layer"})
+        assert all(c.q == {"W3": E.RICH_Q[mode], "W65793": 65793}.get(family, E.TWO_PART_Q[mode]) for c in cases if c.rich)
+    sweep = [c for c in E.RICH_CASES[mode] if c.family in ("W3", "W2")]
+    assert [(c.rich, c.net.n, c.net.n_layers) for c in sweep] == E.RICH_SWEEP
+    assert sweep[-1].net.skips == (1,) and sweep[-1].rich == "positional_net.1" and sweep[2].net.skips == (4,)
+
+
+@pytest.mark.parametrize("mode", sorted(E.RICH_CASES))
+def test_dropping_a_kept_term_leaves_the_float64_reference(mode):
+    """(f, second half): with any one kept term left out of the forward, the dgrad or the wgrad, the emulation differs from float64 in
+    a case of the family named for that term - a kernel that loses the term cannot pass the GPU test"""
+    ns = E.SPLIT_MODES[mode][0]
+    assert set(E.RICH_SENSITIVE[ns]) == {(kind, t) for kind in ("fwd", "dgrad", "wgrad") for t in E.TERMS[ns]}
+    for (kind, t), family in E.RICH_SENSITIVE[ns].items():
+        cases = [c for c in E.RICH_CASES[mode] if c.family == family]
+        assert any(not E.emulation_is_reference(c, mode, (kind, t)) for c in cases), (mode, kind, t, family)
+
+
+def test_the_restated_split_and_the_constants():
+    """257, 131329 and 2049 need every part of their mode under the pack kernels' rounding; 65793 = 65536 + 256 + 1 does NOT need three
+    bf16 parts under round-to-nearest-even (66048 - 255), and no integer below 2^17 does; the f16x3 weight exponent takes the largest
+    |w| of the layer to [2^14, 2^15); the term tables are those of mlp_bf16_device.h"""
+    parts = lambda q, mode: [float(p[0, 0]) for p in E.weight_parts(np.array([[q, -1.0]]), mode)]
+    assert parts(257, "bf16x3") == [256, 1] and parts(257, "bf16x6") == [256, 1, 0]
+    assert parts(131329, "bf16x6") == [131072, 256, 1] and parts(65793, "bf16x6") == [66048, -255, 0]
+    assert parts(2049, "f16x3") == [2048, 1] and parts(3 * 2049, "f16x3") == [6148, -1]          # (RNE on the weights: 6147 -> 6148)
+    rng = np.random.default_rng(0)
+    some = rng.integers(1, 2 ** 17, 4096).astype(np.float64)[None]
+    assert not E.weight_parts(some, "bf16x6")[2].any() and np.array_equal(sum(E.weight_parts(some, "bf16x6")), some)
+    w = np.array([[3.0, -2049.0, 0.0]])
+    p = E.weight_parts(w, "f16x3")
+    assert np.array_equal(sum(p), w) and np.array_equal(p[0] * 8, [[24.0, -16384.0, 0.0]])
+    assert [float(v[0, 0]) for v in E.operand_parts(np.array([[6147.0]]), "f16x3", 12)] == [6144, 3]        # (truncation on the operands)
+    assert [float(v[0, 0]) for v in E.split_parts(np.array([[6147.0, 9000.0]]), "f16x3")] == [6144, 3]
+    assert E.TERMS[2] == ((1, 0), (0, 1), (0, 0)) and E.TERMS[3] == ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0))
+    assert E.wgrad_is_wide(256, 256) and E.wgrad_is_wide(128, 256) and not E.wgrad_is_wide(128, 128) and not E.wgrad_is_wide(256, 3)
+    assert not E.wgrad_is_wide(1, 256) and not E.wgrad_is_wide(3, 128)
+
+
+def test_the_low_part_generator_makes_what_it_says():
+    case = E.RICH_CASES["bf16x6"][2]
+    state, inp, rows, d_raw = E.rich_data(case)
+    assert case.rich == "positional_net.4" and case.q == 131329 and case.g_every == 16
+    for name, n_out, n_in in E.render_net_shapes(*case.net[1:8]):
+        w, b = state[name + ".weight"], state[name + ".bias"]
+        assert w.shape == (n_out, n_in) and w.dtype == b.dtype == np.float32 and np.array_equal(b, np.rint(b))
+        per_row = (w != 0).sum(1)
+        assert (per_row == (E.HEAD_ENTRIES if n_out <= 3 else 2 if name == case.rich else 1)).all(), name
+        assert set(np.unique(np.abs(w))) == {0.0, float(case.q) if name == case.rich else 1.0}
+        used = (w != 0).sum(0)
+        assert n_out <= 3 or used.max() - used.min() <= (2 if name == case.rich else 1) or name == case.rich, name
+        assert n_in <= 256 or (w[:, 256:] != 0).any(0).all()          # the input columns of a skip layer / the directions are used
+    assert set(np.unique(inp["x"])) == {-1.0, 0.0, 1.0} and np.array_equal(rows[:, :3], inp["x"])
+    assert np.array_equal(rows[:, 3:], E.direction_premise(inp["d"]))
+    live = np.nonzero(d_raw.any(1))[0]
+    assert (live % 16 == 8).all() and len(live) >= 333 // 16 - 4 and set(np.unique(d_raw)) == {-1.0, 0.0, 1.0}
+    again = E.rich_data.__wrapped__(case)
+    assert all(np.array_equal(state[k], again[0][k]) for k in state) and np.array_equal(d_raw, again[3])
+    x2 = E.rich_data(E.RICH_CASES["f16x3"][9])
+    assert E.RICH_CASES["f16x3"][9].family == "X2" and set(np.unique(np.abs(x2[1]["x"]))) == {0.0, 2049.0}
+
+
+@pytest.mark.parametrize("case", E.RICH_TEETH, ids=IDS)
+def test_two_part_emulation_of_three_part_cases_leaves_float64(case):
+    """the cases of the GPU test's teeth: emulated with the parts and terms of bf16x3, raw differs from the float64 reference"""
+    assert case.mode == "bf16x6" and case.family in ("W3", "W2X2")
+    raw, _, _ = E.split_emulate(case, "bf16x3")
+    assert (raw != E.rich_reference(case).out).mean() > 0.1
+    assert {c.family for c in E.RICH_TEETH} == {"W3", "W2X2"}
+
+
+def test_split_profile_is_the_record_of_these_cases():
+    """profiles/mlp_split_exact_cases.txt holds what this run measures (rewrite it with `python tests/exact_net_ref.py`)"""
+    with open(E.SPLIT_PROFILE) as f:
+        assert f.read() == E.split_profile_text()
+    names = [c.name for c in E.ALL_RICH_CASES + E.RICH_WARP_CASES]
+    assert len(set(names)) == len(names)
 
 
 def test_profile_is_the_record_of_these_cases():

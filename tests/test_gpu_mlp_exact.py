@@ -20,7 +20,16 @@ Cases whose generator parameters differ from the default (4 non-zeros per weight
 above NET_DEFAULT - the single-sample net, the 64 x 16 net (3 per row, not 2) and the split-precision net (3 per row, not 2) miss a
 coverage condition on the reference otherwise.  No shape was replaced: the Python classes accept every one the cases name.  One
 case more than the shapes' list: the default net at n = 4111, where the wide and the narrow jobs are split into different numbers of
-chunks (test_default_net_with_two_chunk_counts_is_exact)."""
+chunks (test_default_net_with_two_chunk_counts_is_exact).
+
+Split precision: every weight of every case HERE is in {-1, 0, +1} and every operand of test_split_precision_backward_is_exact fits
+the first bf16 part, so this module holds only the products (part 0) x (part 0) of the split kernels.  The further parts - weight
+parts 1 and 2 of the streams of snerf_mlp_pack_bf16 / snerf_mlp_pack_t_bf16, the terms (A1,B0), (A2,B0), (A1,B1), (A0,B1), (A0,B2) of
+Terms<2> / Terms<3> in the training forward snerf_mlp_fwd_train_bf16_f32, the dgrad and the wide wgrad jobs, and the whole f16x3
+training path with its weight exponents, per-sample operand scales, layer statistics and job scales (wgrad_f16_scales,
+mlp_wgrad_f16_kernel, mlp_wgrad_direct_f16_kernel) - are held exactly by tests/test_gpu_mlp_split_exact.py.  Still held by tolerance
+only (tests/test_gpu_grad.py, test_gpu_round*.py): the split kernels on real-valued data, whose operands do not recombine from their
+parts and whose sums round; the sin / cos columns; snerf_mlp_bwd_inputs_bf16_f32."""
 import contextlib
 import os
 import subprocess
@@ -239,7 +248,8 @@ def test_split_precision_backward_is_exact(dev, nsplit):
     """snerf_mlp_bwd_bf16_f32 (stream from snerf_mlp_pack_t_bf16) on the `act` of the fp32 encoded training forward - a mix the header
     allows.  Every layer input and every d Y_l of the case is an integer of at most 255 (asserted on the reference), so it is its own
     first bf16 part, the further parts and every cross term are zero, and the fp32 accumulation is exact as before: flat_grad equals
-    float64 exactly with 3 parts and with 2.  (f16x3 needs the statistics of an f16x3 training forward: not here.)"""
+    float64 exactly with 3 parts and with 2.  (Operands with further parts, the split training forward and f16x3 with the statistics
+    of its own forward: tests/test_gpu_mlp_split_exact.py.)"""
     from smpl_nerf_amd import _lib, nets
     lib = _lib.load()
     case = E.NET_SPLIT

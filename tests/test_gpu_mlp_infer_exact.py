@@ -28,7 +28,12 @@ one-call render entries, which run these kernels behind expf and the sampler.
 
 Split precision: every mode forms the products (weight part 0) x (operand part s) for every s it keeps (mlp_bf16_device.h: Terms<2>,
 Terms<3>), and a weight of +-1 is its own part 0, so no mode drops a product these operands make non-zero: both cases run in all
-three modes."""
+three modes.  What the cases HERE hold exactly is therefore (A0,B0), (A0,B1) and (A0,B2) of snerf_mlp_fwd_bf16_f32 with the per-sample
+f16x3 operand scale, and (A0,B0) of snerf_warp_fwd_bf16_f32.  The weights' further parts - parts 1 and 2 of every slab of
+snerf_mlp_pack_bf16 / snerf_warp_pack_bf16, the f16x3 table of weight exponents above 2^14, the terms (A1,B0), (A2,B0), (A1,B1) of both
+inference kernels - are held exactly by tests/test_gpu_mlp_split_exact.py, which runs its rich-weight cases through these same no-grad
+entries.  Held by tolerance only (test_split_bf16_stress_against_fp32_kernel and the compose / weight-ring tests): real-valued
+operands, which do not recombine from their parts, and the sin / cos columns."""
 import os
 import subprocess
 import sys
