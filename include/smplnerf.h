@@ -682,6 +682,51 @@ SNERF_API int64_t snerf_smpl_estimator_workspace_bytes(int64_t N, int human_size
 SNERF_API int snerf_smpl_estimator_fwd_f32(const snerf_smpl_estimator *net, const float *images, int64_t N, float *out, void *workspace,
                               int64_t workspace_bytes, snerf_stream_t stream);
 
+/* ---- SmplEstimator, training: the block with batch statistics and its backward (csrc/conv_train.hip) --------------------------
+ *   z = conv3x3_pad1(x, w) + b              snerf_conv3x3_block_f32 with scale = 1, shift = b, relu = pool = 0 (x 1 is exact)
+ *   mean, invstd                            snerf_bn_stats_f32: per channel over M = N H W values, biased variance
+ *   y = [maxpool2x2](relu(pre))             snerf_bn_relu_pool_fwd_f32: xhat = (z - mean) invstd, pre = xhat gamma + beta, each
+ *                                           operation rounded to fp32; odd extents floor as in the block above
+ *   dz, dgamma, dbeta from dy               snerf_bn_relu_pool_bwd_f32: g = dy routed through the pool (the FIRST maximum of a
+ *                                           window in the order (0,0), (0,1), (1,0), (1,1); pixels in no window get 0) and the
+ *                                           ReLU (0 where pre <= 0), both recomputed from z; dbeta = s1 = sum g, dgamma = s2 =
+ *                                           sum g xhat, dz = gamma invstd (g - s1 / M - xhat s2 / M).  Each of dz, dgamma, dbeta
+ *                                           may be null and is then not computed.
+ *   dx = conv3x3_pad1(dz, w')               snerf_conv3x3_bwd_input_f32: w'[ci][co][ky][kx] = w[co][ci][2 - ky][2 - kx] is written
+ *                                           into scratch, then the forward kernel runs: one chain over 9 Co per element of dx
+ *   dw, dbias                               snerf_conv3x3_bwd_weight_f32: dw[co][ci][ky][kx] = sum dz[n][co][y][x] xpad[n][ci][y+ky-1]
+ *                                           [x+kx-1] on the matrix cores (exact fp32), dbias[co] = sum dz; either may be null
+ * Tensors are contiguous NCHW fp32; z, dz [N,C,H,W]; y, dy [N,C,H,W] or [N,C,H/2,W/2]; mean, invstd, gamma, beta, dgamma, dbeta,
+ * running_mean, running_var [C].  running_mean / running_var (each nullable) are moved in place as F.batch_norm(training=True)
+ * does: running = (1 - momentum) running + momentum stat, with the unbiased variance var M / (M - 1).
+ * Sums.  Every per-channel sum (the statistics, s1, s2, dbias) is float64 in a fixed order: slices of consecutive n-major terms,
+ *   one partial per (channel, slice) in scratch, one finisher that adds them in slice order; results are rounded once to fp32.
+ *   A dw element is, per slice of consecutive (image, 16 x 16 pixel tile) jobs, four fp32 chains over the rows 4 v .. 4 v + 3
+ *   (v = 0 .. 3) of the tiles, added in that order, then the slices in float64 in slice order, rounded once.  The slice counts
+ *   (snerf_conv3x3_bwd_weight_slices; min(128, ceil(terms / 8192)) for the per-channel sums) depend on the shapes alone, not on
+ *   the device: same inputs, same bits.  No atomics, nothing allocated, nothing synchronises.
+ * scratch: the *_scratch_floats query of the entry, in floats, 8-byte aligned (SNERF_E_ALIGN otherwise); for the weight gradient
+ *   4 Co S floats of dbias partials (S as for snerf_bn_stats_scratch_floats(N, 1, H, W) / 4) and then slices x Co Ci 9 floats.
+ * Limits: 1 <= C, Ci, Co <= 256, N >= 0 (0: SNERF_OK whatever the pointers are), element counts below 2^31, H, W >= 1 (>= 2 with
+ *   pooling); the statistics and the backward need M = N H W >= 2; eps >= 0 and finite, momentum finite; with N > 0 no null
+ *   pointer but the optional ones.  SNERF_E_BADARG on the host, before anything touches a device; the queries return -1. */
+SNERF_API int64_t snerf_bn_stats_scratch_floats(int64_t N, int C, int64_t H, int64_t W);
+SNERF_API int snerf_bn_stats_f32(const float *z, int64_t N, int C, int64_t H, int64_t W, double eps, double momentum, float *running_mean,
+                              float *running_var, float *mean, float *invstd, float *scratch, snerf_stream_t stream);
+SNERF_API int snerf_bn_relu_pool_fwd_f32(const float *z, int64_t N, int C, int64_t H, int64_t W, const float *mean, const float *invstd,
+                              const float *gamma, const float *beta, int relu, int pool, float *y, snerf_stream_t stream);
+SNERF_API int64_t snerf_bn_relu_pool_bwd_scratch_floats(int64_t N, int C, int64_t H, int64_t W, int pool);
+SNERF_API int snerf_bn_relu_pool_bwd_f32(const float *z, const float *dy, int64_t N, int C, int64_t H, int64_t W, const float *mean,
+                              const float *invstd, const float *gamma, const float *beta, int relu, int pool, float *dz,
+                              float *dgamma, float *dbeta, float *scratch, snerf_stream_t stream);
+SNERF_API int64_t snerf_conv3x3_bwd_input_scratch_floats(int Ci, int Co);
+SNERF_API int snerf_conv3x3_bwd_input_f32(const float *dz, int64_t N, int Co, int64_t H, int64_t W, const float *w, int Ci, float *dx,
+                              float *scratch, snerf_stream_t stream);
+SNERF_API int64_t snerf_conv3x3_bwd_weight_slices(int64_t N, int Ci, int64_t H, int64_t W, int Co);
+SNERF_API int64_t snerf_conv3x3_bwd_weight_scratch_floats(int64_t N, int Ci, int64_t H, int64_t W, int Co);
+SNERF_API int snerf_conv3x3_bwd_weight_f32(const float *dz, const float *x, int64_t N, int Ci, int Co, int64_t H, int64_t W, float *dw,
+                              float *dbias, float *scratch, snerf_stream_t stream);
+
 /* ---- 8(f)-1: on-device ray generation + stratified coarse sampling --------------------------------------
  * Replaces get_rays (utils.py:50-54) + CoarseSampling (datasets/transforms.py:80-89) + ToTensor (:13-21) for a
  * batch of rays.  poses: fp64 [n_frames, 4, 4] camera-to-world; ray_index int64 [B] = frame*H*W + row*W + col;

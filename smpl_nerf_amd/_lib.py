@@ -190,6 +190,17 @@ SIGNATURES = {
     "snerf_conv3x3_block_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
     "snerf_smpl_estimator_workspace_bytes": (c_int64, [c_int64, c_int]),
     "snerf_smpl_estimator_fwd_f32": (c_int, [POINTER(SmplEstimatorNet), _P, c_int64, _P, _P, c_int64, _P]),
+    # SmplEstimator, training: batch statistics, the block's apply and backward, the convolution's gradients (csrc/conv_train.hip)
+    "snerf_bn_stats_scratch_floats": (c_int64, [c_int64, c_int, c_int64, c_int64]),
+    "snerf_bn_stats_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, c_double, c_double, _P, _P, _P, _P, _P, _P]),
+    "snerf_bn_relu_pool_fwd_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    "snerf_bn_relu_pool_bwd_scratch_floats": (c_int64, [c_int64, c_int, c_int64, c_int64, c_int]),
+    "snerf_bn_relu_pool_bwd_f32": (c_int, [_P, _P, c_int64, c_int, c_int64, c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "snerf_conv3x3_bwd_input_scratch_floats": (c_int64, [c_int, c_int]),
+    "snerf_conv3x3_bwd_input_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, _P, c_int, _P, _P, _P]),
+    "snerf_conv3x3_bwd_weight_slices": (c_int64, [c_int64, c_int, c_int64, c_int64, c_int]),
+    "snerf_conv3x3_bwd_weight_scratch_floats": (c_int64, [c_int64, c_int, c_int64, c_int64, c_int]),
+    "snerf_conv3x3_bwd_weight_f32": (c_int, [_P, _P, c_int64, c_int, c_int, c_int64, c_int64, _P, _P, _P, _P]),
     "snerf_raygen_f64": (c_int, [_P, c_int64, c_int, c_int, c_double, _P, _P, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "snerf_mlp_fwd_encoded_f32": (c_int, [POINTER(MlpDesc), _P, _P, c_int64, c_int64, _P, _P]),
     "snerf_render_rays_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),

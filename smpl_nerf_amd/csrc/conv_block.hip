@@ -23,7 +23,7 @@
 
 #include <algorithm>
 
-#include "snerf_common.h"
+#include "conv_block.h"
 
 namespace snerf {
 
@@ -38,7 +38,6 @@ constexpr int CB_LW = 20;                     // row pitch of the input tile
 constexpr int CB_PLANE = CB_HALO * CB_LW;
 constexpr int CB_WP = CB_KC + 2;              // row pitch of the weight slice
 constexpr int CB_THREADS = 256;
-constexpr int CB_MAX_C = 256;
 constexpr int CB_GRID_X = 1 << 16;             // (image, tile) pairs per grid row: 2^16 x 256 threads stays below HIP's 2^32 per dimension
 
 struct ConvArgs {
@@ -195,7 +194,7 @@ static bool below_2_31(int64_t a, int64_t b, int64_t c, int64_t d) {
 }
 
 // the scalar checks of a block (an error whatever N is); *Ho, *Wo: the extents of y
-static int conv_check(const char *what, int64_t N, int Ci, int64_t H, int64_t W, int Co, int pool, int64_t *Ho, int64_t *Wo) {
+int conv_check(const char *what, int64_t N, int Ci, int64_t H, int64_t W, int Co, int pool, int64_t *Ho, int64_t *Wo) {
     if (Ci < 1 || Ci > CB_MAX_C) return fail(SNERF_E_BADARG, "%s: Ci = %d is outside 1 .. %d", what, Ci, CB_MAX_C);
     if (Co < 1 || Co > CB_MAX_C) return fail(SNERF_E_BADARG, "%s: Co = %d is outside 1 .. %d", what, Co, CB_MAX_C);
     if (N < 0) return fail(SNERF_E_BADARG, "%s: N = %lld is negative", what, (long long)N);
@@ -210,8 +209,8 @@ static int conv_check(const char *what, int64_t N, int Ci, int64_t H, int64_t W,
 }
 
 // one block on checked arguments, N > 0
-static int conv_launch(const char *what, const float *x, int64_t N, int Ci, int H, int W, const float *w, const float *scale, const float *shift,
-                       int Co, int relu, int pool, float *y, hipStream_t s) {
+int conv_launch(const char *what, const float *x, int64_t N, int Ci, int H, int W, const float *w, const float *scale, const float *shift,
+                int Co, int relu, int pool, float *y, hipStream_t s) {
     ConvArgs G{x, w, scale, shift, y, Ci, Co, H, W, pool ? H / 2 : H, pool ? W / 2 : W, 0, 0, 0, relu ? 1 : 0, pool ? 1 : 0};
     G.tiles_x = (W + CB_TILE - 1) / CB_TILE;
     G.tiles = G.tiles_x * ((H + CB_TILE - 1) / CB_TILE);

@@ -2,12 +2,14 @@
 
 The module has the reference's parameter and buffer names, so a model_smpl_estimator.pt written by the reference's save_run loads
 with io.load_run, and the other way round.  On the GPU, in eval() mode with grad disabled, forward is ONE call of the library
-(snerf_smpl_estimator_fwd_f32: the BatchNorm fold, five fused conv-BN-ReLU-pool launches, fc1, fc2).  Everywhere else - training
-mode, grad enabled, CPU tensors - it is the reference's expression in torch ops: the training kernels of the convolution block
-(batch-statistics BatchNorm, dropout, weight gradient, pool / ReLU / BN backward) do not exist yet.
+(snerf_smpl_estimator_fwd_f32: the BatchNorm fold, five fused conv-BN-ReLU-pool launches, fc1, fc2).  On the GPU in training mode -
+the only mode the reference's solver ever runs in - it is five ops.conv3x3_bn_block (csrc/conv_train.hip: batch statistics, the
+weight and input gradients, the pool / ReLU / BatchNorm backward), nn.Dropout as torch ops on the [N,8192] and [N,500] rows, and
+layered.linear for fc1 and fc2.  Everywhere else - CPU tensors, eval mode with grad enabled, momentum=None,
+other dtypes - it is the reference's expression in torch ops.
 
-validate() is the validation half of SmplEstimatorSolver.train (solver/smpl_estimator_solver.py:70-84); normalize_image restates
-the data set's transform (datasets/transforms.py NormalizeRGBImage, smpl_estimator_dataset.py:78-80).
+train_epoch() and validate() are the two halves of SmplEstimatorSolver.train (solver/smpl_estimator_solver.py:52-68, :70-84);
+normalize_image restates the data set's transform (datasets/transforms.py NormalizeRGBImage, smpl_estimator_dataset.py:78-80).
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, layered, ops
 from ._lib import check, current_stream, ptr
 
 CHANNELS = (3, 16, 32, 64, 64, 128)      # features in front of and behind each of the five blocks
@@ -100,9 +102,37 @@ class SmplEstimator(nn.Module):
                   "snerf_smpl_estimator_fwd_f32")
         return out
 
+    def _trains_on_device(self, x):
+        """Whether the training-mode device path takes x: fp32 GPU images [N,3,128,128], N >= 1, contiguous fp32 GPU parameters,
+        BatchNorm2d with affine weights, running statistics and a float momentum."""
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, SIDE, SIDE) or x.shape[0] < 1 or x.dtype != torch.float32:
+            return False
+        for conv, bn in self._blocks():
+            if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+                return False
+            for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var):
+                if t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                    return False
+        return all(t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                   for t in (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias))
+
+    def _forward_train_device(self, x):
+        """Training mode on the library's kernels: per block one ops.conv3x3_bn_block (which moves the running statistics) and the
+        step of num_batches_tracked that nn.BatchNorm2d makes; the dropout of the reference's two places in torch ops."""
+        h = x.contiguous()
+        for (conv, bn), pooled in zip(self._blocks(), POOL):
+            h = ops.conv3x3_bn_block(h, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum=bn.momentum,
+                                     eps=bn.eps, relu=True, pool=pooled)
+            bn.num_batches_tracked.add_(1)
+        h = self.dropout(h.reshape(-1, FLAT))
+        h = self.dropout(layered.linear([(h, self.fc1.weight)], self.fc1.bias, relu=True))
+        return layered.linear([(h, self.fc2.weight)], self.fc2.bias)
+
     def forward(self, x):
         if x.is_cuda and not self.training and not torch.is_grad_enabled():
             return self._forward_device(x)
+        if x.is_cuda and self.training and self._trains_on_device(x):
+            return self._forward_train_device(x)
         return self._forward_torch(x)
 
     @property
@@ -130,6 +160,34 @@ def normalize_image(frames):
         raise ValueError(f"normalize_image: expected [H,W,3] or [F,H,W,3], got {frames.shape}")
     unit = np.true_divide(frames, 255.0, dtype=np.float64).astype(np.float32)
     return torch.from_numpy(np.ascontiguousarray(np.moveaxis(unit, -1, -3)))
+
+
+def train_epoch(model, loader, optim, loss_func=None, log_iterations=None):
+    """The training loop of SmplEstimatorSolver.train (:52-68) for one epoch: per batch the forward in training mode, zero_grad, the
+    loss (nn.MSELoss unless given), backward and the step of `optim` (any torch optimiser over model.parameters()), on the model's
+    device - on the GPU the forward and the backward run on the library's kernels.  A model with two outputs is scored against
+    columns 38 and 41 of the 69-vector truth (:56).  Every log_iterations-th batch prints the reference's line.  The model is put
+    into train() mode and stays there.  Returns the mean loss over the batches as a float (0.0 for an empty loader)."""
+    criterion = nn.MSELoss() if loss_func is None else loss_func
+    device = model.fc2.weight.device
+    two_angles = model.fc2.out_features == 2
+    model.train()
+    total, batches = 0.0, 0
+    for i, (images, truth) in enumerate(loader):
+        images, truth = images.to(device), truth.to(device)
+        if two_angles:
+            truth = truth[:, [38, 41]]
+        pose = model(images)
+        optim.zero_grad()
+        loss = criterion(pose, truth)
+        loss.backward()
+        item = loss.item()
+        optim.step()
+        if log_iterations and i % log_iterations == log_iterations - 1:
+            print('[Iteration %5d] TRAIN loss: %.7f' % (i + 1, item))
+        total += item
+        batches += 1
+    return total / max(batches, 1)
 
 
 def validate(model, loader, loss_func=None):

@@ -13,6 +13,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     ray_mesh_first_hit                   render.py:222-319 (get_warp: the depth and the true warp of the single-sample model)
     ssim / image_scores util/scores.py:88-173 (ssim) and :11-48 (img2mse, img2psnr): the scores of print_scores, on the device
     conv3x3_block       models/smpl_estimator.py:35-39: one conv - BatchNorm (eval) - ReLU - pool block of SmplEstimator, inference only
+    conv3x3_bn_block    the same block under nn.Module.train(): BatchNorm on the batch statistics, differentiable to every input
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -1045,7 +1046,8 @@ def conv3x3_block(x, weight, scale, shift, relu: bool = True, pool: bool = False
         _need_cuda(nm, t)
         if t.requires_grad and torch.is_grad_enabled():
             raise RuntimeError(f"conv3x3_block: `{nm}` requires grad, but this op is inference only: the training kernels of the "
-                               "convolution block (weight gradient, pool / ReLU / BatchNorm backward) do not exist yet")
+                               "convolution block (batch statistics, weight gradient, pool / ReLU / BatchNorm backward) are "
+                               "ops.conv3x3_bn_block")
     if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[1:]) != (x.shape[1], 3, 3):
         raise RuntimeError(f"conv3x3_block: x must be [N,Ci,H,W] and weight [Co,Ci,3,3], got {tuple(x.shape)} and {tuple(weight.shape)}")
     N, Ci, H, W = x.shape
@@ -1058,3 +1060,101 @@ def conv3x3_block(x, weight, scale, shift, relu: bool = True, pool: bool = False
         check(_lib.load().snerf_conv3x3_block_f32(ptr(x), N, Ci, H, W, ptr(weight), ptr(scale), ptr(shift), Co, int(bool(relu)),
                                                   int(bool(pool)), ptr(y), current_stream()), "snerf_conv3x3_block_f32")
     return y
+
+
+# ------------------------------------------------------------------------------------------------
+# ... and the block in training mode (csrc/conv_train.hip): batch statistics, and every gradient
+# ------------------------------------------------------------------------------------------------
+def _scratch(query, what, dev):
+    """torch.empty of the floats a *_scratch_floats query asks for (a caching-allocator block: aligned far beyond the 8 bytes asked)."""
+    n = int(query)
+    if n < 0:
+        check(-1, what)
+    return torch.empty(max(n, 2), device=dev, dtype=torch.float32)
+
+
+class _ConvBnBlockFn(torch.autograd.Function):
+    """forward(x, weight, bias, bn_weight, bn_bias, running_mean, running_var, momentum, eps, relu, pool) -> (y, and the running
+    statistics that were given: marked dirty); saves x, z, mean, invstd (and the three parameters the backward reads)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, momentum, eps, relu, pool):
+        lib, dev = _lib.load(), x.device
+        N, Ci, H, W = x.shape
+        Co = weight.shape[0]
+        xd, wd, bd, gd, btd = (t.detach().contiguous() for t in (x, weight, bias, gamma, beta))
+        z = torch.empty((N, Co, H, W), device=dev, dtype=torch.float32)
+        mean, invstd = torch.empty(Co, device=dev, dtype=torch.float32), torch.empty(Co, device=dev, dtype=torch.float32)
+        y = torch.empty((N, Co, H // 2, W // 2) if pool else (N, Co, H, W), device=dev, dtype=torch.float32)
+        ones = torch.ones(Co, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev), _lib.timed(f"conv3x3_bn_block_fwd[{Ci}->{Co},{H}x{W}]"):
+            s = current_stream()
+            check(lib.snerf_conv3x3_block_f32(ptr(xd), N, Ci, H, W, ptr(wd), ptr(ones), ptr(bd), Co, 0, 0, ptr(z), s), "snerf_conv3x3_block_f32")
+            scratch = _scratch(lib.snerf_bn_stats_scratch_floats(N, Co, H, W), "snerf_bn_stats_scratch_floats", dev)
+            check(lib.snerf_bn_stats_f32(ptr(z), N, Co, H, W, eps, momentum, ptr(running_mean), ptr(running_var), ptr(mean), ptr(invstd),
+                                         ptr(scratch), s), "snerf_bn_stats_f32")
+            check(lib.snerf_bn_relu_pool_fwd_f32(ptr(z), N, Co, H, W, ptr(mean), ptr(invstd), ptr(gd), ptr(btd), int(relu), int(pool), ptr(y), s),
+                  "snerf_bn_relu_pool_fwd_f32")
+        dirty = tuple(t for t in (running_mean, running_var) if t is not None)      # moved in place: autograd wants them returned
+        ctx.mark_dirty(*dirty)
+        ctx.mark_non_differentiable(*dirty)
+        ctx.save_for_backward(xd, wd, gd, btd, z, mean, invstd)
+        ctx.relu, ctx.pool = int(relu), int(pool)
+        return (y,) + dirty
+
+    @staticmethod
+    def backward(ctx, dy, *_):
+        xd, wd, gd, btd, z, mean, invstd = ctx.saved_tensors
+        need_x, need_w, need_b, need_g, need_bt = ctx.needs_input_grad[:5]
+        lib, dev = _lib.load(), dy.device
+        N, Ci, H, W = xd.shape
+        Co = wd.shape[0]
+        dy = dy.contiguous()
+        need_dz = need_x or need_w or need_b
+        dz = torch.empty_like(z) if need_dz else None
+        dg = torch.empty(Co, device=dev, dtype=torch.float32) if need_g else None
+        dbt = torch.empty(Co, device=dev, dtype=torch.float32) if need_bt else None
+        dx = dw = db = None
+        with torch.cuda.device(dev), _lib.timed(f"conv3x3_bn_block_bwd[{Ci}->{Co},{H}x{W}]"):
+            s = current_stream()
+            if need_dz or need_g or need_bt:
+                scratch = _scratch(lib.snerf_bn_relu_pool_bwd_scratch_floats(N, Co, H, W, ctx.pool), "snerf_bn_relu_pool_bwd_scratch_floats", dev)
+                check(lib.snerf_bn_relu_pool_bwd_f32(ptr(z), ptr(dy), N, Co, H, W, ptr(mean), ptr(invstd), ptr(gd), ptr(btd), ctx.relu, ctx.pool,
+                                                     ptr(dz), ptr(dg), ptr(dbt), ptr(scratch), s), "snerf_bn_relu_pool_bwd_f32")
+            if need_w or need_b:
+                dw = torch.empty_like(wd) if need_w else None
+                db = torch.empty(Co, device=dev, dtype=torch.float32) if need_b else None
+                scratch = _scratch(lib.snerf_conv3x3_bwd_weight_scratch_floats(N, Ci, H, W, Co), "snerf_conv3x3_bwd_weight_scratch_floats", dev)
+                check(lib.snerf_conv3x3_bwd_weight_f32(ptr(dz), ptr(xd), N, Ci, Co, H, W, ptr(dw), ptr(db), ptr(scratch), s),
+                      "snerf_conv3x3_bwd_weight_f32")
+            if need_x:
+                dx = torch.empty_like(xd)
+                scratch = _scratch(lib.snerf_conv3x3_bwd_input_scratch_floats(Ci, Co), "snerf_conv3x3_bwd_input_scratch_floats", dev)
+                check(lib.snerf_conv3x3_bwd_input_f32(ptr(dz), N, Co, H, W, ptr(wd), Ci, ptr(dx), ptr(scratch), s), "snerf_conv3x3_bwd_input_f32")
+        return dx, dw, db, dg, dbt, None, None, None, None, None, None
+
+
+def conv3x3_bn_block(x, weight, bias, bn_weight, bn_bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, relu: bool = True,
+                     pool: bool = False):
+    """The block as nn.Conv2d(3, padding=1) - nn.BatchNorm2d in TRAINING mode - ReLU - nn.MaxPool2d(2, 2) compute it:
+    y = [maxpool2x2](relu(BN_batch(conv3x3_pad1(x, weight) + bias))), x [N,Ci,H,W], weight [Co,Ci,3,3], the rest [Co]; N H W >= 2.
+    Differentiable to x, weight, bias, bn_weight and bn_bias (only what requires grad is computed); running_mean / running_var, when
+    given, are moved in place with `momentum` (a float) as F.batch_norm(training=True) moves them.  fp32 GPU tensors, made contiguous."""
+    for nm, t in (("x", x), ("weight", weight), ("bias", bias), ("bn_weight", bn_weight), ("bn_bias", bn_bias)):
+        _need_cuda(nm, t)
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[1:]) != (x.shape[1], 3, 3):
+        raise RuntimeError(f"conv3x3_bn_block: x must be [N,Ci,H,W] and weight [Co,Ci,3,3], got {tuple(x.shape)} and {tuple(weight.shape)}")
+    Co = weight.shape[0]
+    for nm, t in (("bias", bias), ("bn_weight", bn_weight), ("bn_bias", bn_bias), ("running_mean", running_mean), ("running_var", running_var)):
+        if t is None:
+            continue
+        if tuple(t.shape) != (Co,):
+            raise RuntimeError(f"conv3x3_bn_block: `{nm}` must be [{Co}], got {tuple(t.shape)}")
+        if nm.startswith("running"):
+            _need_cuda(nm, t)
+            if not t.is_contiguous() or t.requires_grad:
+                raise RuntimeError(f"conv3x3_bn_block: `{nm}` is updated in place: it must be contiguous and must not require grad")
+    if momentum is None:
+        raise RuntimeError("conv3x3_bn_block: momentum=None (the cumulative average) is not supported")
+    return _ConvBnBlockFn.apply(x, weight, bias, bn_weight, bn_bias, running_mean, running_var, float(momentum), float(eps), bool(relu),
+                                bool(pool))[0]
