@@ -609,6 +609,56 @@ SNERF_API int snerf_ray_mesh_first_hit_f32(const float *origins, const float *di
 SNERF_API int snerf_vertex_sphere_warp_f32(const float *samples, const float *goal, const float *canon, int64_t n, int V, float radius,
                               int by_mean, float *warp, int32_t *nearest, int32_t *count, snerf_stream_t stream);
 
+/* ---- The mesh renderer: textured, lit frames of a posed body (create_dataset.py:106-129 through render.py:322-367) ----------------
+ * One call renders N frames of H x W pixels of one triangle mesh per frame, seen through pinhole cameras.
+ * Inputs: poses [N,4,4] float64 camera-to-world, row-major, and focal, as snerf_raygen_f64 takes them; vertices [Nv,V,3] with
+ *   Nv = 1 (one body for all frames) or Nv = N (one per frame); faces [F,3] int32; vf_offsets [V+1], vf_faces [3F] int32: for
+ *   every vertex its incident faces in ascending face index, as a CSR table (vertex v owns vf_faces[vf_offsets[v] ..
+ *   vf_offsets[v+1])); uv [V,2]: one texture coordinate per vertex; texture [Ht,Wt,3] in [0,1]; args; optionally canon [V,3].
+ * Rays: pixel (row j, column i) of frame n has the origin and the direction snerf_raygen_f64 gives ray index (n H + j) W + i:
+ *   float32 i - W 0.5 and -(j - H 0.5), float64 divide by focal, float64 rotation summed left to right, rounded once to fp32.  In
+ *   camera space these directions have z = -1, so t is the z-depth and t |d| the distance from the camera.
+ * Hit: the intersection rule, the first-hit order (the smallest t; the smaller face index on equal t) and the miss markers of
+ *   snerf_ray_mesh_first_hit_f32.  t [N,H,W], face [N,H,W] int32, bary [N,H,W,2] (its uv) and, with canon, depth [N,H,W] and
+ *   warp [N,H,W,3] equal, bit for bit, what that entry returns for these rays, frame by frame.
+ * Image [N,H,W,3], per hit pixel with (u, v) = bary, w0 = (1 - u) - v, (a, b, c) = faces[face], products and sums kept apart,
+ *   mix(x) = (w0 x_a + u x_b) + v x_c and dot = (x0 y0 + x1 y1) + x2 y2:
+ *     vertex normals  n_v = the sum, over the incident faces of v in CSR order, of e1 x e2 = (b - a) x (c - a), not normalised
+ *                     (area-weighted; each cross component is one product minus the other)
+ *     normal          m = mix(n);  n = m / sqrtf((mx mx + my my) + mz mz), 0 where that root is 0
+ *     light           l = column 2 of the frame's rotation (the camera's +z, towards the viewer) rounded to fp32: a directional
+ *                     light at the camera pose, as the reference places it
+ *     shade           lambert = fmaxf(0, dot(n, l));  shade = fminf(1, ambient + intensity lambert)
+ *     texel           (U, V) = mix(uv);  x = U Wt - 0.5,  y = (1 - V) Ht - 0.5;  x0 = floorf(x), fx = x - x0, columns x0 and x0 + 1
+ *                     clamped to [0, Wt - 1]; rows alike from y.  Per channel, rows first:
+ *                       top = t[y0][x0] (1 - fx) + t[y0][x1] fx,  bottom = t[y1][x0] (1 - fx) + t[y1][x1] fx,
+ *                       texel = top (1 - fy) + bottom fy
+ *     pixel           image = texel shade.  A miss pixel gets args->background.
+ *   This is a Lambert model.  It is not pyrender's metallic-roughness shader, and nothing is pinned against pyrender or trimesh.
+ * The cull: per frame and face a conservative screen-space box decides whether an 8 x 8 pixel tile looks at the face at all.  It is
+ *   an optimisation only: every output equals the brute-force walk over all faces bit for bit, which SNERF_RENDER_NO_CULL in
+ *   args->flags runs instead.
+ * Every element of every non-NULL output is written; no atomics; nothing of size pixels x faces; two calls give the same bits.
+ * There is no backward: the frames are data.
+ * workspace: snerf_mesh_render_workspace_bytes(N, V, F) bytes = 4 N (13 F + 3 V), written by two pre-passes of every call.
+ * Argument checks, on the host before any device work: N < 0, H, W, Ht or Wt < 1, a focal that is not positive and finite, V < 1,
+ *   F < 1, 3 V or 9 F not below 2^31 are SNERF_E_BADARG whatever N is; N = 0 is a no-op returning 0, also with null pointers; then Nv
+ *   other than 1 or N, a required null pointer, a mix of null and non-null among canon, warp and depth, N times the 8 x 8 tiles of
+ *   a frame or 3 Ht Wt not below 2^31, N above 65535, and a workspace that is missing or too small.  Face indices in [0, V) and a
+ *   CSR table of this face table are preconditions (the Python operator checks the one and builds the other). */
+#define SNERF_RENDER_NO_CULL 1 /* flags: walk all faces for every tile */
+typedef struct snerf_mesh_render_args {
+    float ambient, intensity; /* shade = min(1, ambient + intensity max(0, n . l)) */
+    float background[3];      /* colour of a miss pixel */
+    int32_t flags;            /* 0 or SNERF_RENDER_NO_CULL */
+} snerf_mesh_render_args;
+SNERF_API int64_t snerf_mesh_render_workspace_bytes(int64_t N, int V, int F);   /* -1 on a bad argument */
+SNERF_API int snerf_mesh_render_f32(const double *poses, double focal, int64_t N, int H, int W, const float *vertices, int Nv, int V,
+                              const int32_t *faces, int F, const int32_t *vf_offsets, const int32_t *vf_faces, const float *uv,
+                              const float *texture, int Ht, int Wt, const snerf_mesh_render_args *args, const float *canon,
+                              float *image, float *t, int32_t *face, float *bary, float *depth, float *warp, void *workspace,
+                              int64_t workspace_bytes, snerf_stream_t stream);
+
 /* ---- Image scores: structural similarity with its backward, and the squared error of MSE / PSNR (util/scores.py:11-48, 88-173) ----
  * x, y: N images of C channels, H x W pixels, fp32, BOTH read through the four element strides (sn, sc, sh, sw): element
  *   (n, c, h, w) lies at n sn + c sc + h sh + w sw, so [N,C,H,W] and channels-last [N,H,W,C] storage run without a copy.

@@ -66,6 +66,14 @@ class SmplEstimatorNet(ctypes.Structure):
                 ("human_size", c_int32)]
 
 
+class MeshRenderArgs(ctypes.Structure):
+    """struct snerf_mesh_render_args - the shading constants and flags of snerf_mesh_render_f32."""
+    _fields_ = [("ambient", c_float), ("intensity", c_float), ("background", c_float * 3), ("flags", c_int32)]
+
+
+RENDER_NO_CULL = 1     # include/smplnerf.h SNERF_RENDER_NO_CULL
+
+
 class AdamState(ctypes.Structure):
     """struct snerf_adam_state - torch.optim.Adam over one flat fp32 buffer (solver/nerf_solver.py:11-14, 31-33)."""
     _fields_ = [("params", _P), ("grads", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("n_params", c_int64),
@@ -179,6 +187,10 @@ SIGNATURES = {
     "snerf_ray_mesh_workspace_bytes": (c_int64, [c_int]),
     "snerf_ray_mesh_hits_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, c_int64, _P]),
     "snerf_ray_mesh_first_hit_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
+    # the mesh renderer: textured, lit frames from poses (csrc/mesh_render.hip)
+    "snerf_mesh_render_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "snerf_mesh_render_f32": (c_int, [_P, c_double, c_int64, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int,
+                                      POINTER(MeshRenderArgs), _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     "snerf_vertex_sphere_warp_f32": (c_int, [_P, _P, _P, c_int64, c_int, c_float, c_int, _P, _P, _P, _P]),
     # image scores: SSIM with its backward and the squared error of MSE / PSNR (csrc/ssim.hip)
     "snerf_ssim_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int]),

@@ -16,18 +16,15 @@
 // by 1e-5 so that it never decides: the decision is taken on the divided values.
 //
 // The first hit (render.py:222-319, get_warp: one intersector call, then two Python loops over the rays): the same walk and the same
-// pair rule (rm_pair below, shared by both kernels), but a lane keeps (t, face, u, v) of its nearest hit, replaced only on a strict
+// pair rule (rm_pair of ray_mesh_pair.h, shared with mesh_render.hip), but a lane keeps (t, face, u, v) of its nearest hit, replaced only on a strict
 // t <.  A wave walks its slice in ascending face order, the slices ascend with the wave index and wave 0 merges in wave order with the
 // same strict <, so equal t goes to the smaller face index.  The face index is the walk's own counter.  With `canon` wave 0 then
 // gathers, per hit ray, the three indices of its face and nine floats of the canonical body: depth = t |d| and
 // warp = (ca + u (cb - ca) + v (cc - ca)) - (o + d t).  The extra state is written inside the hit branch only.
-#include <math.h>
-
-#include "pair_walk.h"
+#include "ray_mesh_pair.h"
 
 namespace snerf {
 
-constexpr int RM_WAVES = 8;       // waves of a ray-chunk workgroup: the face slices
 constexpr int RM_MAX_HITS = 16;   // largest K
 
 struct RmArgs {
@@ -41,15 +38,10 @@ struct RmArgs {
 __global__ __launch_bounds__(256) void ray_mesh_faces_kernel(const float *vertices, const int32_t *faces, int F, float *tri) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
-    const float *a = vertices + (int64_t)faces[f * 3 + 0] * 3, *b = vertices + (int64_t)faces[f * 3 + 1] * 3,
-                *c = vertices + (int64_t)faces[f * 3 + 2] * 3;
-    float *o = tri + (int64_t)f * 9;
+    float T[9];
+    rm_face(vertices, faces, f, T);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        o[i] = a[i];
-        o[3 + i] = b[i] - a[i];
-        o[6 + i] = c[i] - a[i];
-    }
+    for (int i = 0; i < 9; ++i) tri[(int64_t)f * 9 + i] = T[i];
 }
 
 // the sorted list of the KC smallest values seen: a new value sinks in by one compare-and-swap per slot
@@ -63,38 +55,8 @@ __device__ __forceinline__ void rm_insert(float (&list)[KC], float t) {
     }
 }
 
-__device__ __forceinline__ float dot3(float x0, float x1, float x2, float y0, float y1, float y2) { return x0 * y0 + x1 * y1 + x2 * y2; }
-
-// one ray of a lane
-struct RmRay {
-    float ox, oy, oz, dx, dy, dz;
-};
-
 __device__ __forceinline__ RmRay rm_load_ray(const float *origins, const float *dirs, int64_t rr) {
     return {origins[rr * 3 + 0], origins[rr * 3 + 1], origins[rr * 3 + 2], dirs[rr * 3 + 0], dirs[rr * 3 + 1], dirs[rr * 3 + 2]};
-}
-
-// The pair rule, for both kernels: the ray against T, the nine floats (a, e1, e2) of one face at a wave-uniform address;
-// hit(t, u, v) runs for a pair that is one.
-template <class Hit>
-__device__ __forceinline__ void rm_pair(const RmRay &y, const float *T, Hit &&hit) {
-    const float px = y.dy * T[8] - y.dz * T[7], py = y.dz * T[6] - y.dx * T[8], pz = y.dx * T[7] - y.dy * T[6];   // p = d x e2
-    const float det = dot3(T[3], T[4], T[5], px, py, pz);
-    const float sx = y.ox - T[0], sy = y.oy - T[1], sz = y.oz - T[2];
-    const float un = dot3(sx, sy, sz, px, py, pz);
-    const float qx = sy * T[5] - sz * T[4], qy = sz * T[3] - sx * T[5], qz = sx * T[4] - sy * T[3];   // q = s x e1
-    const float vn = dot3(y.dx, y.dy, y.dz, qx, qy, qz);
-    // the wide test: u and v through the hardware reciprocal (1 ulp), 1e-5 to spare; a tiny det goes to the exact rule as it is
-    const float inv = __builtin_amdgcn_rcpf(det);
-    const float ur = un * inv, vr = vn * inv;
-    const bool maybe = (ur >= -1e-5f && vr >= -1e-5f && ur + vr <= 1.f + 1e-5f) || fabsf(det) < 1e-30f;
-    if (maybe && det != 0.f) {
-        const float u = un / det, v = vn / det;
-        if (u >= 0.f && v >= 0.f && u + v <= 1.f) {
-            const float t = dot3(T[6], T[7], T[8], qx, qy, qz) / det;
-            if (t > 0.f) hit(t, u, v);
-        }
-    }
 }
 
 template <int KC>
@@ -159,14 +121,9 @@ __global__ __launch_bounds__(RM_WAVES * 64) void ray_mesh_first_hit_kernel(RmFir
     const bool valid = r < A.R;
     const RmRay y = rm_load_ray(A.origins, A.dirs, tail_index(r, A.R, valid));
     const Slice sl = wave_slice(A.F, RM_WAVES, wave);
-    float best = INFINITY, bu = 0.f, bv = 0.f;
-    int bf = -1;
+    RmFirst best;
 
-    auto pair = [&](int f, const float *T) {
-        rm_pair(y, T, [&](float t, float u, float v) {
-            if (t < best) best = t, bf = f, bu = u, bv = v;   // strict: of equal t the face seen first, the smaller index, stays
-        });
-    };
+    auto pair = [&](int f, const float *T) { rm_pair(y, T, [&](float t, float u, float v) { best.take(t, f, u, v); }); };
 
     walk4<9>(
         A.tri, sl.lo, sl.hi,
@@ -176,29 +133,21 @@ __global__ __launch_bounds__(RM_WAVES * 64) void ray_mesh_first_hit_kernel(RmFir
         },
         [&](int f, const float *T) { pair(f, T); });
 
-    put_partials(part[wave], lane, best, __int_as_float(bf), bu, bv);
+    put_partials(part[wave], lane, best.t, __int_as_float(best.face), best.u, best.v);
     __syncthreads();
     if (wave != 0 || !valid) return;
-    for (int w = 1; w < RM_WAVES; ++w)   // in wave order = ascending face order
-        if (part[w][0][lane] < best) best = part[w][0][lane], bf = __float_as_int(part[w][1][lane]), bu = part[w][2][lane], bv = part[w][3][lane];
-    A.t[r] = best;
-    A.face[r] = bf;
-    A.uv[r * 2 + 0] = bu;
-    A.uv[r * 2 + 1] = bv;
+    rm_merge_first(best, part, lane);
+    A.t[r] = best.t;
+    A.face[r] = best.face;
+    A.uv[r * 2 + 0] = best.u;
+    A.uv[r * 2 + 1] = best.v;
     if (!A.canon) return;
-    float wx = 0.f, wy = 0.f, wz = 0.f, depth = 0.f;
-    if (bf >= 0) {
-        const float *ca = A.canon + (int64_t)A.faces[bf * 3 + 0] * 3, *cb = A.canon + (int64_t)A.faces[bf * 3 + 1] * 3,
-                    *cc = A.canon + (int64_t)A.faces[bf * 3 + 2] * 3;
-        depth = best * sqrtf(dist2(y.dx, y.dy, y.dz));
-        wx = ((ca[0] + bu * (cb[0] - ca[0])) + bv * (cc[0] - ca[0])) - (y.ox + y.dx * best);
-        wy = ((ca[1] + bu * (cb[1] - ca[1])) + bv * (cc[1] - ca[1])) - (y.oy + y.dy * best);
-        wz = ((ca[2] + bu * (cb[2] - ca[2])) + bv * (cc[2] - ca[2])) - (y.oz + y.dz * best);
-    }
+    float depth, warp[3];
+    rm_canon(y, best, A.faces, A.canon, depth, warp);
     A.depth[r] = depth;
-    A.warp[r * 3 + 0] = wx;
-    A.warp[r * 3 + 1] = wy;
-    A.warp[r * 3 + 2] = wz;
+    A.warp[r * 3 + 0] = warp[0];
+    A.warp[r * 3 + 1] = warp[1];
+    A.warp[r * 3 + 2] = warp[2];
 }
 
 template <int KC>

@@ -9,7 +9,8 @@ layered.linear for fc1 and fc2.  Everywhere else - CPU te
 other dtypes - it is the reference's expression in torch ops.
 
 train_epoch() and validate() are the two halves of SmplEstimatorSolver.train (solver/smpl_estimator_solver.py:52-68, :70-84);
-normalize_image restates the data set's transform (datasets/transforms.py NormalizeRGBImage, smpl_estimator_dataset.py:78-80).
+normalize_image restates the data set's transform (datasets/transforms.py NormalizeRGBImage, smpl_estimator_dataset.py:78-80);
+rendered_batches is a loader that renders its (image, pose) pairs on the spot (create_dataset.BodyRenderer).
 """
 from __future__ import annotations
 
@@ -160,6 +161,22 @@ def normalize_image(frames):
         raise ValueError(f"normalize_image: expected [H,W,3] or [F,H,W,3], got {frames.shape}")
     unit = np.true_divide(frames, 255.0, dtype=np.float64).astype(np.float32)
     return torch.from_numpy(np.ascontiguousarray(np.moveaxis(unit, -1, -3)))
+
+
+def rendered_batches(renderer, pose_sampler, transforms, betas, batch_size: int, steps: int):
+    """An endless-data-set stand-in for the loader of train_epoch: `steps` batches of (images [batch_size,3,H,W] fp32, poses
+    [batch_size,69] fp32), both on the renderer's device, rendered on the spot - no disk, no host copy of a frame.  renderer: a
+    create_dataset.BodyRenderer; pose_sampler(batch_size) -> body poses [batch_size,69] (array or tensor); transforms [n,4,4]: the
+    camera path, walked cyclically frame by frame.  The images are what normalize_image makes of the frames as io.load_dataset would
+    read them back: BGR, the quotient by 255 taken in float64 and rounded once."""
+    transforms = np.asarray(transforms, np.float64).reshape(-1, 4, 4)
+    for step in range(int(steps)):
+        poses = pose_sampler(int(batch_size))
+        poses = torch.as_tensor(np.asarray(poses) if not isinstance(poses, torch.Tensor) else poses, dtype=torch.float32,
+                                device=renderer.device).reshape(int(batch_size), -1)
+        cams = transforms[(step * int(batch_size) + np.arange(int(batch_size))) % len(transforms)]
+        rgb = renderer.frames(cams, poses, betas)[0]
+        yield rgb.flip(-1).permute(0, 3, 1, 2).double().div_(255.0).float().contiguous(), poses
 
 
 def train_epoch(model, loader, optim, loss_func=None, log_iterations=None):

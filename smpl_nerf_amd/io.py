@@ -46,12 +46,13 @@ def load_dataset(image_directory: str, transforms_file: str = None):
 
 
 def write_dataset(directory: str, images_rgb_uint8, poses, camera_angle_x, human_poses=None, betas=None,
-                  expression=None):
+                  expression=None, indices=None):
     """Writes img_XXX.png + transforms.json in the layout of create_dataset.save_split
-    (create_dataset.py:86-134).  `images_rgb_uint8` [F,H,W,3] RGB like plt.imsave writes them."""
+    (create_dataset.py:86-134).  `images_rgb_uint8` [F,H,W,3] RGB like plt.imsave writes them.  `indices`: the number each
+    frame carries in its file name (save_split names a split's frames by their index in the whole data set); 0, 1, ... if None."""
     from PIL import Image
     os.makedirs(directory, exist_ok=True)
-    names = ["img_{:03d}.png".format(i) for i in range(len(images_rgb_uint8))]
+    names = ["img_{:03d}.png".format(i) for i in (range(len(images_rgb_uint8)) if indices is None else indices)]
     for n, im in zip(names, images_rgb_uint8):
         Image.fromarray(np.asarray(im, np.uint8), "RGB").save(os.path.join(directory, n))
     td = {"camera_angle_x": float(camera_angle_x),

@@ -11,6 +11,7 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     smpl_lbs            the body model the reference takes from smplx (train.py:214): SMPL linear blend skinning
     ray_mesh_hits / vertex_sphere_warp   datasets/vertex_sphere_dataset.py:84-116 (trimesh's intersector) and :128-159 (the true warp)
     ray_mesh_first_hit                   render.py:222-319 (get_warp: the depth and the true warp of the single-sample model)
+    render_mesh                          render.py:322-367 (render_scene: the textured, lit frames create_dataset.py saves; Lambert, not pyrender's shader)
     ssim / image_scores util/scores.py:88-173 (ssim) and :11-48 (img2mse, img2psnr): the scores of print_scores, on the device
     conv3x3_block       models/smpl_estimator.py:35-39: one conv - BatchNorm (eval) - ReLU - pool block of SmplEstimator, inference only
     conv3x3_bn_block    the same block under nn.Module.train(): BatchNorm on the batch statistics, differentiable to every input
@@ -20,9 +21,13 @@ no CPU implementation here: a CPU tensor is an error, like a missing library.
 """
 from __future__ import annotations
 
+import collections
+import ctypes
 import platform
+import weakref
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -847,6 +852,98 @@ def ray_mesh_first_hit(origins, directions, vertices, faces, canon=None, faces_c
         check(lib.snerf_ray_mesh_first_hit_f32(ptr(o), ptr(d), ptr(vt), ptr(fc), R, V, F, ptr(cn), ptr(t), ptr(face), ptr(uv), ptr(warp),
                                                ptr(depth), ptr(ws), nbytes, current_stream()), "snerf_ray_mesh_first_hit_f32")
     return (t, face, uv) if cn is None else (t, face, uv, warp, depth)
+
+
+MeshFrames = collections.namedtuple("MeshFrames", "image t face bary depth warp")
+_VERTEX_FACES = {}      # (data_ptr, device, F, V, tensor version) -> (weak reference to the face tensor, vf_offsets, vf_faces)
+
+
+def vertex_face_table(faces, V: int):
+    """The CSR table of a face table [F,3] (any integer dtype, host or device): (vf_offsets [V+1], vf_faces [3F]) int32 numpy
+    arrays - vertex v owns vf_faces[vf_offsets[v]:vf_offsets[v+1]], its incident faces in ascending face index (a face that names
+    a vertex twice is listed twice)."""
+    f = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces).astype(np.int64).reshape(-1, 3)
+    flat = f.reshape(-1)
+    order = np.argsort(flat, kind="stable")                       # stable: within a vertex the corners stay in face order
+    offsets = np.zeros(V + 1, np.int64)
+    np.cumsum(np.bincount(flat, minlength=V), out=offsets[1:])
+    return offsets.astype(np.int32), (order // 3).astype(np.int32)
+
+
+def _vertex_faces_cached(faces, V):
+    key = (faces.data_ptr(), faces.device, faces.shape[0], V, faces._version)
+    hit = _VERTEX_FACES.get(key)
+    if hit is not None and hit[0]() is faces:
+        return hit[1], hit[2]
+    for k in [k for k, v in _VERTEX_FACES.items() if v[0]() is None]:
+        del _VERTEX_FACES[k]
+    off, vf = (torch.from_numpy(a).to(faces.device) for a in vertex_face_table(faces, V))
+    _VERTEX_FACES[key] = (weakref.ref(faces), off, vf)
+    return off, vf
+
+
+@torch.no_grad()
+def render_mesh(poses, focal, H: int, W: int, vertices, faces, uv, texture, ambient: float = 0., intensity: float = 1.,
+                background=(1., 1., 1.), canon=None, cull: bool = True, faces_checked: bool = False):
+    """N textured, lit frames of a triangle mesh in one call (csrc/mesh_render.hip; include/smplnerf.h, snerf_mesh_render_f32, states
+    the rule operation by operation): what create_dataset.py asks pyrender for frame by frame.  poses [N,4,4] float64 camera-to-world
+    and focal as RayGenerator holds them; vertices [V,3] (one body for all frames) or [N,V,3] (one per frame) fp32; faces [F,3]
+    int32; uv [V,2] fp32, one texture coordinate per vertex; texture [Ht,Wt,3] fp32 in [0,1]; optionally canon [V,3] ->
+    MeshFrames(image [N,H,W,3] fp32 - Lambert shade min(1, ambient + intensity max(0, n . l)) times the bilinear texel, `background`
+    on a miss -, t [N,H,W] (+inf on a miss; the z-depth: the rays have camera-space z = -1), face [N,H,W] int32 (-1), bary [N,H,W,2]
+    (0) and, with canon, depth [N,H,W] and warp [N,H,W,3] (0), else None).  t, face, bary, depth and warp are, bit for bit, what
+    ray_mesh_first_hit returns for the rays RayGenerator makes for these poses.  cull=False walks every face for every pixel tile:
+    the same bits, slower.  The face table is range-checked once (faces_checked=True skips it) and its vertex-to-face table is
+    built on the host once per faces tensor and cached.  The frames are data: no backward, no grad_fn."""
+    if faces.dtype != torch.int32:
+        raise RuntimeError(f"render_mesh: `faces` must be int32 (got {faces.dtype})")
+    if vertices.dim() == 2:
+        vertices = vertices[None]
+    if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[1] < 1 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise RuntimeError(f"render_mesh: vertices {tuple(vertices.shape)} must be [V >= 1, 3] or [N, V, 3] and faces {tuple(faces.shape)} [F >= 1, 3]")
+    Nv, V, F = vertices.shape[0], vertices.shape[1], faces.shape[0]
+    if not faces_checked:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= V:
+            raise RuntimeError(f"render_mesh: faces index vertices {lo} .. {hi}, outside [0, {V})")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.dtype != torch.float64:
+        raise RuntimeError(f"render_mesh: poses must be float64 [N,4,4], got {poses.dtype} {tuple(poses.shape)}")
+    N = poses.shape[0]
+    if Nv not in (1, N):
+        raise RuntimeError(f"render_mesh: {Nv} bodies for {N} frames (one for all, or one per frame)")
+    if tuple(uv.shape) != (V, 2) or texture.dim() != 3 or texture.shape[2] != 3 or texture.shape[0] < 1 or texture.shape[1] < 1:
+        raise RuntimeError(f"render_mesh: uv {tuple(uv.shape)} must be [V,2] and texture {tuple(texture.shape)} [Ht,Wt,3]")
+    if canon is not None and tuple(canon.shape) != (V, 3):
+        raise RuntimeError(f"render_mesh: canon {tuple(canon.shape)} must be [V,3] = [{V},3]")
+    if int(H) < 1 or int(W) < 1 or not float(focal) > 0:
+        raise RuntimeError("render_mesh: H and W must be at least 1 and focal positive")
+    for nm, t in (("poses", poses), ("vertices", vertices), ("faces", faces), ("uv", uv), ("texture", texture), ("canon", canon)):
+        if t is not None:
+            if not t.is_cuda:
+                raise RuntimeError(f"smpl_nerf_amd: `{nm}` must live on the GPU (got {t.device}); there is no CPU path")
+            if nm not in ("poses", "faces") and t.dtype != torch.float32:
+                raise RuntimeError(f"render_mesh: `{nm}` must be float32 (got {t.dtype})")
+    off, vf = _vertex_faces_cached(faces, V)
+    ps, vt, fc, uvc, tex = (x.detach().contiguous() for x in (poses, vertices, faces, uv, texture))
+    cn = None if canon is None else canon.detach().contiguous()
+    dev, H, W = ps.device, int(H), int(W)
+    image = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
+    t = torch.empty((N, H, W), device=dev, dtype=torch.float32)
+    face = torch.empty((N, H, W), device=dev, dtype=torch.int32)
+    bary = torch.empty((N, H, W, 2), device=dev, dtype=torch.float32)
+    depth, warp = (torch.empty((N, H, W), device=dev, dtype=torch.float32), torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)) if cn is not None else (None, None)
+    lib = _lib.load()
+    nbytes = lib.snerf_mesh_render_workspace_bytes(N, V, F)
+    if nbytes < 0:
+        check(-1, "snerf_mesh_render_workspace_bytes")
+    ws = torch.empty((max(nbytes, 1),), device=dev, dtype=torch.uint8)
+    args = _lib.MeshRenderArgs(float(ambient), float(intensity), (ctypes.c_float * 3)(*(float(b) for b in background)),
+                               0 if cull else _lib.RENDER_NO_CULL)
+    with torch.cuda.device(dev), _lib.timed(f"mesh_render[N={N},F={F}]"):
+        check(lib.snerf_mesh_render_f32(ptr(ps), float(focal), N, H, W, ptr(vt), Nv, V, ptr(fc), F, ptr(off), ptr(vf), ptr(uvc), ptr(tex),
+                                        tex.shape[0], tex.shape[1], ctypes.byref(args), ptr(cn), ptr(image), ptr(t), ptr(face), ptr(bary),
+                                        ptr(depth), ptr(warp), ptr(ws), nbytes, current_stream()), "snerf_mesh_render_f32")
+    return MeshFrames(image, t, face, bary, depth, warp)
 
 
 def vertex_sphere_warp(samples, goal, canon, radius, by_mean: bool = False, want_indices: bool = False):

@@ -161,3 +161,31 @@ def surface_smpl_arrays(seed: int, level: int = 2, n_joints: int = 24, num_betas
             "weights": (wts / wts.sum(1, keepdims=True)).astype(f),
             "parents": np.array([SMPL_PARENTS[j] if j < len(SMPL_PARENTS) else j - 1 for j in range(J)], np.int32),
             "faces": faces}
+
+
+def surface_uv(vertices, seed: int = 0) -> np.ndarray:
+    """One texture coordinate per vertex, [V,2] float32 in [0,1]: the spherical coordinates of the rest vertices about their
+    centroid, U the azimuth over 2 pi and V the polar angle over pi, in a frame rotated by a seeded random rotation (so that the
+    seam and the poles do not sit on a symmetry plane of the body).  The reference reads per-vertex uv from its SMPL texture file
+    (its mesh is built with process=False); this stands in for it in tests and examples."""
+    rng = np.random.default_rng(seed)
+    q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+    p = (np.asarray(vertices, np.float64) - np.asarray(vertices, np.float64).mean(0)) @ q
+    r = np.maximum(np.linalg.norm(p, axis=-1), 1e-12)
+    u = np.arctan2(p[:, 1], p[:, 0]) / (2 * np.pi) + 0.5
+    v = np.arccos(np.clip(p[:, 2] / r, -1, 1)) / np.pi
+    return np.stack([u, v], -1).astype(np.float32)
+
+
+def smooth_texture(seed: int, height: int = 64, width: int = 64, waves: int = 4) -> np.ndarray:
+    """A seeded smooth RGB texture [height,width,3] float32 in [0,1]: per channel a mean plus `waves` low-frequency plane waves,
+    periodic in the horizontal direction (the azimuth of surface_uv wraps there)."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid((np.arange(height) + 0.5) / height, (np.arange(width) + 0.5) / width, indexing="ij")
+    out = np.empty((height, width, 3))
+    for c in range(3):
+        kx, ky = rng.integers(1, 4, waves), rng.uniform(0.5, 3.0, waves)
+        phase, amp = rng.uniform(0, 2 * np.pi, waves), rng.uniform(0.3, 1.0, waves)
+        wave = sum(amp[k] * np.sin(2 * np.pi * (kx[k] * xx + ky[k] * yy) + phase[k]) for k in range(waves))
+        out[..., c] = 0.55 + 0.4 * wave / np.abs(amp).sum()
+    return np.clip(out, 0.0, 1.0).astype(np.float32)
