@@ -732,6 +732,69 @@ SNERF_API int64_t snerf_smpl_estimator_workspace_bytes(int64_t N, int human_size
 SNERF_API int snerf_smpl_estimator_fwd_f32(const snerf_smpl_estimator *net, const float *images, int64_t N, float *out, void *workspace,
                               int64_t workspace_bytes, snerf_stream_t stream);
 
+/* ---- LPIPS: the VGG16 feature stack and the fused tap distance (util/scores.py:286-456; csrc/conv_block.hip, csrc/lpips.hip) ----
+ * The convolution block with a tap: snerf_conv3x3_block_f32's rule, chain and bits, written to the un-pooled map y_full [N,Co,H,W]
+ *   when it is not NULL and to the pooled map y_pool [N,Co,H/2,W/2] when it is not NULL, both from the same accumulators in one
+ *   launch.  One of the two at least.  1 <= Ci, Co <= 512; H, W >= 1, and >= 2 with y_pool; the other refusals of
+ *   snerf_conv3x3_block_f32, on the host, before anything touches a device; a bad scalar is an error whatever N is, N = 0 is
+ *   SNERF_OK whatever the pointers are.  For Ci, Co <= 256 either output has the bits snerf_conv3x3_block_f32 gives it.
+ *   Above 256 input channels the chain over k is segmented: it starts again at zero every 128 channels (1152 elements) and the
+ *   segment sums are added in ascending order, the first to zero - one fp32 chain of 4608 terms measured 8.1 times the fp32 CPU
+ *   convolution's error against float64, a chain of 1152 with three additions 4.1 times.  Still one fixed order that depends on Ci
+ *   alone. */
+SNERF_API int snerf_conv3x3_block_tap_f32(const float *x, int64_t N, int Ci, int64_t H, int64_t W, const float *w, const float *scale,
+                              const float *shift, int Co, int relu, float *y_full, float *y_pool, snerf_stream_t stream);
+/* The distance of two feature maps fx, fy [N,C,h,w] (contiguous fp32) under channel weights wl [C] -> out [N]:
+ *   out[n] = (1 / (h w)) sum_p sum_c wl[c] (x^[c,p] - y^[c,p])^2
+ *   normalize != 0: x^[c,p] = fx[c,p] / (sqrt(sum_c fx[c,p]^2) + 1e-10) (ContentLoss.normalize, scores.py:403-411); else x^ = fx.
+ * Rule, per pixel p, operation by operation:
+ *   s   = sum over c = 0, 1, .. of fx[c,p]^2, accumulated in float64 (the products are exact there), rounded to fp32 once
+ *   nx  = sqrt(s) + 1e-10f      fp32: an IEEE square root, then the addition (ny from fy alike)
+ *   a   = fx[c,p] / nx          fp32, IEEE division (b = fy[c,p] / ny; without normalize a = fx, b = fy)
+ *   d   = a - b,  t = d d       fp32
+ *   acc = sum over c = 0, 1, .. of (double)wl[c] (double)t, one float64 fused multiply-add per channel
+ *   A tile is 64 consecutive pixels of the flattened h w map; its pixels' acc are added in float64 by the wavefront scan (lane order)
+ *   into workspace[n][tile]; a second launch adds an image's tiles - lane l the tiles l, l + 64, .. in that order, then the scan -
+ *   divides by h w in float64 and rounds to fp32 once.
+ * The difference form: fx == fy gives 0 exactly; a pixel whose features are all zero contributes 0 (nx = 1e-10, a = 0).  No atomics;
+ *   two calls give the same bits; an image's value does not depend on the rest of the batch.  Nothing of map size is stored.
+ * workspace: snerf_feature_distance_workspace_bytes(N, h, w) bytes (-1 on a bad argument), 8-byte aligned.
+ * SNERF_E_BADARG on the host: N negative or above 65535; C, h or w below 1; N C h w at 2^31 or above; with N > 0 a null fx, fy, wl or
+ *   out, a workspace that is null or too small.  SNERF_E_ALIGN: a misaligned workspace.  N = 0: SNERF_OK whatever the pointers are. */
+SNERF_API int64_t snerf_feature_distance_workspace_bytes(int64_t N, int64_t h, int64_t w);
+SNERF_API int snerf_feature_distance_f32(const float *fx, const float *fy, int64_t N, int64_t C, int64_t h, int64_t w, const float *wl,
+                              int normalize, float *out, void *workspace, int64_t workspace_bytes, snerf_stream_t stream);
+/* The network: device pointers to the tensors of torchvision's vgg16().features and of the reference's lpips_weights.pt. */
+typedef struct snerf_conv_wb {
+    const float *weight, *bias;                                         /* [Co,Ci,3,3], [Co] */
+} snerf_conv_wb;
+typedef struct snerf_vgg_lpips {
+    snerf_conv_wb conv[13];                                             /* VGG16 order: 2, 2, 3, 3, 3 convolutions per stage */
+    int32_t channels[5];                                                /* per stage, each 1 .. 512; VGG16: 64, 128, 256, 512, 512 */
+    const float *lin[5];                                                /* lin[l] [channels[l]]: the learned channel weights */
+    float mean[3], std[3];                                              /* the input standardisation (ImageNet's for LPIPS) */
+} snerf_vgg_lpips;
+/* x, y: N frames each of 3 channels, H x W pixels, fp32, both read through the element strides (sn, sc, sh, sw) as snerf_ssim_fwd_f32
+ *   reads them -> layers [N,5]: the distance of each tap; total [N] (may be NULL): their fp32 sum in ascending order of the stage.
+ * What runs: (v - mean[c]) / std[c] in fp32, a subtraction and then a division as scores.py:394 (not folded into the first
+ *   convolution: its zero padding is applied after the standardisation); x and y as ONE batch through the 13 convolutions
+ *   (snerf_conv3x3_block_tap_f32's kernel with scale = 1, shift = bias, ReLU); the taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3,
+ *   each followed by its distance with normalize on (the kernel of snerf_feature_distance_f32), the first four also pooled in the
+ *   same launch.  The entry adds no arithmetic of its own: layers has the bits of the two entries above called one by one.
+ * pool5 is not run, its output is unused: H, W >= 16 are accepted, where the reference (which runs it) raises below 32.
+ * Inputs are not checked for >= 0: the reference's assert is a device synchronisation.
+ * workspace: at least snerf_lpips_workspace_bytes(1, H, W, channels) bytes, 16-byte aligned.  The call walks the batch in chunks of
+ *   as many pairs as the workspace holds (snerf_lpips_workspace_bytes(n_pairs, ..) bytes hold n_pairs); the bits do not depend on
+ *   the workspace's size.  Nothing is allocated and nothing synchronises: the call - a linear chain of launches - can be captured
+ *   into a graph.  Same inputs, same bits; a frame pair's values do not depend on the rest of the batch.
+ * SNERF_E_BADARG on the host: a null net; a channel count outside 1 .. 512; a std that is zero or not finite, a mean that is not
+ *   finite; H or W below 16; N negative; 2 x the widest layer x H x W at 2^31 or above; with N > 0 a null pointer in the net, null x, y or layers,
+ *   a workspace that is null or smaller than one pair's.  SNERF_E_ALIGN: a workspace that is not 16-byte aligned.  N = 0: SNERF_OK. */
+SNERF_API int64_t snerf_lpips_workspace_bytes(int64_t n_pairs, int64_t H, int64_t W, const int32_t *channels);   /* -1 on a bad argument */
+SNERF_API int snerf_lpips_fwd_f32(const snerf_vgg_lpips *net, const float *x, const float *y, int64_t N, int64_t H, int64_t W, int64_t sn,
+                              int64_t sc, int64_t sh, int64_t sw, float *layers, float *total, void *workspace,
+                              int64_t workspace_bytes, snerf_stream_t stream);
+
 /* ---- SmplEstimator, training: the block with batch statistics and its backward (csrc/conv_train.hip) --------------------------
  *   z = conv3x3_pad1(x, w) + b              snerf_conv3x3_block_f32 with scale = 1, shift = b, relu = pool = 0 (x 1 is exact)
  *   mean, invstd                            snerf_bn_stats_f32: per channel over M = N H W values, biased variance

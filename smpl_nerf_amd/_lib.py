@@ -66,6 +66,16 @@ class SmplEstimatorNet(ctypes.Structure):
                 ("human_size", c_int32)]
 
 
+class ConvWb(ctypes.Structure):
+    """struct snerf_conv_wb - one convolution of the VGG stack: device pointers to its weight and bias."""
+    _fields_ = [("weight", _P), ("bias", _P)]
+
+
+class VggLpipsNet(ctypes.Structure):
+    """struct snerf_vgg_lpips - the 13 convolutions of vgg16().features, the five lin vectors, the input standardisation."""
+    _fields_ = [("conv", ConvWb * 13), ("channels", c_int32 * 5), ("lin", _P * 5), ("mean", c_float * 3), ("std", c_float * 3)]
+
+
 class MeshRenderArgs(ctypes.Structure):
     """struct snerf_mesh_render_args - the shading constants and flags of snerf_mesh_render_f32."""
     _fields_ = [("ambient", c_float), ("intensity", c_float), ("background", c_float * 3), ("flags", c_int32)]
@@ -202,6 +212,13 @@ SIGNATURES = {
     "snerf_conv3x3_block_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
     "snerf_smpl_estimator_workspace_bytes": (c_int64, [c_int64, c_int]),
     "snerf_smpl_estimator_fwd_f32": (c_int, [POINTER(SmplEstimatorNet), _P, c_int64, _P, _P, c_int64, _P]),
+    # LPIPS: the convolution block with a tap, the tap distance, the whole metric (csrc/conv_block.hip, csrc/lpips.hip)
+    "snerf_conv3x3_block_tap_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, _P, _P, _P, c_int, c_int, _P, _P, _P]),
+    "snerf_feature_distance_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "snerf_feature_distance_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, _P, c_int, _P, _P, c_int64, _P]),
+    "snerf_lpips_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, POINTER(c_int32)]),
+    "snerf_lpips_fwd_f32": (c_int, [POINTER(VggLpipsNet), _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P,
+                                    _P, c_int64, _P]),
     # SmplEstimator, training: batch statistics, the block's apply and backward, the convolution's gradients (csrc/conv_train.hip)
     "snerf_bn_stats_scratch_floats": (c_int64, [c_int64, c_int, c_int64, c_int64]),
     "snerf_bn_stats_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, c_double, c_double, _P, _P, _P, _P, _P, _P]),

@@ -8,7 +8,8 @@
 // Tile.  A workgroup of 4 waves owns 16 x 16 output pixels of one image and 16 MT output channels (MT = 1, 2, 4 by Co).  A wave owns
 // an 8 x 8 quadrant = 4 x 4 pool windows.  Its 4 B tiles are the 4 positions (dy, dx) of a pool window: column p = lane & 15 of tile
 // (dy, dx) is pixel (2 (p >> 2) + dy, 2 (p & 3) + dx) of the quadrant.  So the four pixels of a window are four accumulators of ONE
-// lane, and the epilogue - scale, shift, ReLU, the 2 x 2 max - stays in registers; with pooling on the un-pooled map is never stored.
+// lane, and the epilogue - scale, shift, ReLU, the 2 x 2 max - stays in registers; with pooling on the un-pooled map is never stored,
+// unless the caller asks for it as well (snerf_conv3x3_block_tap_f32: both maps from the same accumulators in one launch).
 //
 // LDS.  The reduction is walked in chunks of 8 input channels = 72 elements = 18 MFMA steps.  Per chunk:
 //   s_in [8][18][20]  the 16 x 16 input tile with its one-pixel halo; positions outside the image and channels past Ci are written
@@ -19,6 +20,10 @@
 // Summation order.  Every output element is ONE accumulator chain over k = 0, 1, .. in steps of 4, padded with zero products up to
 // the next multiple of 4 after 9 Ci (the chunks before the last hold 72 = 18 x 4 elements).  The chain depends on Ci alone: not on
 // N, not on the grid, not on where the pixel lies in a tile.  No atomics.
+// Above 256 input channels (the tap entry and the LPIPS stack alone: up to 512) the chain is segmented: it starts again at zero every
+// 128 channels = 1152 elements, and the segment sums are added in ascending order, the first to zero.  One chain of 4608 fp32 terms
+// measured 8.1 times the fp32 CPU convolution's error against float64 on random inputs (the rule of DESIGN.md section 8g allows 8);
+// up to 256 channels the chain, and so every bit, is what it was.
 #include <math.h>
 
 #include <algorithm>
@@ -42,11 +47,11 @@ constexpr int CB_GRID_X = 1 << 16;             // (image, tile) pairs per grid r
 
 struct ConvArgs {
     const float *x, *w, *scale, *shift;
-    float *y;
-    int Ci, Co, H, W, Ho, Wo;     // Ho, Wo: the extents of y (H / 2, W / 2 with pooling)
+    float *y_full, *y_pool;       // the un-pooled map [N,Co,H,W] and the pooled one [N,Co,Hp,Wp]; either may be null, not both
+    int Ci, Co, H, W, Hp, Wp;     // Hp, Wp = H / 2, W / 2
     int tiles_x, tiles;           // 16 x 16 tiles per row and per image
     int64_t jobs;                 // N tiles
-    int relu, pool;
+    int relu;
 };
 
 // A chunk travels global memory -> registers -> LDS, so that the next chunk's loads are in flight while this one multiplies.  The
@@ -95,7 +100,7 @@ __device__ __forceinline__ void conv_chunk_store(float *s_in, float *s_w, int ti
         if (k0 + j < CB_KC) s_w[co * CB_WP + k0 + j] = rw[j];
 }
 
-template <int MT>
+template <int MT, bool SEG>
 __global__ __launch_bounds__(CB_THREADS) void conv3x3_block_kernel(ConvArgs G) {
     __shared__ float s_in[CB_CI * CB_PLANE];
     __shared__ float s_w[16 * MT * CB_WP];
@@ -119,6 +124,13 @@ __global__ __launch_bounds__(CB_THREADS) void conv3x3_block_kernel(ConvArgs G) {
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int d = 0; d < 4; ++d) acc[m][d] = cf4{0.f, 0.f, 0.f, 0.f};
+    cf4 base[SEG ? MT : 1][4];   // SEG: the sum of the segments before this one
+    if constexpr (SEG) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) base[m][d] = cf4{0.f, 0.f, 0.f, 0.f};
+    }
     const float *xn = G.x + n * G.Ci * (int64_t)G.H * G.W;
     const float *pb = s_in + (qy * 8 + 2 * py) * CB_LW + qx * 8 + 2 * px;
     const float *pa = s_w + p * CB_WP + kq;
@@ -130,6 +142,14 @@ __global__ __launch_bounds__(CB_THREADS) void conv3x3_block_kernel(ConvArgs G) {
         conv_chunk_store<MT>(s_in, s_w, tid, rin, rw);
         __syncthreads();
         if (c0 + CB_CI < G.Ci) conv_chunk_load<MT>(G, xn, c0 + CB_CI, y0, x0, co0, tid, rin, rw);
+        if constexpr (SEG) {
+            if (c0 > 0 && c0 % CB_SEG_C == 0) {   // (uniform) a new segment: its chain starts at zero
+#pragma unroll
+                for (int m = 0; m < MT; ++m)
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) base[m][d] = base[m][d] + acc[m][d], acc[m][d] = cf4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
 #pragma unroll
         for (int s = 0; s < CB_STEPS; ++s) {
             if (s < steps) {   // (uniform: the last chunk of a Ci that is no multiple of 8 is shorter)
@@ -146,6 +166,12 @@ __global__ __launch_bounds__(CB_THREADS) void conv3x3_block_kernel(ConvArgs G) {
             }
         }
     }
+    if constexpr (SEG) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) acc[m][d] = base[m][d] + acc[m][d];
+    }
     // D layout: acc[m][2 dy + dx][r] = channel co0 + 16 m + 4 kq + r at pixel (y0 + 8 qy + 2 py + dy, x0 + 8 qx + 2 px + dx)
     const int oy = y0 + 8 * qy + 2 * py, ox = x0 + 8 * qx + 2 * px;
 #pragma unroll
@@ -154,20 +180,22 @@ __global__ __launch_bounds__(CB_THREADS) void conv3x3_block_kernel(ConvArgs G) {
         for (int r = 0; r < 4; ++r) {
             const int co = co0 + 16 * m + 4 * kq + r;
             if (co >= G.Co) continue;
-            const float sc = G.scale[co], sh = G.shift[co];
+            const float sc = G.scale ? G.scale[co] : 1.f, sh = G.shift[co];   // (no scale: x 1 is exact, the bits of a vector of ones)
             float v[4];
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 v[d] = __fadd_rn(__fmul_rn(acc[m][d][r], sc), sh);
                 if (G.relu) v[d] = fmaxf(v[d], 0.f);
             }
-            float *yc = G.y + (n * G.Co + co) * (int64_t)G.Ho * G.Wo;
-            if (G.pool) {
-                if ((oy >> 1) < G.Ho && (ox >> 1) < G.Wo) yc[(int64_t)(oy >> 1) * G.Wo + (ox >> 1)] = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-            } else {
+            if (G.y_pool) {
+                float *yc = G.y_pool + (n * G.Co + co) * (int64_t)G.Hp * G.Wp;
+                if ((oy >> 1) < G.Hp && (ox >> 1) < G.Wp) yc[(int64_t)(oy >> 1) * G.Wp + (ox >> 1)] = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+            }
+            if (G.y_full) {   // the tap: the same four values, before the max
+                float *yc = G.y_full + (n * G.Co + co) * (int64_t)G.H * G.W;
 #pragma unroll
                 for (int d = 0; d < 4; ++d)
-                    if (oy + (d >> 1) < G.Ho && ox + (d & 1) < G.Wo) yc[(int64_t)(oy + (d >> 1)) * G.Wo + ox + (d & 1)] = v[d];
+                    if (oy + (d >> 1) < G.H && ox + (d & 1) < G.W) yc[(int64_t)(oy + (d >> 1)) * G.W + ox + (d & 1)] = v[d];
             }
         }
 }
@@ -194,9 +222,9 @@ static bool below_2_31(int64_t a, int64_t b, int64_t c, int64_t d) {
 }
 
 // the scalar checks of a block (an error whatever N is); *Ho, *Wo: the extents of y
-int conv_check(const char *what, int64_t N, int Ci, int64_t H, int64_t W, int Co, int pool, int64_t *Ho, int64_t *Wo) {
-    if (Ci < 1 || Ci > CB_MAX_C) return fail(SNERF_E_BADARG, "%s: Ci = %d is outside 1 .. %d", what, Ci, CB_MAX_C);
-    if (Co < 1 || Co > CB_MAX_C) return fail(SNERF_E_BADARG, "%s: Co = %d is outside 1 .. %d", what, Co, CB_MAX_C);
+int conv_check(const char *what, int64_t N, int Ci, int64_t H, int64_t W, int Co, int pool, int64_t *Ho, int64_t *Wo, int max_c) {
+    if (Ci < 1 || Ci > max_c) return fail(SNERF_E_BADARG, "%s: Ci = %d is outside 1 .. %d", what, Ci, max_c);
+    if (Co < 1 || Co > max_c) return fail(SNERF_E_BADARG, "%s: Co = %d is outside 1 .. %d", what, Co, max_c);
     if (N < 0) return fail(SNERF_E_BADARG, "%s: N = %lld is negative", what, (long long)N);
     const int64_t lo = pool ? 2 : 1;
     if (H < lo || H > 0x7fffffffLL) return fail(SNERF_E_BADARG, "%s: H = %lld is outside %d .. 2^31 - 1%s", what, (long long)H, (int)lo, pool ? " (pooling)" : "");
@@ -208,10 +236,10 @@ int conv_check(const char *what, int64_t N, int Ci, int64_t H, int64_t W, int Co
     return SNERF_OK;
 }
 
-// one block on checked arguments, N > 0
-int conv_launch(const char *what, const float *x, int64_t N, int Ci, int H, int W, const float *w, const float *scale, const float *shift,
-                int Co, int relu, int pool, float *y, hipStream_t s) {
-    ConvArgs G{x, w, scale, shift, y, Ci, Co, H, W, pool ? H / 2 : H, pool ? W / 2 : W, 0, 0, 0, relu ? 1 : 0, pool ? 1 : 0};
+// one block on checked arguments, N > 0, to either or both of its outputs
+int conv_launch_tap(const char *what, const float *x, int64_t N, int Ci, int H, int W, const float *w, const float *scale,
+                    const float *shift, int Co, int relu, float *y_full, float *y_pool, hipStream_t s) {
+    ConvArgs G{x, w, scale, shift, y_full, y_pool, Ci, Co, H, W, H / 2, W / 2, 0, 0, 0, relu ? 1 : 0};
     G.tiles_x = (W + CB_TILE - 1) / CB_TILE;
     G.tiles = G.tiles_x * ((H + CB_TILE - 1) / CB_TILE);
     G.jobs = N * G.tiles;                                        // (<= N H W < 2^31)
@@ -223,10 +251,18 @@ int conv_launch(const char *what, const float *x, int64_t N, int Ci, int H, int 
     while (mt > 1 && G.jobs * ((Co + 16 * mt - 1) / (16 * mt)) < 2 * (int64_t)n_cu) mt >>= 1;
     const dim3 grid((unsigned)std::min<int64_t>(G.jobs, CB_GRID_X), (unsigned)((Co + 16 * mt - 1) / (16 * mt)),
                     (unsigned)((G.jobs + CB_GRID_X - 1) / CB_GRID_X));   // z <= 2^15
-    if (mt == 1) hipLaunchKernelGGL(conv3x3_block_kernel<1>, grid, dim3(CB_THREADS), 0, s, G);
-    else if (mt == 2) hipLaunchKernelGGL(conv3x3_block_kernel<2>, grid, dim3(CB_THREADS), 0, s, G);
-    else hipLaunchKernelGGL(conv3x3_block_kernel<4>, grid, dim3(CB_THREADS), 0, s, G);
+    if (Ci > CB_MAX_C) {   // the segmented chain
+        if (mt == 1) hipLaunchKernelGGL((conv3x3_block_kernel<1, true>), grid, dim3(CB_THREADS), 0, s, G);
+        else if (mt == 2) hipLaunchKernelGGL((conv3x3_block_kernel<2, true>), grid, dim3(CB_THREADS), 0, s, G);
+        else hipLaunchKernelGGL((conv3x3_block_kernel<4, true>), grid, dim3(CB_THREADS), 0, s, G);
+    } else if (mt == 1) hipLaunchKernelGGL((conv3x3_block_kernel<1, false>), grid, dim3(CB_THREADS), 0, s, G);
+    else if (mt == 2) hipLaunchKernelGGL((conv3x3_block_kernel<2, false>), grid, dim3(CB_THREADS), 0, s, G);
+    else hipLaunchKernelGGL((conv3x3_block_kernel<4, false>), grid, dim3(CB_THREADS), 0, s, G);
     return check_launch(what);
+}
+int conv_launch(const char *what, const float *x, int64_t N, int Ci, int H, int W, const float *w, const float *scale, const float *shift,
+                int Co, int relu, int pool, float *y, hipStream_t s) {
+    return conv_launch_tap(what, x, N, Ci, H, W, w, scale, shift, Co, relu, pool ? nullptr : y, pool ? y : nullptr, s);
 }
 
 // ---- the network: models/smpl_estimator.py:14-30 -------------------------------------------------------------------------------
@@ -247,6 +283,18 @@ extern "C" int snerf_conv3x3_block_f32(const float *x, int64_t N, int Ci, int64_
     if (!x || !w || !scale || !shift || !y)
         return fail(SNERF_E_BADARG, "conv3x3_block: null pointer (%s)", !x ? "x" : !w ? "w" : !scale ? "scale" : !shift ? "shift" : "y");
     return conv_launch("conv3x3_block", x, N, Ci, (int)H, (int)W, w, scale, shift, Co, relu, pool, y, (hipStream_t)stream);
+}
+
+extern "C" int snerf_conv3x3_block_tap_f32(const float *x, int64_t N, int Ci, int64_t H, int64_t W, const float *w, const float *scale,
+                                           const float *shift, int Co, int relu, float *y_full, float *y_pool, snerf_stream_t stream) {
+    using namespace snerf;
+    int64_t Ho, Wo;
+    if (int rc = conv_check("conv3x3_block_tap", N, Ci, H, W, Co, y_pool != nullptr, &Ho, &Wo, CB_TAP_MAX_C)) return rc;
+    if (N == 0) return SNERF_OK;
+    if (!y_full && !y_pool) return fail(SNERF_E_BADARG, "conv3x3_block_tap: y_full and y_pool are both null: one output at least");
+    if (!x || !w || !scale || !shift)
+        return fail(SNERF_E_BADARG, "conv3x3_block_tap: null pointer (%s)", !x ? "x" : !w ? "w" : !scale ? "scale" : "shift");
+    return conv_launch_tap("conv3x3_block_tap", x, N, Ci, (int)H, (int)W, w, scale, shift, Co, relu, y_full, y_pool, (hipStream_t)stream);
 }
 
 extern "C" int64_t snerf_smpl_estimator_workspace_bytes(int64_t N, int human_size) {

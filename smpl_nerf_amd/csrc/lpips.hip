@@ -1,0 +1,244 @@
+// LPIPS (util/scores.py:286-456: ContentLoss with normalize_features, as LPIPS() configures it) on a VGG16-shaped feature stack:
+// the distance between two feature maps, and the whole metric as one call.  The convolutions are csrc/conv_block.hip's.
+//
+// Distance of two maps fx, fy [N,C,h,w] with channel weights wl [C], per image n:
+//   out[n] = (1 / (h w)) sum_p sum_c wl[c] (x^[c,p] - y^[c,p])^2        x^[c,p] = fx[c,p] / (sqrt(sum_c fx[c,p]^2) + 1e-10)
+// (scores.py:372, :403-411; without `normalize` x^ = fx).  The rule, operation by operation, per pixel p:
+//   s   = the sum over c = 0, 1, .. of fx[c,p]^2 in float64 (the products are exact there), rounded to fp32 once
+//   nx  = sqrt(s) + 1e-10f                      fp32, IEEE square root, then the addition              (ny from fy alike)
+//   a   = fx[c,p] / nx,  b = fy[c,p] / ny       fp32, IEEE divisions                                  (a = fx, b = fy without normalize)
+//   d   = a - b,  t = d d                       fp32
+//   acc = the sum over c = 0, 1, .. of (double)wl[c] (double)t in float64, one fma per channel
+// The difference form: fx == fy gives d = 0 and out = 0 exactly; a pixel whose features are all zero has nx = 1e-10, a = 0.
+// Pixels: a tile is 64 consecutive pixels of the flattened h w map, one per lane (coalesced along w); the tile's sum goes through
+// the wave's DPP scan in float64 to workspace[n][tile]; a second launch adds an image's tiles in a fixed order (lane l takes tiles
+// l, l + 64, ..., then the scan), divides by h w in float64 and rounds to fp32 once.
+//
+// Mapping.  Workgroup = one wave = one tile of one image.  Two passes over c: the norms, then the differences; a tile's working set is
+// 64 pixels x C channels x 2 maps (256 KB at C = 512), so the second pass is served by the L2.  Nothing of map size is stored, no
+// atomics, no LDS; an image's value depends on its own pixels alone, and two calls give the same bits.
+#include <math.h>
+
+#include <algorithm>
+
+#include "conv_block.h"
+
+namespace snerf {
+
+constexpr int FD_TILE = WAVE;                       // pixels per workgroup
+constexpr float LPIPS_EPS = 1e-10f;                 // scores.py:179
+constexpr int LPIPS_MIN_SIDE = 16;                  // four pools leave the fifth stage one pixel at least
+constexpr int VGG_CONVS[5] = {2, 2, 3, 3, 3};
+
+struct DistArgs {
+    const float *fx, *fy, *wl;
+    int C, hw, tiles, normalize;
+    double *part;   // [N][tiles]
+};
+
+__global__ __launch_bounds__(FD_TILE) void feature_distance_kernel(DistArgs A) {
+    const int tile = blockIdx.x, n = blockIdx.y, p = tile * FD_TILE + (int)threadIdx.x;
+    const bool in = p < A.hw;
+    const int64_t base = (int64_t)n * A.C * A.hw + (in ? p : 0);
+    const float *x = A.fx + base, *y = A.fy + base;
+    float nx = 1.f, ny = 1.f;
+    if (A.normalize) {
+        double sx = 0.0, sy = 0.0;
+#pragma unroll 4
+        for (int c = 0; c < A.C; ++c) {
+            const double a = (double)x[(int64_t)c * A.hw], b = (double)y[(int64_t)c * A.hw];
+            sx = fma(a, a, sx), sy = fma(b, b, sy);
+        }
+        nx = __fadd_rn(__fsqrt_rn((float)sx), LPIPS_EPS), ny = __fadd_rn(__fsqrt_rn((float)sy), LPIPS_EPS);
+    }
+    double acc = 0.0;
+#pragma unroll 4
+    for (int c = 0; c < A.C; ++c) {
+        float a = x[(int64_t)c * A.hw], b = y[(int64_t)c * A.hw];
+        if (A.normalize) a = __fdiv_rn(a, nx), b = __fdiv_rn(b, ny);
+        const float d = __fsub_rn(a, b), t = __fmul_rn(d, d);
+        acc = fma((double)A.wl[c], (double)t, acc);
+    }
+    const double sum = wave_sum(in ? acc : 0.0);
+    if (threadIdx.x == 0) A.part[(int64_t)n * A.tiles + tile] = sum;
+}
+
+// one wave per image: out[n out_stride] = the sum of its tiles / (h w); with `total`, total[n] = the ascending fp32 sum of the
+// n_total values out[n out_stride - (n_total - 1)] .. out[n out_stride] (the stage distances of one image: the last of them is this one)
+__global__ __launch_bounds__(WAVE) void feature_distance_reduce_kernel(const double *part, int tiles, double pixels, float *out,
+                                                                        int out_stride, float *total, int n_total) {
+    const int lane = threadIdx.x, n = blockIdx.x;
+    const double *p = part + (int64_t)n * tiles;
+    double s = 0.0;
+    for (int t = lane; t < tiles; t += WAVE) s += p[t];
+    s = wave_sum(s);
+    if (lane != 0) return;
+    const float v = (float)(s / pixels);
+    float *o = out + (int64_t)n * out_stride;
+    *o = v;
+    if (total) {
+        float sum = n_total > 1 ? o[1 - n_total] : v;
+        for (int l = 2 - n_total; l < 0; ++l) sum = __fadd_rn(sum, o[l]);
+        if (n_total > 1) sum = __fadd_rn(sum, v);
+        total[n] = sum;
+    }
+}
+
+static int64_t dist_tiles(int64_t h, int64_t w) { return (h * w + FD_TILE - 1) / FD_TILE; }
+
+static int dist_check(const char *op, int64_t N, int64_t C, int64_t h, int64_t w) {
+    if (N < 0) return fail(SNERF_E_BADARG, "%s: N = %lld is negative", op, (long long)N);
+    if (C < 1 || C > 0x7fffffffLL) return fail(SNERF_E_BADARG, "%s: C = %lld is outside 1 .. 2^31 - 1", op, (long long)C);
+    if (h < 1 || h > 0x7fffffffLL) return fail(SNERF_E_BADARG, "%s: h = %lld is outside 1 .. 2^31 - 1", op, (long long)h);
+    if (w < 1 || w > 0x7fffffffLL) return fail(SNERF_E_BADARG, "%s: w = %lld is outside 1 .. 2^31 - 1", op, (long long)w);
+    if (N > 65535) return fail(SNERF_E_BADARG, "%s: N = %lld is above 65535 images a call", op, (long long)N);
+    if ((unsigned __int128)std::max<int64_t>(N, 1) * (unsigned __int128)C * (unsigned __int128)h * (unsigned __int128)w >= ((unsigned __int128)1 << 31))
+        return fail(SNERF_E_BADARG, "%s: N C h w = %lld x %lld x %lld x %lld reaches 2^31 elements", op, (long long)N, (long long)C, (long long)h,
+                    (long long)w);
+    return SNERF_OK;
+}
+
+// the two launches on checked arguments, N > 0: out[n out_stride], n < N
+static int dist_launch(const char *op, const float *fx, const float *fy, int N, int C, int h, int w, const float *wl, int normalize,
+                       float *out, int out_stride, float *total, int n_total, double *part, hipStream_t s) {
+    const int tiles = (int)dist_tiles(h, w);
+    DistArgs A{fx, fy, wl, C, h * w, tiles, normalize ? 1 : 0, part};
+    hipLaunchKernelGGL(feature_distance_kernel, dim3((unsigned)tiles, (unsigned)N), dim3(FD_TILE), 0, s, A);
+    hipLaunchKernelGGL(feature_distance_reduce_kernel, dim3((unsigned)N), dim3(WAVE), 0, s, (const double *)part, tiles,
+                       (double)h * (double)w, out, out_stride, total, n_total);
+    return check_launch(op);
+}
+
+// (v - mean[c]) / std[c] (scores.py:394: a subtraction, then a division) of m frames of x and m frames of y, read through the
+// element strides, into one contiguous batch [2 m,3,H,W]: x's frames first
+struct NormArgs {
+    const float *x, *y;
+    int64_t sn, sc, sh, sw;
+    int m, H, W;
+    float mean[3], std[3];
+    float *out;
+};
+__global__ __launch_bounds__(256) void lpips_normalize_kernel(NormArgs A) {
+    const int hw = A.H * A.W, p = blockIdx.x * 256 + (int)threadIdx.x, c = blockIdx.y, i = blockIdx.z;
+    if (p >= hw) return;
+    const int h = p / A.W, w = p - h * A.W;
+    const float *src = i < A.m ? A.x + (int64_t)i * A.sn : A.y + (int64_t)(i - A.m) * A.sn;
+    const float v = src[(int64_t)c * A.sc + (int64_t)h * A.sh + (int64_t)w * A.sw];
+    A.out[((int64_t)i * 3 + c) * hw + p] = __fdiv_rn(__fsub_rn(v, A.mean[c]), A.std[c]);
+}
+
+// floats and partial sums one image pair needs: two activation buffers of F floats, one of P (the normalised input, the pooled maps)
+struct LpipsPlan {
+    int64_t F, P, tiles, bytes;   // per pair
+    int64_t max_pairs;            // pairs a chunk may hold: 2 m (widest layer) H W stays below 2^31
+};
+static int lpips_plan(const char *op, int64_t H, int64_t W, const int32_t *channels, LpipsPlan &L) {
+    if (!channels) return fail(SNERF_E_BADARG, "%s: channels is null", op);
+    for (int l = 0; l < 5; ++l)
+        if (channels[l] < 1 || channels[l] > CB_TAP_MAX_C)
+            return fail(SNERF_E_BADARG, "%s: channels[%d] = %d is outside 1 .. %d", op, l, channels[l], CB_TAP_MAX_C);
+    if (H < LPIPS_MIN_SIDE || H > 0x7fffffffLL) return fail(SNERF_E_BADARG, "%s: H = %lld is outside %d .. 2^31 - 1", op, (long long)H, LPIPS_MIN_SIDE);
+    if (W < LPIPS_MIN_SIDE || W > 0x7fffffffLL) return fail(SNERF_E_BADARG, "%s: W = %lld is outside %d .. 2^31 - 1", op, (long long)W, LPIPS_MIN_SIDE);
+    unsigned __int128 F = 0, P = (unsigned __int128)6 * H * W;
+    int64_t h = H, w = W, cmax = 3;
+    for (int l = 0; l < 5; ++l, h /= 2, w /= 2) {
+        F = std::max(F, (unsigned __int128)2 * channels[l] * h * w);
+        if (l < 4) P = std::max(P, (unsigned __int128)2 * channels[l] * (h / 2) * (w / 2));
+        cmax = std::max<int64_t>(cmax, channels[l]);
+    }
+    const unsigned __int128 per_image = (unsigned __int128)cmax * H * W;
+    if (2 * per_image >= ((unsigned __int128)1 << 31))
+        return fail(SNERF_E_BADARG, "%s: 2 x %lld channels x H W = %lld x %lld reaches 2^31 elements", op, (long long)cmax, (long long)H, (long long)W);
+    L.F = (int64_t)F, L.P = (int64_t)P, L.tiles = dist_tiles(H, W);
+    L.bytes = (4 * (2 * L.F + L.P) + 8 * L.tiles + 15) / 16 * 16;
+    L.max_pairs = std::min<int64_t>((int64_t)((((unsigned __int128)1 << 31) - 1) / (2 * per_image)), 32767);
+    return SNERF_OK;
+}
+
+}  // namespace snerf
+
+extern "C" int64_t snerf_feature_distance_workspace_bytes(int64_t N, int64_t h, int64_t w) {
+    using namespace snerf;
+    if (dist_check("feature_distance_workspace_bytes", N, 1, h, w)) return -1;
+    return N * dist_tiles(h, w) * (int64_t)sizeof(double);
+}
+
+extern "C" int snerf_feature_distance_f32(const float *fx, const float *fy, int64_t N, int64_t C, int64_t h, int64_t w, const float *wl,
+                                          int normalize, float *out, void *workspace, int64_t workspace_bytes, snerf_stream_t stream) {
+    using namespace snerf;
+    if (int rc = dist_check("feature_distance", N, C, h, w)) return rc;
+    if (N == 0) return SNERF_OK;
+    if (!fx || !fy || !wl || !out)
+        return fail(SNERF_E_BADARG, "feature_distance: null pointer (%s)", !fx ? "fx" : !fy ? "fy" : !wl ? "wl" : "out");
+    const int64_t need = N * dist_tiles(h, w) * (int64_t)sizeof(double);
+    if (!workspace || workspace_bytes < need)
+        return fail(SNERF_E_BADARG, "feature_distance: workspace of %lld bytes, need %lld", (long long)(workspace ? workspace_bytes : 0), (long long)need);
+    if (!aligned(workspace, 8)) return fail(SNERF_E_ALIGN, "feature_distance: workspace %p is not 8-byte aligned", workspace);
+    return dist_launch("feature_distance", fx, fy, (int)N, (int)C, (int)h, (int)w, wl, normalize, out, 1, nullptr, 0, (double *)workspace,
+                       (hipStream_t)stream);
+}
+
+extern "C" int64_t snerf_lpips_workspace_bytes(int64_t n_pairs, int64_t H, int64_t W, const int32_t *channels) {
+    using namespace snerf;
+    LpipsPlan L;
+    if (n_pairs < 0) return fail(SNERF_E_BADARG, "lpips_workspace_bytes: n_pairs = %lld is negative", (long long)n_pairs);
+    if (lpips_plan("lpips_workspace_bytes", H, W, channels, L)) return -1;
+    if (n_pairs > 0x7fffffffffffffffLL / L.bytes) return fail(SNERF_E_BADARG, "lpips_workspace_bytes: n_pairs = %lld overflows", (long long)n_pairs);
+    return n_pairs * L.bytes;
+}
+
+extern "C" int snerf_lpips_fwd_f32(const snerf_vgg_lpips *net, const float *x, const float *y, int64_t N, int64_t H, int64_t W, int64_t sn,
+                                   int64_t sc, int64_t sh, int64_t sw, float *layers, float *total, void *workspace, int64_t workspace_bytes,
+                                   snerf_stream_t stream) {
+    using namespace snerf;
+    if (!net) return fail(SNERF_E_BADARG, "lpips_fwd: null net");
+    LpipsPlan L;
+    if (int rc = lpips_plan("lpips_fwd", H, W, net->channels, L)) return rc;
+    for (int c = 0; c < 3; ++c) {
+        if (!isfinite(net->std[c]) || net->std[c] == 0.f) return fail(SNERF_E_BADARG, "lpips_fwd: std[%d] = %g is zero or not finite", c, (double)net->std[c]);
+        if (!isfinite(net->mean[c])) return fail(SNERF_E_BADARG, "lpips_fwd: mean[%d] = %g is not finite", c, (double)net->mean[c]);
+    }
+    if (N < 0) return fail(SNERF_E_BADARG, "lpips_fwd: N = %lld is negative", (long long)N);
+    if (N == 0) return SNERF_OK;
+    for (int i = 0; i < 13; ++i)
+        if (!net->conv[i].weight || !net->conv[i].bias) return fail(SNERF_E_BADARG, "lpips_fwd: null pointer in convolution %d", i + 1);
+    for (int l = 0; l < 5; ++l)
+        if (!net->lin[l]) return fail(SNERF_E_BADARG, "lpips_fwd: null pointer (lin[%d])", l);
+    if (!x || !y || !layers) return fail(SNERF_E_BADARG, "lpips_fwd: null pointer (%s)", !x ? "x" : !y ? "y" : "layers");
+    if (!workspace || workspace_bytes < L.bytes)
+        return fail(SNERF_E_BADARG, "lpips_fwd: workspace of %lld bytes, need %lld for one image pair", (long long)(workspace ? workspace_bytes : 0),
+                    (long long)L.bytes);
+    if (!aligned(workspace, 16)) return fail(SNERF_E_ALIGN, "lpips_fwd: workspace %p is not 16-byte aligned", workspace);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t chunk = std::min(std::min(N, workspace_bytes / L.bytes), L.max_pairs);
+    // the chunk's buffers: stage l runs P -> A -> B [-> A], its last convolution writing the tap and, pooled, the next stage's input to P
+    float *A = static_cast<float *>(workspace), *B = A + chunk * L.F, *P = B + chunk * L.F;
+    double *part = reinterpret_cast<double *>(P + chunk * L.P);   // (8-byte aligned: F and P are even)
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+        const int m = (int)std::min(chunk, N - n0);
+        NormArgs Z{x + n0 * sn, y + n0 * sn, sn, sc, sh, sw, m, (int)H, (int)W, {net->mean[0], net->mean[1], net->mean[2]},
+                   {net->std[0], net->std[1], net->std[2]}, P};
+        hipLaunchKernelGGL(lpips_normalize_kernel, dim3((unsigned)((H * W + 255) / 256), 3, (unsigned)(2 * m)), dim3(256), 0, s, Z);
+        if (int rc = check_launch("lpips_fwd(normalize)")) return rc;
+        const float *in = P;
+        int h = (int)H, w = (int)W, ci = 3, conv = 0;
+        for (int l = 0; l < 5; ++l, h /= 2, w /= 2) {
+            const int co = net->channels[l];
+            float *bufs[2] = {A, B};
+            for (int j = 0; j < VGG_CONVS[l]; ++j, ++conv) {
+                const bool last = j == VGG_CONVS[l] - 1;
+                float *full = bufs[j & 1];   // (the last convolution's `full` is the tap)
+                if (int rc = conv_launch_tap("lpips_fwd(conv)", in, 2 * m, ci, h, w, net->conv[conv].weight, nullptr /* scale = 1 */, net->conv[conv].bias, co, 1,
+                                             full, last && l < 4 ? P : nullptr, s))
+                    return rc;
+                in = full, ci = co;
+            }
+            const int64_t map = (int64_t)co * h * w;
+            if (int rc = dist_launch("lpips_fwd(distance)", in, in + m * map, m, co, h, w, net->lin[l], 1, layers + n0 * 5 + l, 5,
+                                     l == 4 && total ? total + n0 : nullptr, 5, part, s))
+                return rc;
+            in = P;
+        }
+    }
+    return SNERF_OK;
+}

@@ -15,6 +15,8 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     ssim / image_scores util/scores.py:88-173 (ssim) and :11-48 (img2mse, img2psnr): the scores of print_scores, on the device
     conv3x3_block       models/smpl_estimator.py:35-39: one conv - BatchNorm (eval) - ReLU - pool block of SmplEstimator, inference only
     conv3x3_bn_block    the same block under nn.Module.train(): BatchNorm on the batch statistics, differentiable to every input
+    lpips               util/scores.py:286-456 (ContentLoss as LPIPS() configures it) on the weights of a lpips.VggLpips; its parts:
+                        conv3x3_block_tap (the block's un-pooled and pooled maps from one launch) and feature_distance
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -1102,12 +1104,13 @@ def ssim(x, y, kernel_size: int = 11, kernel_sigma: float = 1.5, data_range=1., 
     return (ssim_val, cs) if full else ssim_val
 
 
-def image_scores(renders, truths, channels_first: bool = False, **ssim_kwargs):
-    """The scores of the reference's print_scores that need no network (util/scores.py:457-464; LPIPS needs VGG weights) of frames
-    [N,H,W,3] (channels_first=True: [N,3,H,W]) in ONE forward call: dict of 0-d device tensors
+def image_scores(renders, truths, channels_first: bool = False, lpips=None, **ssim_kwargs):
+    """The scores of the reference's print_scores (util/scores.py:457-464) of frames [N,H,W,3] (channels_first=True: [N,3,H,W]);
+    mse, psnr and ssim come from ONE forward call of the SSIM kernel: dict of 0-d device tensors
         mse   scores.py:28: the mean of (x - y)^2 over every pixel and channel - the kernel's per-channel sums, added in float64
         psnr  scores.py:47-48: -10 ln(mse) / ln(10)
         ssim  ssim(renders, truths, **ssim_kwargs)
+        lpips only with lpips=<a lpips.VggLpips on the frames' device>: ops.lpips(renders, truths, lpips), the batch mean (fp32)
     mse and psnr are float64 tensors (an fp32 ulp of a 30 dB PSNR is 2e-6, more than the error of the sums), ssim is fp32.  The
     images are taken to lie in [0, 1] for psnr, as the reference's img2psnr takes them.  Evaluation only: nothing here is
     differentiated through."""
@@ -1127,7 +1130,10 @@ def image_scores(renders, truths, channels_first: bool = False, **ssim_kwargs):
     if reduction != 'none':
         val = {'mean': torch.mean, 'sum': torch.sum}[reduction](val, dim=0)
     mse = sqerr.double().sum() / x.numel()
-    return {"mse": mse, "psnr": -10. * torch.log(mse) / math.log(10.), "ssim": val}
+    scores = {"mse": mse, "psnr": -10. * torch.log(mse) / math.log(10.), "ssim": val}
+    if lpips is not None:
+        scores["lpips"] = _lpips_op(x, y, lpips)      # (ops.lpips: the argument shadows its name here)
+    return scores
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1255,3 +1261,107 @@ def conv3x3_bn_block(x, weight, bias, bn_weight, bn_bias, running_mean=None, run
         raise RuntimeError("conv3x3_bn_block: momentum=None (the cumulative average) is not supported")
     return _ConvBnBlockFn.apply(x, weight, bias, bn_weight, bn_bias, running_mean, running_var, float(momentum), float(eps), bool(relu),
                                 bool(pool))[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# LPIPS (util/scores.py:286-456): the convolution with a tap, the tap distance, the metric (csrc/conv_block.hip, csrc/lpips.hip)
+# ------------------------------------------------------------------------------------------------
+def _forward_only(op, tensors):
+    for nm, t in tensors:
+        _need_cuda(nm, t)
+        if t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{op}: `{nm}` requires grad, but this op is forward only (LPIPS is a score here, not a training loss); "
+                               "call it under torch.no_grad() or detach the tensor")
+
+
+def conv3x3_block_tap(x, weight, scale, shift, relu: bool = True, full: bool = True, pool: bool = True):
+    """ops.conv3x3_block with both of its outputs from one launch: (y_full [N,Co,H,W] or None, y_pool [N,Co,H//2,W//2] or None), the
+    un-pooled map (the LPIPS "tap") and its 2 x 2 max from the same accumulators.  Ci, Co up to 512.  Either output has the bits
+    ops.conv3x3_block gives it.  Forward only, as ops.conv3x3_block."""
+    _forward_only("conv3x3_block_tap", (("x", x), ("weight", weight), ("scale", scale), ("shift", shift)))
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[1:]) != (x.shape[1], 3, 3):
+        raise RuntimeError(f"conv3x3_block_tap: x must be [N,Ci,H,W] and weight [Co,Ci,3,3], got {tuple(x.shape)} and {tuple(weight.shape)}")
+    if not (full or pool):
+        raise RuntimeError("conv3x3_block_tap: one of `full` and `pool` at least")
+    N, Ci, H, W = x.shape
+    Co = weight.shape[0]
+    if tuple(scale.shape) != (Co,) or tuple(shift.shape) != (Co,):
+        raise RuntimeError(f"conv3x3_block_tap: scale and shift must be [{Co}], got {tuple(scale.shape)} and {tuple(shift.shape)}")
+    x, weight, scale, shift = (t.detach().contiguous() for t in (x, weight, scale, shift))
+    y_full = torch.empty((N, Co, H, W), device=x.device, dtype=torch.float32) if full else None
+    y_pool = torch.empty((N, Co, H // 2, W // 2), device=x.device, dtype=torch.float32) if pool else None
+    with torch.cuda.device(x.device), _lib.timed(f"conv3x3_block_tap[{Ci}->{Co},{H}x{W}]"):
+        check(_lib.load().snerf_conv3x3_block_tap_f32(ptr(x), N, Ci, H, W, ptr(weight), ptr(scale), ptr(shift), Co, int(bool(relu)),
+                                                      ptr(y_full), ptr(y_pool), current_stream()), "snerf_conv3x3_block_tap_f32")
+    return y_full, y_pool
+
+
+def feature_distance(fx, fy, weights, normalize: bool = True):
+    """out[n] = mean_p sum_c weights[c] (x^[c,p] - y^[c,p])^2 of two feature maps [N,C,h,w], x^ = fx / (sqrt(sum_c fx^2) + 1e-10) with
+    `normalize` (ContentLoss.normalize, scores.py:403-411) and fx without: one layer's term of the reference's ContentLoss -> [N].
+    The rule is written out in include/smplnerf.h; fx == fy gives 0 exactly.  Forward only."""
+    _forward_only("feature_distance", (("fx", fx), ("fy", fy), ("weights", weights)))
+    if fx.dim() != 4 or fx.shape != fy.shape or weights.numel() != fx.shape[1]:
+        raise RuntimeError(f"feature_distance: fx and fy must be [N,C,h,w] of one shape and weights [C], got {tuple(fx.shape)}, "
+                           f"{tuple(fy.shape)} and {tuple(weights.shape)}")
+    fx, fy, weights = fx.detach().contiguous(), fy.detach().contiguous(), weights.detach().reshape(-1).contiguous()
+    N, C, h, w = fx.shape
+    lib = _lib.load()
+    nbytes = lib.snerf_feature_distance_workspace_bytes(N, h, w)
+    if nbytes < 0:
+        check(-1, "snerf_feature_distance_workspace_bytes")
+    ws = torch.empty((max(nbytes, 8),), device=fx.device, dtype=torch.uint8)
+    out = torch.empty((N,), device=fx.device, dtype=torch.float32)
+    with torch.cuda.device(fx.device), _lib.timed(f"feature_distance[{C},{h}x{w}]"):
+        check(lib.snerf_feature_distance_f32(ptr(fx), ptr(fy), N, C, h, w, ptr(weights), int(bool(normalize)), ptr(out), ptr(ws), nbytes,
+                                             current_stream()), "snerf_feature_distance_f32")
+    return out
+
+
+LPIPS_WORKSPACE_BYTES = 1 << 30      # what ops.lpips allocates at the most (one image pair's need, where that is more)
+
+
+def lpips_layers(x, y, net, workspace=None, max_pairs: Optional[int] = None):
+    """snerf_lpips_fwd_f32 on frames x, y [N,3,H,W] of any strides (one set for both; channels-last views run without a copy):
+    (layers [N,5], total [N]).  workspace: a uint8 device tensor to run in (a graph capture hands one over: nothing is allocated
+    then but the outputs); else one is allocated for min(N, max_pairs) pairs within LPIPS_WORKSPACE_BYTES.  The bits do not depend
+    on it."""
+    _forward_only("lpips", (("x", x), ("y", y)))
+    if x.dim() != 4 or x.shape != y.shape or x.shape[1] != 3:
+        raise RuntimeError(f"lpips: x and y must be [N,3,H,W] of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.device != y.device:
+        raise RuntimeError(f"lpips: x on {x.device}, y on {y.device}")
+    x, y = _ssim_layout(x.detach(), y.detach())
+    N, _, H, W = x.shape
+    rec = net.record(x.device)
+    lib = _lib.load()
+    if workspace is None:
+        one = lib.snerf_lpips_workspace_bytes(1, H, W, rec.channels)
+        if one < 0:
+            check(-1, "snerf_lpips_workspace_bytes")
+        pairs = max(1, min(N, LPIPS_WORKSPACE_BYTES // one, max_pairs if max_pairs else N))
+        workspace = torch.empty((pairs * one,), device=x.device, dtype=torch.uint8)
+    layers = torch.empty((N, 5), device=x.device, dtype=torch.float32)
+    total = torch.empty((N,), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device), _lib.timed(f"lpips_fwd[{N}x{H}x{W}]"):
+        check(lib.snerf_lpips_fwd_f32(ctypes.byref(rec), ptr(x), ptr(y), N, H, W, *x.stride(), ptr(layers), ptr(total), ptr(workspace),
+                                      workspace.numel(), current_stream()), "snerf_lpips_fwd_f32")
+    return layers, total
+
+
+def lpips(x, y, net, reduction: str = 'mean', per_layer: bool = False):
+    """The reference's LPIPS()(x, y) (util/scores.py:423-456, ContentLoss.forward :356-379) on the device, with the weights of `net`
+    (a lpips.VggLpips): frames [N,3,H,W], fp32 - the sum over the five taps of the weighted distance of the unit-normalised features,
+    then `reduction` ('mean' | 'sum' | 'none') over the batch.  per_layer=True: (value, the five taps' terms [N,5], reduced alike).
+    H, W >= 16 (the reference, which runs the unused pool5, needs 32).  The inputs are not checked for >= 0 (the reference's assert is
+    a device synchronisation).  Forward only: an input that requires grad while grad mode is on is refused."""
+    if reduction not in ('mean', 'sum', 'none'):
+        raise KeyError(reduction)
+    layers, total = lpips_layers(x, y, net)
+    if reduction != 'none':
+        op = {'mean': torch.mean, 'sum': torch.sum}[reduction]
+        total, layers = op(total, dim=0), op(layers, dim=0)
+    return (total, layers) if per_layer else total
+
+
+_lpips_op = lpips

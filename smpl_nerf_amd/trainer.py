@@ -779,17 +779,18 @@ class DataParallelTrainer:
         return val_loss, psnr, frames
 
     @torch.no_grad()
-    def validate_scores(self, val_loader, h: int, w: int, **ssim_kwargs):
-        """validate()'s pass with the whole frames scored ON THE DEVICE: the scores of the reference's print_scores that need no
-        network (util/scores.py:457-464: MSE, PSNR, SSIM; inference.py:257-258) through ops.image_scores - one forward call of the
+    def validate_scores(self, val_loader, h: int, w: int, lpips=None, **ssim_kwargs):
+        """validate()'s pass with the whole frames scored ON THE DEVICE: the scores of the reference's print_scores
+        (util/scores.py:457-464: MSE, PSNR, SSIM; inference.py:257-258) through ops.image_scores - one forward call of the
         SSIM kernel over the frames [-1, h, w, 3] as they lie, no host copy.  Returns (val_loss, dict of 0-d device tensors mse,
-        psnr, ssim - or None when the loader did not cover whole frames)."""
+        psnr, ssim - or None when the loader did not cover whole frames).  lpips: a lpips.VggLpips on the frames' device - the
+        dict gains "lpips", the fourth score of print_scores."""
         val_loss, renders, truths = self._validation_pass(val_loader)
         scores = None
         if renders and h and w:
             r, t = torch.cat(renders), torch.cat(truths)
             if r.shape[0] % (h * w) == 0:
-                scores = ops.image_scores(r.reshape(-1, h, w, 3), t.reshape(-1, h, w, 3), **ssim_kwargs)
+                scores = ops.image_scores(r.reshape(-1, h, w, 3), t.reshape(-1, h, w, 3), lpips=lpips, **ssim_kwargs)
         return val_loss, scores
 
     def save_checkpoint(self, save_dir: str, model_names, epoch: int, history=None):
