@@ -112,7 +112,8 @@ SNERF_API int snerf_searchsorted(int dtype, const void *a, int64_t nrow_a, int64
 
 /* ---- a1: positional encoding ----------------------------------------------------------------
  * x [n, c] -> out [n, c*(identity + 2*L)], frequency-major: [x] [sin(2^0 x) cos(2^0 x)] ...
- * (utils.py:116-131; no pi factor). */
+ * (utils.py:116-131; no pi factor).  0 <= L <= 30, c >= 1 and a row of at most 16384 floats, in the backward too;
+ * anything else is SNERF_E_BADARG. */
 SNERF_API int snerf_posenc_f32(const float *x, int64_t n, int c, int L, int identity, float *out,
                      snerf_stream_t stream);
 

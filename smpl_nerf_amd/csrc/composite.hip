@@ -68,7 +68,11 @@ __global__ __launch_bounds__(CP_THREADS) void composite_fwd_kernel(
         float dist = (i + 1 < N) ? __fsub_rn(zn, zi) : 1e10f;
         dist = __fmul_rn(dist, nrm);
         const float sig = noise ? __fadd_rn(r.w, nz) : r.w;
-        const float a = ok ? __fsub_rn(1.0f, expf(__fmul_rn(-fmaxf(sig, 0.f), dist))) : 0.f;
+        // exp in double, rounded once (as the backward has it): expf's error has a mean of about a tenth of an ulp on the device,
+        // which 1 - a carries into the transmittance once per live sample - 1.3e-5 of a weight after 4096 samples, 2.7e-5 after
+        // 8192, where the reference's own fp32 arithmetic is 1e-6 off float64.  Everything else stays fp32 in the reference's order.
+        const float ex = (float)exp((double)__fmul_rn(-fmaxf(sig, 0.f), dist));
+        const float a = ok ? __fsub_rn(1.0f, ex) : 0.f;
         const float om = ok ? __fadd_rn(__fsub_rn(1.0f, a), 1e-10f) : 1.0f;
         // inclusive fp64 prefix product over the chunk, shifted to exclusive
         const double incl = wave_scan_mul((double)om);

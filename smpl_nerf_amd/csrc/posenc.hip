@@ -74,6 +74,13 @@ __global__ __launch_bounds__(PE_THREADS) void posenc_bwd_kernel(const float *__r
     d_x[i] = acc;
 }
 
+// a row of the encoding is one workgroup's LDS tile at the least: c * (identity + 2L) <= PE_MAX_ROW floats.  The product is formed
+// in 64 bits (c = 70409300, L = 30, identity wraps to 4 in an int) with c bounded first.
+constexpr int PE_MAX_ROW = 16384;
+static bool row_width_ok(int c, int L, int identity) {
+    return c <= PE_MAX_ROW && (int64_t)c * (int64_t)(identity + 2 * L) <= PE_MAX_ROW;
+}
+
 }  // namespace snerf
 
 extern "C" int snerf_posenc_bwd_f32(const float *x, const float *d_out, int64_t n, int c, int L, int identity, float *d_x,
@@ -81,6 +88,8 @@ extern "C" int snerf_posenc_bwd_f32(const float *x, const float *d_out, int64_t 
     using namespace snerf;
     if (n < 0 || c <= 0 || L < 0 || L > 30) return fail(SNERF_E_BADARG, "posenc_bwd: bad n/c/L");
     identity = identity ? 1 : 0;
+    // the forward cannot produce a wider row (snerf_posenc_f32), so there is none to differentiate
+    if (!row_width_ok(c, L, identity)) return fail(SNERF_E_BADARG, "posenc_bwd: c*(identity+2L) too large (c = %d)", c);
     if (n == 0) return SNERF_OK;
     if (!x || !d_x) return fail(SNERF_E_BADARG, "posenc_bwd: null pointer");
     if (!d_out && (identity + 2 * L) > 0) return fail(SNERF_E_BADARG, "posenc_bwd: d_out is null");
@@ -97,13 +106,13 @@ extern "C" int snerf_posenc_f32(const float *x, int64_t n, int c, int L, int ide
     using namespace snerf;
     if (n < 0 || c <= 0 || L < 0 || L > 30) return fail(SNERF_E_BADARG, "posenc: bad n/c/L");
     identity = identity ? 1 : 0;
+    if (!row_width_ok(c, L, identity)) return fail(SNERF_E_BADARG, "posenc: c*(identity+2L) too large (c = %d)", c);
     const int outdim = c * (identity + 2 * L);
     if (n == 0 || outdim == 0) return SNERF_OK;
     if (!x || !out) return fail(SNERF_E_BADARG, "posenc: null pointer");
     // points per workgroup: as many as fit 64 KiB of LDS, at most PE_TILE (wide rows, e.g. a 69-channel
     // pose with L = 10 -> 1380 floats per point, get fewer points per group)
-    if (outdim > 16384) return fail(SNERF_E_BADARG, "posenc: c*(identity+2L) too large (%d)", outdim);
-    int tile = 16384 / outdim;
+    int tile = PE_MAX_ROW / outdim;
     if (tile > PE_TILE) tile = PE_TILE;
     const size_t lds = (size_t)tile * outdim * sizeof(float);
     const int64_t grid = (n + tile - 1) / tile;
