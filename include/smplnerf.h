@@ -660,6 +660,64 @@ SNERF_API int snerf_mesh_render_f32(const double *poses, double focal, int64_t N
                               float *image, float *t, int32_t *face, float *bary, float *depth, float *warp, void *workspace,
                               int64_t workspace_bytes, snerf_stream_t stream);
 
+/* ---- The soft silhouette: a coverage image that is differentiable in the vertices (legacy/neural_mesh_renderer.py's use of a
+ * differentiable renderer: fit a pose until the drawn body covers a target).  This is SoftRas's probabilistic union,
+ * 1 - prod_f (1 - sigmoid(+-d^2 / sigma)), written as a sum of logs; it is not kaolin's rasteriser and nothing is pinned against it.
+ * Inputs: poses, focal, N, H, W, vertices [Nv,V,3] (Nv = 1 or N), faces [F,3] as snerf_mesh_render_f32 takes them; sigma in
+ *   pixel^2; cutoff (17: softplus(-17) = 4.1e-8); flags 0 or SNERF_RENDER_NO_CULL.
+ * Rule, for frame n, with the camera of snerf_mesh_render_f32 (rotation R in float64, origin o rounded to fp32):
+ *   projection      per corner v of a face, in float64: p = v - o; c_i = (p0 R[0][i] + p1 R[1][i]) + p2 R[2][i]  (c = R^T p);
+ *                   depth = -c2;  x = W 0.5 + focal c0 / depth;  y = H 0.5 - focal c1 / depth;  x and y rounded once to fp32
+ *   live face       all three depths > 0 and all six |x|, |y| below 2^30 (the fp32 pair test cannot place anything farther out);
+ *                   a face that is not live contributes nothing, forward or backward
+ *   sample point    q = (i, j) for the pixel in row j, column i: where that pixel's ray of snerf_raygen_f64 pierces the image plane
+ *   pair            for the segments k = 0: p0 p1, 1: p1 p2, 2: p2 p0 from a to b (products and sums kept apart):
+ *                     e = b - a;  w = q - a;  ee = ex ex + ey ey;  t = ee > 0 ? min(max((wx ex + wy ey) / ee, 0), 1) : 0;
+ *                     r = w - t e;  d2_k = rx rx + ry ry;  edge_k = ex wy - ey wx
+ *                   d2 = the smallest d2_k, the lowest k on a tie;
+ *                   inside = the three edge_k are all > 0 or all < 0, and q lies in the bounding box of the three corners (which
+ *                   exact arithmetic implies; asked of the fp32 signs it keeps a far pixel outside).  Either winding counts; a
+ *                   zero-area face is never inside.
+ *   decision, fp32  the pair in fp32 gives inside and d2; a pair with !inside and d2 > cutoff sigma (float64 product, d2 widened)
+ *                   contributes exactly 0
+ *   value, float64  a contributing pair is evaluated again in float64 on the same fp32 corners: d2, its segment k, t and r (the
+ *                   fp32 distances cannot tell the nearest segment where the foot point is near a corner, and t shares the
+ *                   gradient between two corners);  z = (inside ? d2 : -d2) / sigma with the decision's inside
+ *   per pixel       L = the sum of softplus(z_f) = max(z, 0) + log1p(exp(-|z|)) over the contributing faces, in float64: ascending
+ *                   face index within each of the 8 slices wave_slice(F, 8, .) of the face axis, the slices' sums added in order;
+ *                   silhouette = -expm1(-L), rounded to fp32 once;  transmittance = exp(-L), float64, for the backward
+ *   z is C^1 across a triangle's boundary (d2 -> 0 there): a pixel on a vertex or an edge gets sigmoid(0) = 1/2 from that face and
+ *   a zero distance gradient.  The only kink is where the nearest segment changes.
+ * Backward: d_vertices[b][v] = sum_n sum_{pixels p, faces f} dS_p T_p sigmoid(z_pf) dz_pf/dv, over all frames n when one body is
+ *   shared (Nv = 1), over frame b otherwise.  With g = dS T sigmoid(z) (inside ? 2 : -2) / sigma and the nearest segment a -> b of
+ *   the pair, d/da = -g (1 - t) r and d/db = -g t r (the clamp and r . e = 0 make the t-terms vanish); the roundings to fp32 pass the
+ *   gradient through; through the projection d/dc = (gx focal / depth, -gy focal / depth, (gx c0 - gy c1) focal / depth^2) and
+ *   d/dv = R d/dc.  All of it in float64: per (frame, face) the pixels of the face's box in row-major order, 64 interleaved partial
+ *   sums added in one fixed order; per vertex its incident corners in CSR order, frames ascending; rounded to fp32 once.
+ * The cull: per frame and face the bounding box of the projected corners, widened by sqrt(cutoff sigma) plus a margin for the fp32
+ *   roundings and rounded outward.  A pixel outside it contributes exactly 0 under the rule, so skipping the face changes nothing:
+ *   every output equals the walk over all faces (SNERF_RENDER_NO_CULL) bit for bit.  The backward always walks boxes.
+ * Every element of every output is written; no atomics; nothing of size pixels x faces; two calls give the same bits; the entries
+ *   neither allocate nor synchronise.
+ * workspace: snerf_soft_silhouette_workspace_bytes(N, V, F) = 112 N F bytes, 8-byte aligned, written by a pre-pass of every call
+ *   (the backward does not need the forward's).
+ * vf_offsets [V+1], vf_faces [3F], vf_corners [3F] int32: the CSR table of snerf_mesh_render_f32 plus, for each entry, which of
+ *   the face's three corners it is (a face that names a vertex twice owns two distinct corners).
+ * Argument checks, on the host before any device work: N < 0, H or W < 1, a focal or sigma that is not positive and finite, a
+ *   cutoff that is negative or not finite, unknown flags, V < 1, F < 1, 3 V or 9 F not below 2^31 are SNERF_E_BADARG whatever N is;
+ *   N = 0 is a no-op returning 0, also with null pointers; then Nv other than 1 or N, a null pointer, N times the 8 x 8 tiles of a
+ *   frame not below 2^31, N above 65535, a workspace that is missing, misaligned or too small.  Face indices in [0, V) and a CSR
+ *   table of this face table are preconditions. */
+SNERF_API int64_t snerf_soft_silhouette_workspace_bytes(int64_t N, int V, int F);   /* -1 on a bad argument */
+SNERF_API int snerf_soft_silhouette_fwd_f32(const double *poses, double focal, int64_t N, int H, int W, const float *vertices, int Nv,
+                              int V, const int32_t *faces, int F, double sigma, double cutoff, int flags, float *silhouette,
+                              double *transmittance, void *workspace, int64_t workspace_bytes, snerf_stream_t stream);
+SNERF_API int snerf_soft_silhouette_bwd_f32(const double *poses, double focal, int64_t N, int H, int W, const float *vertices, int Nv,
+                              int V, const int32_t *faces, int F, double sigma, double cutoff, int flags, const float *d_silhouette,
+                              const double *transmittance, const int32_t *vf_offsets, const int32_t *vf_faces,
+                              const int32_t *vf_corners, float *d_vertices, void *workspace, int64_t workspace_bytes,
+                              snerf_stream_t stream);
+
 /* ---- Image scores: structural similarity with its backward, and the squared error of MSE / PSNR (util/scores.py:11-48, 88-173) ----
  * x, y: N images of C channels, H x W pixels, fp32, BOTH read through the four element strides (sn, sc, sh, sw): element
  *   (n, c, h, w) lies at n sn + c sc + h sh + w sw, so [N,C,H,W] and channels-last [N,H,W,C] storage run without a copy.

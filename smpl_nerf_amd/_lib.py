@@ -201,6 +201,12 @@ SIGNATURES = {
     "snerf_mesh_render_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
     "snerf_mesh_render_f32": (c_int, [_P, c_double, c_int64, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int,
                                       POINTER(MeshRenderArgs), _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
+    # the soft silhouette with its vertex gradient (csrc/soft_silhouette.hip)
+    "snerf_soft_silhouette_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "snerf_soft_silhouette_fwd_f32": (c_int, [_P, c_double, c_int64, c_int, c_int, _P, c_int, c_int, _P, c_int, c_double, c_double, c_int,
+                                              _P, _P, _P, c_int64, _P]),
+    "snerf_soft_silhouette_bwd_f32": (c_int, [_P, c_double, c_int64, c_int, c_int, _P, c_int, c_int, _P, c_int, c_double, c_double, c_int,
+                                              _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     "snerf_vertex_sphere_warp_f32": (c_int, [_P, _P, _P, c_int64, c_int, c_float, c_int, _P, _P, _P, _P]),
     # image scores: SSIM with its backward and the squared error of MSE / PSNR (csrc/ssim.hip)
     "snerf_ssim_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int]),

@@ -22,12 +22,11 @@
 //
 // Shading runs in wave 0 after the merge, per hit pixel; products and sums kept apart (-ffp-contract=off).  No atomics, nothing of
 // size pixels x faces, every element of every output written, two calls give the same bits.
+#include "mesh_tile.h"
 #include "ray_mesh_pair.h"
 
 namespace snerf {
 
-constexpr int MR_TILE = 8;                     // a workgroup's pixel tile is MR_TILE x MR_TILE = one lane per pixel
-static_assert(MR_TILE * MR_TILE == WAVE, "lane = pixel");
 constexpr int MR_BOX_ALL_LO = INT32_MIN, MR_BOX_ALL_HI = INT32_MAX;
 
 struct MrArgs {
@@ -44,23 +43,6 @@ struct MrArgs {
     int N, Nv, V, F, H, W, Ht, Wt, tiles_x, tiles_y;
     float ambient, intensity, bg[3];
 };
-
-// the camera of frame n as the ray generator uses it: rotation in float64, origin rounded to fp32
-struct MrCamera {
-    double R[3][3];
-    float o[3];
-};
-__device__ __forceinline__ MrCamera mr_camera(const double *poses, int n) {
-    const double *M = poses + (int64_t)n * 16;
-    MrCamera c;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c.R[r][k] = M[r * 4 + k];
-        c.o[r] = (float)M[r * 4 + 3];
-    }
-    return c;
-}
 
 // The screen-space box of the face T = (a, e1, e2) under camera C, in whole pixels, or "everything".
 //
@@ -164,12 +146,9 @@ template <bool CULL>
 __global__ __launch_bounds__(RM_WAVES * 64) void mesh_render_kernel(MrArgs A) {
     __shared__ float part[RM_WAVES][4][WAVE];   // t, face (its bits), u, v of each wave's nearest hit
     const int lane = lane_id(), wave = wave_index();
-    const int tiles = A.tiles_x * A.tiles_y;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / A.tiles_x, tx = tile - ty * A.tiles_x;
-    const int i_own = tx * MR_TILE + (lane & (MR_TILE - 1)), j_own = ty * MR_TILE + (lane >> 3);
-    const bool valid = i_own < A.W && j_own < A.H;
-    const int i = tail_index(i_own, A.W, i_own < A.W), j = tail_index(j_own, A.H, j_own < A.H);
+    const MrTile tl = mr_tile(blockIdx.x, A.tiles_x, A.tiles_y, A.H, A.W, lane);
+    const int n = tl.n, i = tl.i, j = tl.j;
+    const bool valid = tl.valid;
     const int body = A.Nv == 1 ? 0 : n;
 
     // the ray of pixel (j, i): raygen.hip:46-58, operation for operation
@@ -192,7 +171,7 @@ __global__ __launch_bounds__(RM_WAVES * 64) void mesh_render_kernel(MrArgs A) {
 
     if constexpr (CULL) {
         // the tile in pixels, clipped; a box meets it when the intervals overlap on both axes (all wave-uniform integers)
-        const int px0 = tx * MR_TILE, px1 = min(px0 + MR_TILE, A.W) - 1, py0 = ty * MR_TILE, py1 = min(py0 + MR_TILE, A.H) - 1;
+        const int px0 = tl.x0(), px1 = tl.x1(A.W), py0 = tl.y0(), py1 = tl.y1(A.H);
         auto boxed = [&](int f, const float *b) {
             const int x0 = __float_as_int(b[0]), x1 = __float_as_int(b[1]), y0 = __float_as_int(b[2]), y1 = __float_as_int(b[3]);
             if (x0 <= px1 && x1 >= px0 && y0 <= py1 && y1 >= py0) {
@@ -315,7 +294,7 @@ extern "C" int snerf_mesh_render_f32(const double *poses, double focal, int64_t 
         return fail(SNERF_E_BADARG, "%s: null pointer (poses, vertices, faces, vf_offsets, vf_faces, uv, texture, args, image, t, face, bary)", op);
     if (!((canon && warp && depth) || (!canon && !warp && !depth)))
         return fail(SNERF_E_BADARG, "%s: canon, warp and depth must be all null or all non-null", op);
-    const int tiles_x = (W + MR_TILE - 1) / MR_TILE, tiles_y = (H + MR_TILE - 1) / MR_TILE;
+    const int tiles_x = mr_tiles(W), tiles_y = mr_tiles(H);
     const int64_t blocks = (int64_t)tiles_x * tiles_y * N;
     if (blocks > 0x7fffffffLL || N > 65535 || (int64_t)Ht * Wt * 3 > 0x7fffffffLL || (int64_t)N * F * 13 > INT64_MAX / 8)
         return fail(SNERF_E_BADARG, "%s: N times the tiles of a frame must stay below 2^31, N below 65536 and 3 Ht Wt below 2^31", op);

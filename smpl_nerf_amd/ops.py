@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import platform
 import weakref
 from typing import Optional, Tuple
@@ -857,7 +858,7 @@ def ray_mesh_first_hit(origins, directions, vertices, faces, canon=None, faces_c
 
 
 MeshFrames = collections.namedtuple("MeshFrames", "image t face bary depth warp")
-_VERTEX_FACES = {}      # (data_ptr, device, F, V, tensor version) -> (weak reference to the face tensor, vf_offsets, vf_faces)
+_VERTEX_FACES = {}      # (data_ptr, device, F, V, tensor version, with corners) -> (weak reference to the face tensor, vf_offsets, vf_faces[, vf_corners])
 
 
 def vertex_face_table(faces, V: int):
@@ -872,16 +873,61 @@ def vertex_face_table(faces, V: int):
     return offsets.astype(np.int32), (order // 3).astype(np.int32)
 
 
-def _vertex_faces_cached(faces, V):
-    key = (faces.data_ptr(), faces.device, faces.shape[0], V, faces._version)
+def vertex_corner_table(faces, V: int):
+    """vertex_face_table with, for every entry, which corner of its face it is: (vf_offsets [V+1], vf_faces [3F], vf_corners [3F])
+    int32 numpy arrays - vertex v is corner vf_corners[k] of face vf_faces[k] for k in vf_offsets[v]:vf_offsets[v+1], in ascending
+    face index and, within a face that names the vertex twice, ascending corner: two distinct corners."""
+    f = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces).astype(np.int64).reshape(-1, 3)
+    flat = f.reshape(-1)
+    order = np.argsort(flat, kind="stable")
+    offsets = np.zeros(V + 1, np.int64)
+    np.cumsum(np.bincount(flat, minlength=V), out=offsets[1:])
+    return offsets.astype(np.int32), (order // 3).astype(np.int32), (order % 3).astype(np.int32)
+
+
+def _vertex_faces_cached(faces, V, corners: bool = False):
+    key = (faces.data_ptr(), faces.device, faces.shape[0], V, faces._version, corners)
     hit = _VERTEX_FACES.get(key)
     if hit is not None and hit[0]() is faces:
-        return hit[1], hit[2]
+        return hit[1:]
     for k in [k for k, v in _VERTEX_FACES.items() if v[0]() is None]:
         del _VERTEX_FACES[k]
-    off, vf = (torch.from_numpy(a).to(faces.device) for a in vertex_face_table(faces, V))
-    _VERTEX_FACES[key] = (weakref.ref(faces), off, vf)
-    return off, vf
+    table = tuple(torch.from_numpy(a).to(faces.device) for a in (vertex_corner_table if corners else vertex_face_table)(faces, V))
+    _VERTEX_FACES[key] = (weakref.ref(faces),) + table
+    return table
+
+
+def _mesh_frames_inputs(op, poses, vertices, faces, faces_checked):
+    """The checks render_mesh and soft_silhouette share on poses, vertices and faces -> (vertices [Nv,V,3], N, Nv, V, F)."""
+    if faces.dtype != torch.int32:
+        raise RuntimeError(f"{op}: `faces` must be int32 (got {faces.dtype})")
+    if vertices.dim() == 2:
+        vertices = vertices[None]
+    if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[1] < 1 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise RuntimeError(f"{op}: vertices {tuple(vertices.shape)} must be [V >= 1, 3] or [N, V, 3] and faces {tuple(faces.shape)} [F >= 1, 3]")
+    Nv, V, F = vertices.shape[0], vertices.shape[1], faces.shape[0]
+    if not faces_checked:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= V:
+            raise RuntimeError(f"{op}: faces index vertices {lo} .. {hi}, outside [0, {V})")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.dtype != torch.float64:
+        raise RuntimeError(f"{op}: poses must be float64 [N,4,4], got {poses.dtype} {tuple(poses.shape)}")
+    N = poses.shape[0]
+    if Nv not in (1, N):
+        raise RuntimeError(f"{op}: {Nv} bodies for {N} frames (one for all, or one per frame)")
+    return vertices, N, Nv, V, F
+
+
+def _mesh_frames_device(op, H, W, focal, tensors):
+    """... and on the frame size and on where the named tensors live (poses and faces keep their own dtypes)."""
+    if int(H) < 1 or int(W) < 1 or not float(focal) > 0:
+        raise RuntimeError(f"{op}: H and W must be at least 1 and focal positive")
+    for nm, t in tensors:
+        if t is not None:
+            if not t.is_cuda:
+                raise RuntimeError(f"smpl_nerf_amd: `{nm}` must live on the GPU (got {t.device}); there is no CPU path")
+            if nm not in ("poses", "faces") and t.dtype != torch.float32:
+                raise RuntimeError(f"{op}: `{nm}` must be float32 (got {t.dtype})")
 
 
 @torch.no_grad()
@@ -897,34 +943,13 @@ def render_mesh(poses, focal, H: int, W: int, vertices, faces, uv, texture, ambi
     ray_mesh_first_hit returns for the rays RayGenerator makes for these poses.  cull=False walks every face for every pixel tile:
     the same bits, slower.  The face table is range-checked once (faces_checked=True skips it) and its vertex-to-face table is
     built on the host once per faces tensor and cached.  The frames are data: no backward, no grad_fn."""
-    if faces.dtype != torch.int32:
-        raise RuntimeError(f"render_mesh: `faces` must be int32 (got {faces.dtype})")
-    if vertices.dim() == 2:
-        vertices = vertices[None]
-    if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[1] < 1 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-        raise RuntimeError(f"render_mesh: vertices {tuple(vertices.shape)} must be [V >= 1, 3] or [N, V, 3] and faces {tuple(faces.shape)} [F >= 1, 3]")
-    Nv, V, F = vertices.shape[0], vertices.shape[1], faces.shape[0]
-    if not faces_checked:
-        lo, hi = (int(x) for x in torch.aminmax(faces))
-        if lo < 0 or hi >= V:
-            raise RuntimeError(f"render_mesh: faces index vertices {lo} .. {hi}, outside [0, {V})")
-    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.dtype != torch.float64:
-        raise RuntimeError(f"render_mesh: poses must be float64 [N,4,4], got {poses.dtype} {tuple(poses.shape)}")
-    N = poses.shape[0]
-    if Nv not in (1, N):
-        raise RuntimeError(f"render_mesh: {Nv} bodies for {N} frames (one for all, or one per frame)")
+    vertices, N, Nv, V, F = _mesh_frames_inputs("render_mesh", poses, vertices, faces, faces_checked)
     if tuple(uv.shape) != (V, 2) or texture.dim() != 3 or texture.shape[2] != 3 or texture.shape[0] < 1 or texture.shape[1] < 1:
         raise RuntimeError(f"render_mesh: uv {tuple(uv.shape)} must be [V,2] and texture {tuple(texture.shape)} [Ht,Wt,3]")
     if canon is not None and tuple(canon.shape) != (V, 3):
         raise RuntimeError(f"render_mesh: canon {tuple(canon.shape)} must be [V,3] = [{V},3]")
-    if int(H) < 1 or int(W) < 1 or not float(focal) > 0:
-        raise RuntimeError("render_mesh: H and W must be at least 1 and focal positive")
-    for nm, t in (("poses", poses), ("vertices", vertices), ("faces", faces), ("uv", uv), ("texture", texture), ("canon", canon)):
-        if t is not None:
-            if not t.is_cuda:
-                raise RuntimeError(f"smpl_nerf_amd: `{nm}` must live on the GPU (got {t.device}); there is no CPU path")
-            if nm not in ("poses", "faces") and t.dtype != torch.float32:
-                raise RuntimeError(f"render_mesh: `{nm}` must be float32 (got {t.dtype})")
+    _mesh_frames_device("render_mesh", H, W, focal, (("poses", poses), ("vertices", vertices), ("faces", faces), ("uv", uv),
+                                                     ("texture", texture), ("canon", canon)))
     off, vf = _vertex_faces_cached(faces, V)
     ps, vt, fc, uvc, tex = (x.detach().contiguous() for x in (poses, vertices, faces, uv, texture))
     cn = None if canon is None else canon.detach().contiguous()
@@ -946,6 +971,68 @@ def render_mesh(poses, focal, H: int, W: int, vertices, faces, uv, texture, ambi
                                         tex.shape[0], tex.shape[1], ctypes.byref(args), ptr(cn), ptr(image), ptr(t), ptr(face), ptr(bary),
                                         ptr(depth), ptr(warp), ptr(ws), nbytes, current_stream()), "snerf_mesh_render_f32")
     return MeshFrames(image, t, face, bary, depth, warp)
+
+
+def _soft_silhouette_workspace(lib, N, V, F, dev):
+    nbytes = lib.snerf_soft_silhouette_workspace_bytes(N, V, F)
+    if nbytes < 0:
+        check(-1, "snerf_soft_silhouette_workspace_bytes")
+    return torch.empty((max(nbytes, 8) // 8,), device=dev, dtype=torch.float64), nbytes
+
+
+class _SoftSilhouette(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vertices, poses, faces, table, focal, H, W, sigma, cutoff, flags):
+        N, (Nv, V, _), F, dev = poses.shape[0], vertices.shape, faces.shape[0], poses.device
+        vt = vertices.detach().contiguous()
+        sil = torch.empty((N, H, W), device=dev, dtype=torch.float32)
+        trans = torch.empty((N, H, W), device=dev, dtype=torch.float64)
+        lib = _lib.load()
+        ws, nbytes = _soft_silhouette_workspace(lib, N, V, F, dev)
+        with torch.cuda.device(dev), _lib.timed(f"soft_silhouette_fwd[N={N},F={F}]"):
+            check(lib.snerf_soft_silhouette_fwd_f32(ptr(poses), focal, N, H, W, ptr(vt), Nv, V, ptr(faces), F, sigma, cutoff, flags, ptr(sil),
+                                                    ptr(trans), ptr(ws), nbytes, current_stream()), "snerf_soft_silhouette_fwd_f32")
+        if ctx.needs_input_grad[0]:      # (under no_grad nothing is kept)
+            ctx.save_for_backward(vt, poses, faces, trans)
+            ctx.table, ctx.scalars = table, (focal, H, W, sigma, cutoff, flags)
+        return sil
+
+    @staticmethod
+    def backward(ctx, d_sil):
+        vt, poses, faces, trans = ctx.saved_tensors
+        focal, H, W, sigma, cutoff, flags = ctx.scalars
+        N, (Nv, V, _), F, dev = poses.shape[0], vt.shape, faces.shape[0], poses.device
+        ds = d_sil.detach().to(torch.float32).contiguous()
+        off, vf, vc = ctx.table
+        dv = torch.empty_like(vt)
+        lib = _lib.load()
+        ws, nbytes = _soft_silhouette_workspace(lib, N, V, F, dev)
+        with torch.cuda.device(dev), _lib.timed(f"soft_silhouette_bwd[N={N},F={F}]"):
+            check(lib.snerf_soft_silhouette_bwd_f32(ptr(poses), focal, N, H, W, ptr(vt), Nv, V, ptr(faces), F, sigma, cutoff, flags, ptr(ds),
+                                                    ptr(trans), ptr(off), ptr(vf), ptr(vc), ptr(dv), ptr(ws), nbytes, current_stream()),
+                  "snerf_soft_silhouette_bwd_f32")
+        return (dv,) + (None,) * 9
+
+
+def soft_silhouette(poses, focal, H: int, W: int, vertices, faces, sigma: float = 1.0, cutoff: float = 17.0, cull: bool = True,
+                    faces_checked: bool = False):
+    """The soft silhouette of a triangle mesh in N frames, differentiable with respect to the vertices (csrc/soft_silhouette.hip;
+    include/smplnerf.h, snerf_soft_silhouette_fwd_f32, states the rule operation by operation): per pixel
+    1 - prod_f (1 - sigmoid(+-d^2 / sigma)) with d the pixel's distance, in pixels, to the projected face's outline and + inside it.
+    poses, focal, H, W, vertices ([V,3]: one body for all frames - several cameras on it are a multi-view fit - or [N,V,3]) and
+    faces as render_mesh takes them, with its checks; sigma in pixel^2; a face farther than sqrt(cutoff sigma) pixels from a pixel
+    contributes exactly 0 to it -> silhouette [N,H,W] fp32 in [0,1].  The gradient reaches `vertices` only (not the camera), in the
+    shape it came in.  cull=False walks every face for every pixel tile: the same bits, slower.  Nothing of size pixels x faces is
+    built; under no_grad nothing is kept.  The vertex-to-corner table of `faces` is built on the host once per faces tensor, by the first
+    call that needs a gradient, and cached."""
+    vt, N, Nv, V, F = _mesh_frames_inputs("soft_silhouette", poses, vertices, faces, faces_checked)
+    _mesh_frames_device("soft_silhouette", H, W, focal, (("poses", poses), ("vertices", vt), ("faces", faces)))
+    if not (float(sigma) > 0 and math.isfinite(float(sigma)) and 0 <= float(cutoff) < math.inf):
+        raise RuntimeError(f"soft_silhouette: sigma must be positive and finite and cutoff finite and not negative, got {sigma} and {cutoff}")
+    # (the corner table hangs on the caller's faces tensor, as render_mesh's table does: built on the host once, then cached)
+    table = _vertex_faces_cached(faces, V, corners=True) if torch.is_grad_enabled() and vertices.requires_grad else None
+    return _SoftSilhouette.apply(vt, poses.detach().contiguous(), faces.detach().contiguous(), table, float(focal), int(H), int(W),
+                                 float(sigma), float(cutoff), 0 if cull else _lib.RENDER_NO_CULL)
 
 
 def vertex_sphere_warp(samples, goal, canon, radius, by_mean: bool = False, want_indices: bool = False):
