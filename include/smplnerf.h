@@ -853,6 +853,60 @@ SNERF_API int64_t snerf_lpips_workspace_bytes(int64_t n_pairs, int64_t H, int64_
 SNERF_API int snerf_lpips_fwd_f32(const snerf_vgg_lpips *net, const float *x, const float *y, int64_t N, int64_t H, int64_t W, int64_t sn,
                               int64_t sc, int64_t sh, int64_t sw, float *layers, float *total, void *workspace,
                               int64_t workspace_bytes, snerf_stream_t stream);
+/* ---- LPIPS as a training loss: the backward to both frames (ContentLoss is a _Loss: differentiable, its weights frozen, scores.py:340)
+ * Common to the three entries: contiguous NCHW fp32 unless strides are named; no atomics and no read-modify-write of global memory;
+ *   one fixed summation order that depends on the shapes alone; every element of every output that is not NULL is written; nothing
+ *   is allocated and nothing synchronises; bad arguments are SNERF_E_BADARG / SNERF_E_ALIGN on the host, before anything touches a
+ *   device, with a message naming the value; a bad scalar is an error whatever N is; N = 0 is SNERF_OK whatever the pointers are.
+ *
+ * The distance gradient: dfx, dfy [N,C,h,w] (either may be NULL, not both) = the gradient of sum_n g[n] out[n] of
+ *   snerf_feature_distance_f32 to fx and to fy; g [N].  Rule, per pixel p, operation by operation:
+ *   s, r = sqrt(s), nx = r + 1e-10f, a = fx / nx, b = fy / ny, d = a - b     fp32, the forward's own values (ry, ny from fy alike)
+ *   gs = (double)g[n] / (h w)              q[c] = ((2 wl[c]) d[c]) gs        float64 from here on
+ *   Dx = sum over c = 0, 1, .. of q[c] a[c], Dy = .. q[c] b[c]               one float64 fused multiply-add per channel
+ *   dfx[k] = (q[k] - fx[k] (Dx / r)) / nx         dfy[k] = -(q[k] - fy[k] (Dy / ry)) / ny         each rounded to fp32 once
+ *   Without normalize: dfx = q, dfy = -q.
+ *   The all-zero pixel: where r = 0 the reference's autograd gives NaN (0 / 0 in the square root's backward).  Here the norm term is
+ *   taken as 0 there: dfx[k] = q[k] / nx, finite.  In the metric it makes no difference: such a pixel sits at the ReLU's zero in
+ *   every channel, and the ReLU's backward masks it to 0, which is why the reference's end-to-end gradient is finite too.
+ *   fx == fy gives +0 everywhere.  Either output alone has the bits it has beside the other; a pixel's gradient depends on its own
+ *   features and g[n] alone.  Lane = pixel, as in the forward; three passes over the channels (HBM once, the L2 twice); nothing of
+ *   map size is stored besides the outputs; no workspace.
+ *   SNERF_E_BADARG: the scalar refusals of snerf_feature_distance_f32; with N > 0 both outputs NULL, a null fx, fy, wl or g. */
+SNERF_API int snerf_feature_distance_bwd_f32(const float *fx, const float *fy, int64_t N, int64_t C, int64_t h, int64_t w, const float *wl,
+                              int normalize, const float *g, float *dfx, float *dfy, snerf_stream_t stream);
+/* The ReLU and the 2 x 2 max-pool that may follow it, without BatchNorm, on the post-ReLU map y [N,C,H,W] -> dz [N,C,H,W]:
+ *   dz = (y > 0) ? dy_full + route(dy_pool) : 0            dy_full [N,C,H,W], dy_pool [N,C,H/2,W/2]; either may be NULL, not both
+ *   route sends a window's gradient to its FIRST maximum in the order (0,0), (0,1), (1,0), (1,1), recomputed from y (the rule of
+ *   snerf_bn_relu_pool_bwd_f32, torch's max_pool2d); elsewhere, and at a pixel in no window (an odd extent), it is 0; a NULL
+ *   gradient is 0.  One fp32 addition per pixel.  dz may be dy_full: a thread reads the four pixels of its 2 x 2 cell before it
+ *   writes them.
+ *   SNERF_E_BADARG: N negative; C, H or W below 1, with dy_pool H or W below 2; N C H W at 2^31 or above; with N > 0 both gradients
+ *   NULL, a null y or dz. */
+SNERF_API int snerf_relu_pool_bwd_f32(const float *y, const float *dy_full, const float *dy_pool, int64_t N, int64_t C, int64_t H, int64_t W,
+                              float *dz, snerf_stream_t stream);
+/* The whole backward: dx, dy (either may be NULL, not both) = the gradient of sum_n sum_l g_layers[n,l] layers[n,l] of
+ *   snerf_lpips_fwd_f32 to the frames x and y, written through the four element strides the frames are read through (which must
+ *   put no two elements at one address); g_layers [N,5].  layers [N,5] (may be NULL): the forward's, with its bits.
+ * What runs, per chunk of as many pairs as the workspace holds:
+ *   the forward with snerf_lpips_fwd_f32's own kernels, keeping the thirteen post-ReLU maps of both frames;
+ *   then from the fifth stage down to the first: at a tap the distance gradient (snerf_feature_distance_bwd_f32's kernel), then
+ *   snerf_relu_pool_bwd_f32's with the gradient that arrives from the next stage's pooled input as dy_pool (none at the fifth); at
+ *   the other eight convolutions snerf_relu_pool_bwd_f32's with dy_full alone; between them the input gradient of a convolution,
+ *   dx = conv3x3_pad1(dz, w') with w'[ci][co][ky][kx] = w[co][ci][2 - ky][2 - kx] written into the workspace, on
+ *   snerf_conv3x3_block_tap_f32's kernel with scale = 1, shift = 0, no ReLU - up to 512 channels, above 256 with its segmented
+ *   chain as it stands; last g / std[c], one fp32 division.
+ *   With one of dx, dy NULL the backward runs on that half of the batch only.
+ * The entry adds no arithmetic of its own: its outputs have the bits of the entries above called one by one.  They do not depend on
+ *   the workspace's size or on the rest of the batch.  A linear chain of launches: it can be captured into a graph.
+ * workspace: at least snerf_lpips_bwd_workspace_bytes(1, H, W, channels) bytes, 16-byte aligned; (n_pairs, ..) bytes hold n_pairs a
+ *   chunk.  Once a call: w' of the widest convolution and 512 zeros.  Per pair: the thirteen maps of both frames (540 H W floats at
+ *   VGG16's widths), two gradient buffers of the widest map (2 x 128 H W), one float64 per 64-pixel tile.
+ * Refusals: snerf_lpips_fwd_f32's, and with N > 0 both outputs NULL or a null g_layers. */
+SNERF_API int64_t snerf_lpips_bwd_workspace_bytes(int64_t n_pairs, int64_t H, int64_t W, const int32_t *channels);   /* -1 on a bad argument */
+SNERF_API int snerf_lpips_bwd_f32(const snerf_vgg_lpips *net, const float *x, const float *y, int64_t N, int64_t H, int64_t W, int64_t sn,
+                              int64_t sc, int64_t sh, int64_t sw, const float *g_layers, float *dx, float *dy, float *layers,
+                              void *workspace, int64_t workspace_bytes, snerf_stream_t stream);
 
 /* ---- SmplEstimator, training: the block with batch statistics and its backward (csrc/conv_train.hip) --------------------------
  *   z = conv3x3_pad1(x, w) + b              snerf_conv3x3_block_f32 with scale = 1, shift = b, relu = pool = 0 (x 1 is exact)

@@ -225,6 +225,12 @@ SIGNATURES = {
     "snerf_lpips_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, POINTER(c_int32)]),
     "snerf_lpips_fwd_f32": (c_int, [POINTER(VggLpipsNet), _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P,
                                     _P, c_int64, _P]),
+    # LPIPS as a loss: the distance gradient, the ReLU / max-pool backward, the whole backward (csrc/lpips.hip)
+    "snerf_feature_distance_bwd_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, _P, c_int, _P, _P, _P, _P]),
+    "snerf_relu_pool_bwd_f32": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P]),
+    "snerf_lpips_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, POINTER(c_int32)]),
+    "snerf_lpips_bwd_f32": (c_int, [POINTER(VggLpipsNet), _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P,
+                                    _P, _P, _P, c_int64, _P]),
     # SmplEstimator, training: batch statistics, the block's apply and backward, the convolution's gradients (csrc/conv_train.hip)
     "snerf_bn_stats_scratch_floats": (c_int64, [c_int64, c_int, c_int64, c_int64]),
     "snerf_bn_stats_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, c_double, c_double, _P, _P, _P, _P, _P, _P]),

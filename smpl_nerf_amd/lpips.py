@@ -7,6 +7,7 @@ the user already has - torchvision's vgg16 checkpoint (or the state_dict of its 
     net = VggLpips.from_files("vgg16-397923af.pth", "lpips_weights.pt").cuda()
     ops.lpips(x, y, net)                      # x, y [N,3,H,W] in [0, 1]
     ops.image_scores(renders, truths, lpips=net)["lpips"]
+    net.loss(render, truth).backward()        # ops.lpips_loss: the same value as a training loss, differentiable to the frames
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ VGG16_CONV_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)
 class VggLpips(nn.Module):
     """The 13 convolutions (buffers conv<i>_weight [Co,Ci,3,3], conv<i>_bias [Co], i = 0 .. 12 in VGG16 order), the five channel
     weights lin<l> [channels[l]] and the input standardisation.  Any channel count of 1 .. 512 per stage: the real net is
-    64, 128, 256, 512, 512.  Forward only: the tensors are buffers, nothing here is trained."""
+    64, 128, 256, 512, 512.  The tensors are buffers, nothing here is trained: forward() is the score, loss() the same value under autograd."""
 
     def __init__(self, convs, lin, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         super().__init__()
@@ -99,3 +100,8 @@ class VggLpips(nn.Module):
     def forward(self, x, y, reduction: str = 'mean'):
         from . import ops
         return ops.lpips(x, y, self, reduction=reduction)
+
+    def loss(self, x, y, reduction: str = 'mean'):
+        """ops.lpips_loss: the same value, differentiable with respect to the frames; the buffers here stay constants."""
+        from . import ops
+        return ops.lpips_loss(x, y, self, reduction=reduction)

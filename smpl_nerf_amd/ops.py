@@ -17,6 +17,8 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     conv3x3_bn_block    the same block under nn.Module.train(): BatchNorm on the batch statistics, differentiable to every input
     lpips               util/scores.py:286-456 (ContentLoss as LPIPS() configures it) on the weights of a lpips.VggLpips; its parts:
                         conv3x3_block_tap (the block's un-pooled and pooled maps from one launch) and feature_distance
+    lpips_loss          the same ContentLoss as the _Loss it is: differentiable to both frames, the weights frozen (:340); its parts:
+                        feature_distance_bwd, relu_pool_bwd and lpips_bwd (the whole backward, one call)
 
 Every function takes CUDA (ROCm) fp32 tensors and launches on PyTorch's current stream.  There is
 no CPU implementation here: a CPU tensor is an error, like a missing library.
@@ -1357,7 +1359,7 @@ def _forward_only(op, tensors):
     for nm, t in tensors:
         _need_cuda(nm, t)
         if t.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError(f"{op}: `{nm}` requires grad, but this op is forward only (LPIPS is a score here, not a training loss); "
+            raise RuntimeError(f"{op}: `{nm}` requires grad, but this op is forward only (the score: ops.lpips_loss is LPIPS as a training loss); "
                                "call it under torch.no_grad() or detach the tensor")
 
 
@@ -1441,7 +1443,8 @@ def lpips(x, y, net, reduction: str = 'mean', per_layer: bool = False):
     (a lpips.VggLpips): frames [N,3,H,W], fp32 - the sum over the five taps of the weighted distance of the unit-normalised features,
     then `reduction` ('mean' | 'sum' | 'none') over the batch.  per_layer=True: (value, the five taps' terms [N,5], reduced alike).
     H, W >= 16 (the reference, which runs the unused pool5, needs 32).  The inputs are not checked for >= 0 (the reference's assert is
-    a device synchronisation).  Forward only: an input that requires grad while grad mode is on is refused."""
+    a device synchronisation).  Forward only: an input that requires grad while grad mode is on is refused (ops.lpips_loss is the
+    differentiable form)."""
     if reduction not in ('mean', 'sum', 'none'):
         raise KeyError(reduction)
     layers, total = lpips_layers(x, y, net)
@@ -1452,3 +1455,136 @@ def lpips(x, y, net, reduction: str = 'mean', per_layer: bool = False):
 
 
 _lpips_op = lpips
+
+
+# ---- LPIPS as a training loss: the backward (csrc/lpips.hip) -------------------------------------------------------------------------
+def feature_distance_bwd(fx, fy, weights, g, normalize: bool = True, want_fx: bool = True, want_fy: bool = True):
+    """snerf_feature_distance_bwd_f32: (dfx, dfy), the gradient of sum_n g[n] feature_distance(fx, fy, weights)[n] to the two maps
+    [N,C,h,w]; g [N].  An output that is not wanted is None; the other has the bits it has beside it.  At a pixel whose features are
+    all zero the norm term is taken as 0 (autograd gives NaN there); the rule is written out in include/smplnerf.h.  A plain
+    function: nothing is recorded for autograd."""
+    for nm, t in (("fx", fx), ("fy", fy), ("weights", weights), ("g", g)):
+        _need_cuda(nm, t)
+    if fx.dim() != 4 or fx.shape != fy.shape or weights.numel() != fx.shape[1] or g.numel() != fx.shape[0]:
+        raise RuntimeError(f"feature_distance_bwd: fx and fy must be [N,C,h,w] of one shape, weights [C] and g [N], got {tuple(fx.shape)}, "
+                           f"{tuple(fy.shape)}, {tuple(weights.shape)} and {tuple(g.shape)}")
+    if not (want_fx or want_fy):
+        raise RuntimeError("feature_distance_bwd: one of `want_fx` and `want_fy` at least")
+    fx, fy, weights, g = (t.detach().float().contiguous() for t in (fx, fy, weights.reshape(-1), g.reshape(-1)))
+    N, C, h, w = fx.shape
+    dfx, dfy = (torch.empty_like(fx) if want else None for want in (want_fx, want_fy))
+    with torch.cuda.device(fx.device), _lib.timed(f"feature_distance_bwd[{C},{h}x{w}]"):
+        check(_lib.load().snerf_feature_distance_bwd_f32(ptr(fx), ptr(fy), N, C, h, w, ptr(weights), int(bool(normalize)), ptr(g), ptr(dfx),
+                                                         ptr(dfy), current_stream()), "snerf_feature_distance_bwd_f32")
+    return dfx, dfy
+
+
+def relu_pool_bwd(y, dy_full=None, dy_pool=None, inplace: bool = False):
+    """snerf_relu_pool_bwd_f32: dz = (y > 0) ? dy_full + route(dy_pool) : 0 on the post-ReLU map y [N,C,H,W]; dy_full [N,C,H,W] and
+    dy_pool [N,C,H//2,W//2], one of them at least.  route: a window's gradient goes to its first maximum in the order (0,0), (0,1),
+    (1,0), (1,1).  inplace=True writes dz over a contiguous fp32 dy_full and returns it.  A plain function."""
+    _need_cuda("y", y)
+    if y.dim() != 4:
+        raise RuntimeError(f"relu_pool_bwd: y must be [N,C,H,W], got {tuple(y.shape)}")
+    if dy_full is None and dy_pool is None:
+        raise RuntimeError("relu_pool_bwd: one of `dy_full` and `dy_pool` at least")
+    N, C, H, W = y.shape
+    for nm, t, shape in (("dy_full", dy_full, (N, C, H, W)), ("dy_pool", dy_pool, (N, C, H // 2, W // 2))):
+        if t is not None:
+            _need_cuda(nm, t)
+            if tuple(t.shape) != shape:
+                raise RuntimeError(f"relu_pool_bwd: `{nm}` must be {list(shape)}, got {tuple(t.shape)}")
+    y = y.detach().float().contiguous()
+    if inplace and (dy_full is None or dy_full.dtype != torch.float32 or not dy_full.is_contiguous()):
+        raise RuntimeError("relu_pool_bwd: inplace=True needs a contiguous fp32 dy_full")
+    dz = dy_full if inplace else torch.empty_like(y)
+    dy_full, dy_pool = (None if t is None else t.detach().float().contiguous() for t in (dy_full, dy_pool))
+    with torch.cuda.device(y.device), _lib.timed(f"relu_pool_bwd[{C},{H}x{W}]"):
+        check(_lib.load().snerf_relu_pool_bwd_f32(ptr(y), ptr(dy_full), ptr(dy_pool), N, C, H, W, ptr(dz), current_stream()),
+              "snerf_relu_pool_bwd_f32")
+    return dz
+
+
+def lpips_bwd(x, y, net, g_layers, want_x: bool = True, want_y: bool = True, want_layers: bool = False, workspace=None,
+              max_pairs: Optional[int] = None):
+    """snerf_lpips_bwd_f32 on frames x, y [N,3,H,W] of one set of strides (what _ssim_layout hands out): (dx, dy, layers), the
+    gradient of sum g_layers[n,l] layers[n,l] to the frames, laid out as they are, None where not wanted.  workspace as
+    ops.lpips_layers': a uint8 device tensor to run in, else one for min(N, max_pairs) pairs within LPIPS_WORKSPACE_BYTES (one
+    pair's need, where that is more).  The bits do not depend on it.  A plain function."""
+    if not (want_x or want_y):
+        raise RuntimeError("lpips_bwd: one of `want_x` and `want_y` at least")
+    for nm, t in (("x", x), ("y", y), ("g_layers", g_layers)):
+        _need_cuda(nm, t)
+    if x.dim() != 4 or x.shape != y.shape or x.shape[1] != 3 or x.stride() != y.stride():
+        raise RuntimeError(f"lpips_bwd: x and y must be [N,3,H,W] of one shape and one set of strides, got {tuple(x.shape)} / {x.stride()} and "
+                           f"{tuple(y.shape)} / {y.stride()}")
+    N, _, H, W = x.shape
+    if tuple(g_layers.shape) != (N, 5):
+        raise RuntimeError(f"lpips_bwd: g_layers must be [{N},5], got {tuple(g_layers.shape)}")
+    x, y, g_layers = x.detach(), y.detach(), g_layers.detach().float().contiguous()
+    rec = net.record(x.device)
+    lib = _lib.load()
+    if workspace is None:
+        fixed, one = (lib.snerf_lpips_bwd_workspace_bytes(k, H, W, rec.channels) for k in (0, 1))
+        if one < 0:
+            check(-1, "snerf_lpips_bwd_workspace_bytes")
+        pairs = max(1, min(N, (LPIPS_WORKSPACE_BYTES - fixed) // (one - fixed), max_pairs if max_pairs else N))
+        workspace = torch.empty((fixed + pairs * (one - fixed),), device=x.device, dtype=torch.uint8)
+    dx, dy = (torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32) if want else None for want in (want_x, want_y))
+    layers = torch.empty((N, 5), device=x.device, dtype=torch.float32) if want_layers else None
+    with torch.cuda.device(x.device), _lib.timed(f"lpips_bwd[{N}x{H}x{W}]"):
+        check(lib.snerf_lpips_bwd_f32(ctypes.byref(rec), ptr(x), ptr(y), N, H, W, *x.stride(), ptr(g_layers), ptr(dx), ptr(dy), ptr(layers),
+                                      ptr(workspace), workspace.numel(), current_stream()), "snerf_lpips_bwd_f32")
+    return dx, dy, layers
+
+
+class _LpipsLossFn(torch.autograd.Function):
+    """snerf_lpips_fwd_f32 / snerf_lpips_bwd_f32 under autograd: (layers [N,5], total [N]).  The frames are kept, no activation is:
+    the backward entry recomputes the forward chunk by chunk.  The net's weights are constants."""
+
+    @staticmethod
+    def forward(ctx, x, y, net):
+        layers, total = lpips_layers(x.detach(), y.detach(), net)
+        ctx.save_for_backward(x, y)
+        ctx.net = net
+        ctx.set_materialize_grads(False)
+        return layers, total
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_layers, g_total):
+        if g_layers is None and g_total is None:
+            return None, None, None
+        x, y = ctx.saved_tensors
+        # total = the sum of the five layers: its gradient reaches each of them
+        g = g_layers.float() if g_layers is not None else torch.zeros((x.shape[0], 5), device=x.device, dtype=torch.float32)
+        if g_total is not None:
+            g = g + g_total.float()[:, None]
+        dx, dy, _ = lpips_bwd(x, y, ctx.net, g, want_x=ctx.needs_input_grad[0], want_y=ctx.needs_input_grad[1])
+        return dx, dy, None
+
+
+def lpips_loss(x, y, net, reduction: str = 'mean', per_layer: bool = False):
+    """ops.lpips as a training loss: the same value, bit for bit (the forward is the same entry), and differentiable once with respect
+    to x and y - the reference's ContentLoss is a _Loss with frozen weights (util/scores.py:286-411).  The backward is one call of
+    snerf_lpips_bwd_f32: the VGG stack is walked forward and back chunk by chunk within LPIPS_WORKSPACE_BYTES, so no activation
+    outlives it.  Frames [N,3,H,W] fp32, channels-first or channels-last views without a copy; H, W >= 16.  The weights of `net` get no
+    gradient.  Under torch.no_grad(), or with no input that requires grad, this is ops.lpips."""
+    if reduction not in ('mean', 'sum', 'none'):
+        raise KeyError(reduction)
+    if not (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)):
+        return lpips(x, y, net, reduction=reduction, per_layer=per_layer)
+    _need_cuda("x", x)
+    _need_cuda("y", y)
+    if x.dim() != 4 or x.shape != y.shape or x.shape[1] != 3:
+        raise RuntimeError(f"lpips: x and y must be [N,3,H,W] of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.device != y.device:
+        raise RuntimeError(f"lpips: x on {x.device}, y on {y.device}")
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise RuntimeError(f"lpips_loss: fp32 frames, got {x.dtype} and {y.dtype}")
+    x, y = _ssim_layout(x, y)
+    layers, total = _LpipsLossFn.apply(x, y, net)
+    if reduction != 'none':
+        op = {'mean': torch.mean, 'sum': torch.sum}[reduction]
+        total, layers = op(total, dim=0), op(layers, dim=0)
+    return (total, layers) if per_layer else total
