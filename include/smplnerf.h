@@ -151,6 +151,42 @@ SNERF_API int snerf_composite_bwd_all_f32(const float *raw, const float *z, cons
                                 const float *d_weights, const float *d_alpha, float *d_raw, float *d_dirs /* nullable */,
                                 float *d_z /* nullable */, snerf_stream_t stream);
 
+/* ---- ray maps: opacity, expected depth and expected point of every ray (utils.py:184, :187) -------------------------
+ * The reference's raw2outputs computes depth_map = sum(weights * z_vals) and acc_map = sum(weights) and drops them; these two
+ * entries compute them, and the expected surface point, from what a compositing already returned, and carry a loss on them back
+ * to alpha.  alpha [B, N]: the alpha of snerf_composite_fwd_f32 (the `densities` of a pipeline); o, d [B, 3]: ray origins and
+ * directions; and exactly one of z [B, N] (the literal mode of utils.py:184) and pts [B, N, 3] (the sample points o + t d, for
+ * callers who hold no depths: the parameter is recovered from the points).  1 <= N <= 4096; B == 0 is a no-op.  o and d are read
+ * with pts only.  Per ray, operation by operation:
+ *   1. t_i = z_i ; with pts: t_i = ((p_i - o) . d) / (d . d), every operation in fp64 on the fp32 inputs, the three products
+ *      summed in x, y, z order; t_i = 0 where d . d == 0.
+ *   2. u_i = fl32(fl32(1 - alpha_i) + 1e-10f): the factor snerf_composite_fwd_f32 forms (utils.py:176).
+ *   3. T_i = prod_{j<i} u_j in fp64 (T_0 = 1), an exclusive prefix product in sample order.
+ *   4. w_i = fl32(alpha_i * fl32(T_i)): the bits snerf_composite_fwd_f32 stores as `weights` for the same alpha - the maps belong
+ *      to the weights the pipeline composited with.
+ *   5. acc = sum_i w_i, depth = sum_i w_i t_i, point = sum_i w_i p_i (point [B, 3]: nullable, with pts only): sums and products
+ *      in fp64, each result rounded to fp32 once.
+ * N == 1 is the rule as written: T_0 = 1, so acc = alpha_0 and depth = alpha_0 t_0 - with the alpha = 1 of the reference's early
+ * return (utils.py:170-171), acc = 1 and depth = t_0.  No disparity (commented out in the reference, NaN for an empty ray), no
+ * median depth.  Every element of acc, depth and point is written; no atomics, no allocation; the same bits for any split of the
+ * batch.  Added after 0.1.9 without a version bump: a C host finds the two entries with dlsym. */
+SNERF_API int snerf_ray_maps_fwd_f32(const float *alpha, const float *z /* nullable */, const float *pts /* nullable */,
+                                     const float *o, const float *d, int64_t B, int N, float *acc, float *depth,
+                                     float *point /* nullable; needs pts */, snerf_stream_t stream);
+
+/* Backward of the ray maps w.r.t. alpha: d_acc [B], d_depth [B], d_point [B, 3] (each nullable = zeros; d_point with pts only)
+ * -> d_alpha [B, N], overwritten.  With G_i = d_acc + d_depth t_i + <d_point, p_i>, T_i as above and w_i = alpha_i T_i (here
+ * unrounded), d u / d alpha = -1:
+ *   d_alpha_k = T_k G_k - S_k / u_k ,  S_k = sum_{i>k} w_i G_i
+ * everything in fp64 and rounded to fp32 once.  S_k is summed as an exclusive suffix (never "inclusive minus the own term": where
+ * alpha_k = 1, u_k = 1e-10 and the quotient would multiply that subtraction's rounding by 1e10).  t, p, o and d get no gradient
+ * (the hierarchical samples are detached in the reference, utils.py:260).  The result is what snerf_composite_bwd_all_f32 takes
+ * as d_alpha. */
+SNERF_API int snerf_ray_maps_bwd_f32(const float *alpha, const float *z /* nullable */, const float *pts /* nullable */,
+                                     const float *o, const float *d, int64_t B, int N, const float *d_acc /* nullable */,
+                                     const float *d_depth /* nullable */, const float *d_point /* nullable; needs pts */,
+                                     float *d_alpha, snerf_stream_t stream);
+
 /* ---- a5: inverse-CDF hierarchical sampling + merge + point generation ------------------------------
  * z [B, Nc] coarse depths (ascending), weights [B, Nc] from compositing, u [Nf] = linspace(0,1,Nf)
  * (passed in so that the caller controls its bits, see oracle/nerf_oracle.py:linspace01),

@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libsmplnerf_hip.so")
-SOURCES = ["api.hip", "searchsorted.hip", "posenc.hip", "composite.hip", "sampler.hip", "mlp.hip", "mlp_train.hip", "warp.hip", "raygen.hip", "mlp_bf16.hip", "render.hip", "mlp_train_bf16.hip", "warp_bf16.hip", "train_step.hip", "contract.hip", "mlp_lat.hip", "dp_comm.hip", "linear.hip", "vertex_warp.hip", "image_warp.hip", "gmm_pdf.hip", "smpl_lbs.hip", "ray_mesh.hip", "mesh_render.hip", "soft_silhouette.hip", "vertex_sphere.hip", "ssim.hip", "conv_block.hip", "conv_train.hip", "lpips.hip"]
+SOURCES = ["api.hip", "searchsorted.hip", "posenc.hip", "composite.hip", "sampler.hip", "mlp.hip", "mlp_train.hip", "warp.hip", "raygen.hip", "mlp_bf16.hip", "render.hip", "mlp_train_bf16.hip", "warp_bf16.hip", "train_step.hip", "contract.hip", "mlp_lat.hip", "dp_comm.hip", "linear.hip", "vertex_warp.hip", "image_warp.hip", "gmm_pdf.hip", "smpl_lbs.hip", "ray_mesh.hip", "mesh_render.hip", "soft_silhouette.hip", "vertex_sphere.hip", "ssim.hip", "conv_block.hip", "conv_train.hip", "lpips.hip", "ray_maps.hip"]
 HEADERS = ["exports.map", "snerf_common.h", "pair_walk.h", "mesh_tile.h", "ray_mesh_pair.h", "mlp_plan.h", "mlp_device.h", "mlp_bf16_device.h", "mlp_train_device.h", "mlp_wgrad_jobs.h", "mlp_lat_device.h", "warp_plan.h", "refsum.h", "ssim_tiles.h", "conv_block.h", os.path.join("..", "..", "include", "smplnerf.h")]
 # -fvisibility=hidden: the SNERF_API entry points of include/smplnerf.h are the library's only dynamic symbols
 # -ffp-contract=off: the HBM-bound ops reproduce the reference's eager (unfused) fp32 op order.

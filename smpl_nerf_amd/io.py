@@ -105,6 +105,24 @@ def mse2psnr(mse: float) -> float:
     return float(-10.0 * np.log10(mse))
 
 
+def depth_error(depth, reference_depth, mask=None):
+    """(mean, maximum) of |depth - reference_depth| over the pixels where the reference has a depth: non-zero and finite (a miss
+    is 0 in SingleSampleRays.depth and +inf in ops.render_mesh's t), and inside `mask` where one is given.  Arrays or tensors of
+    one shape (a tensor on a device is copied to the host); (nan, nan) when no pixel qualifies."""
+    def host(x):
+        return np.asarray(x.detach().cpu() if hasattr(x, "detach") else x, np.float64)
+    d, r = host(depth), host(reference_depth)
+    if d.shape != r.shape:
+        raise ValueError(f"depth_error: depth {d.shape} and reference_depth {r.shape} differ in shape")
+    keep = np.isfinite(r) & (r != 0)
+    if mask is not None:
+        keep &= host(mask).reshape(r.shape) != 0
+    if not keep.any():
+        return float("nan"), float("nan")
+    diff = np.abs(d[keep] - r[keep])
+    return float(diff.mean()), float(diff.max())
+
+
 def to_uint8_rgb(rgb_bgr_float) -> np.ndarray:
     """inference.py:261-263: clip to [0,1], *255, BGR -> RGB for saving."""
     img = np.clip(np.asarray(rgb_bgr_float), 0, 1) * 255

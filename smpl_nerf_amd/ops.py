@@ -4,7 +4,8 @@ HIP library (include/smplnerf.h).  Reference counterparts:
     searchsorted        torchsearchsorted/src/torchsearchsorted/searchsorted.py:20-53
     PositionalEncoder   utils.py:114-131
     raw2outputs         utils.py:134-191
-    sample_pdf          utils.py:194-228
+    ray_maps            utils.py:184, :187 (depth_map and acc_map, which raw2outputs computes and drops) and the expected point
+    sample_pdf         utils.py:194-228
     fine_sampling       utils.py:231-264
     vertex_attention_warp   models/dynamic_pipeline.py:51-70 (the attention warp of DynamicPipeline as one operator)
     GaussianMixture / gaussian_mixture_pdf   utils.py:72-111 (the canonical-density term of SmplNerfSolver's loss)
@@ -244,6 +245,82 @@ def raw2outputs(raw: torch.Tensor, z_vals: torch.Tensor, samples_directions: tor
     if z_vals.shape[-1] > 1 and args.sigma_noise_std > 0.:
         noise = torch.normal(0, args.sigma_noise_std, raw[..., 3].shape, device=raw.device)
     return composite(raw, z_vals, samples_directions, bool(args.white_background), noise)
+
+
+# ------------------------------------------------------------------------------------------------
+# ray maps: acc_map, depth_map (utils.py:184, :187) and the expected point
+# ------------------------------------------------------------------------------------------------
+RayMaps = collections.namedtuple("RayMaps", "acc depth point")
+
+
+class _RayMapsFn(torch.autograd.Function):
+    """ray_maps() under autograd: snerf_ray_maps_fwd_f32 forward, snerf_ray_maps_bwd_f32 backward, differentiable in alpha alone
+    (the sample positions are detached in the reference, utils.py:260).  Its d alpha is what _CompositeFn takes as d_a."""
+
+    @staticmethod
+    def forward(ctx, alpha, o, d, z_vals, samples):
+        ctx.save_for_backward(alpha, o, d, z_vals, samples)
+        ctx.set_materialize_grads(False)
+        return _ray_maps_launch(alpha, o, d, z_vals, samples)
+
+    @staticmethod
+    def backward(ctx, d_acc, d_depth, d_point):
+        alpha, o, d, z_vals, samples = ctx.saved_tensors
+        if d_acc is None and d_depth is None and d_point is None:
+            return (None,) * 5
+        B, N = alpha.shape
+        d_acc, d_depth, d_point = (None if g is None else g.contiguous().float() for g in (d_acc, d_depth, d_point))
+        d_alpha = torch.empty_like(alpha)
+        if B == 0:
+            return d_alpha, None, None, None, None
+        lib = _lib.load()
+        with torch.cuda.device(alpha.device), _lib.timed(f"ray_maps_bwd[N={N}]"):
+            check(lib.snerf_ray_maps_bwd_f32(ptr(alpha), ptr(z_vals), ptr(samples), ptr(o), ptr(d), B, N, ptr(d_acc), ptr(d_depth),
+                                             ptr(d_point), ptr(d_alpha), current_stream()), "snerf_ray_maps_bwd_f32")
+        return d_alpha, None, None, None, None
+
+
+def ray_maps(alpha, ray_translation, ray_direction, z_vals=None, samples=None) -> RayMaps:
+    """The maps raw2outputs computes and drops (utils.py:184, :187) and the expected point, from the per-sample alpha [B, N] of a
+    compositing (composite()'s third result, a pipeline's `densities`): RayMaps(acc [B] = sum of the weights, depth [B] = sum of
+    weights * t, point [B, 3] = sum of weights * samples, or None without samples).  Exactly one of z_vals [B, N] (t = z_vals, the
+    reference's expression) and samples [B, N, 3] (t = ((p - o) . d) / (d . d): for callers who hold the points o + t d but not
+    the depths, like the results of a pipeline).  The weights are rebuilt from alpha with the compositing kernel's own rounding
+    (include/smplnerf.h).  Differentiable in alpha: a loss on depth or acc reaches the nets through composite()'s alpha."""
+    for nm, t in (("alpha", alpha), ("ray_translation", ray_translation), ("ray_direction", ray_direction), ("z_vals", z_vals),
+                  ("samples", samples)):
+        if t is not None:
+            _need_cuda(nm, t)
+    if (z_vals is None) == (samples is None):
+        raise RuntimeError("ray_maps: exactly one of z_vals and samples must be given")
+    if alpha.dim() != 2:
+        raise RuntimeError(f"ray_maps: alpha must be [B, N], got {tuple(alpha.shape)}")
+    B, N = alpha.shape
+    for nm, t, shape in (("ray_translation", ray_translation, (B, 3)), ("ray_direction", ray_direction, (B, 3)),
+                         ("z_vals", z_vals, (B, N)), ("samples", samples, (B, N, 3))):
+        if t is not None and tuple(t.shape) != shape:
+            raise RuntimeError(f"ray_maps: {nm} of shape {tuple(t.shape)} does not match alpha [B={B}, N={N}]: expected {shape}")
+    alpha, o, d = alpha.contiguous(), ray_translation.detach().contiguous(), ray_direction.detach().contiguous()
+    z_vals = None if z_vals is None else z_vals.detach().contiguous()
+    samples = None if samples is None else samples.detach().contiguous()
+    if torch.is_grad_enabled() and alpha.requires_grad:
+        return RayMaps(*_RayMapsFn.apply(alpha, o, d, z_vals, samples))
+    return RayMaps(*_ray_maps_launch(alpha.detach(), o, d, z_vals, samples))
+
+
+def _ray_maps_launch(alpha, o, d, z_vals, samples):
+    B, N = alpha.shape
+    dev = alpha.device
+    acc = torch.empty((B,), device=dev, dtype=torch.float32)
+    depth = torch.empty((B,), device=dev, dtype=torch.float32)
+    point = torch.empty((B, 3), device=dev, dtype=torch.float32) if samples is not None else None
+    if B == 0:      # (an empty tensor has no address to tell z_vals from samples by)
+        return acc, depth, point
+    lib = _lib.load()
+    with torch.cuda.device(dev), _lib.timed(f"ray_maps_fwd[N={N}]"):
+        check(lib.snerf_ray_maps_fwd_f32(ptr(alpha), ptr(z_vals), ptr(samples), ptr(o), ptr(d), B, N, ptr(acc), ptr(depth),
+                                         ptr(point), current_stream()), "snerf_ray_maps_fwd_f32")
+    return acc, depth, point
 
 
 # ------------------------------------------------------------------------------------------------

@@ -260,6 +260,17 @@ class NerfPipeline(nn.Module):
             return tuple(r.outs)
         return r.outs[0], r.outs[0], data[0], r.outs[-1]
 
+    def ray_maps(self, data, out):
+        """The opacity, the expected depth and the expected point of every ray of `data` from out = forward(data):
+        ops.RayMaps(acc [B], depth [B], point [B, 3]) - the acc_map and depth_map the reference's raw2outputs computes and drops
+        (utils.py:184, :187), of the compositing whose colour is out[1].  Reads the `samples` and `densities` of the 4-tuple or of
+        the 6-tuple (with a warp stage: the un-warped samples, on the ray) and the ray's origin and direction, data[1] and data[2].
+        `depth` is the ray parameter t of o + t d: with the generated rays (raygen, d = a camera-space direction of z = -1) the
+        z-depth ops.render_mesh returns as `t`; depth * |d| is the Euclidean distance single_sample.SingleSampleRays.depth holds.
+        Differentiable in the densities: under autograd a loss on depth or acc trains the nets."""
+        samples, densities = (out[2], out[3]) if len(out) == 4 else (out[3], out[5])
+        return ops.ray_maps(densities, data[1], data[2], samples=samples)
+
     def _single_call(self, data):
         """snerf_render_rays_f32."""
         r = self._render_setup(data, (self.model_coarse, self.model_fine), "snerf_render_rays_workspace_bytes")
@@ -512,6 +523,14 @@ class SingleSamplePipeline(NerfPipeline):
                                               self.direction_encoder)                              # :30-38
         rgb = torch.sigmoid(raw[..., :3])                                                          # :39
         return rgb, rgb                                                                            # :40
+
+    def ray_maps(self, data, out):
+        """NerfPipeline.ray_maps for the one sample of every ray: there is no density, so alpha = 1 as in raw2outputs' early
+        return for a single sample (utils.py:170-171) - acc = 1, depth = the parameter of the un-warped sample data[0] on its ray
+        (depth * |d|: SingleSampleRays.depth where the ray hits, the far bound where it misses), point = that sample."""
+        ray_sample = data[0]
+        ones = torch.ones((ray_sample.shape[0], 1), device=ray_sample.device, dtype=torch.float32)
+        return ops.ray_maps(ones, data[1], data[2], samples=ray_sample[:, None, :])
 
 
 class AppendSmplParamsPipeline(NerfPipeline):

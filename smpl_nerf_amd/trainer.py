@@ -793,6 +793,26 @@ class DataParallelTrainer:
                 scores = ops.image_scores(r.reshape(-1, h, w, 3), t.reshape(-1, h, w, 3), lpips=lpips, **ssim_kwargs)
         return val_loss, scores
 
+    @torch.no_grad()
+    def validate_maps(self, val_loader, h: int, w: int):
+        """validate()'s renders with the pictures a ray march gives beside the colour: {"rgb" [F,h,w,3] (rgb_fine), "depth" [F,h,w],
+        "acc" [F,h,w]} on the device, depth and acc from pipeline.ray_maps (the depth_map and acc_map of utils.py:184, :187).  The
+        loader has to cover whole frames of h x w rays, in order.  "depth" is what io.depth_error compares with a mesh depth."""
+        for m in self.models:
+            m.eval()
+        rgb, depth, acc = [], [], []
+        for data in val_loader:
+            out = self.pipeline(data)
+            maps = self.pipeline.ray_maps(data, out)
+            rgb.append(out[1].detach())
+            depth.append(maps.depth)
+            acc.append(maps.acc)
+        n = sum(int(t.shape[0]) for t in depth)
+        if not n or n % (h * w):
+            raise ValueError(f"validate_maps: the loader gave {n} rays, not whole frames of {h} x {w}")
+        return {"rgb": torch.cat(rgb).reshape(-1, h, w, 3), "depth": torch.cat(depth).reshape(-1, h, w),
+                "acc": torch.cat(acc).reshape(-1, h, w)}
+
     def save_checkpoint(self, save_dir: str, model_names, epoch: int, history=None):
         """utils.save_run's per-model state_dict files (utils.py:282-283), plus what the reference does not keep: the
         optimiser state and the epoch counter, so that a run can be resumed.  Rank 0 writes."""
